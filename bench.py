@@ -2,7 +2,8 @@
 """bench.py -- forward+backward views/sec of the GeoSplatting render path on MI355X.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
-prints ONE JSON line on rank 0.
+prints ONE JSON line on rank 0.  --dump-outputs DIR also writes the gradients of the last timed step as .npy files (inputs are
+seeded: the same arguments give the same inputs in every run, so two builds can be compared output for output).
 
 Workload (BASELINE.json `metric`: "fwd+bwd views/sec at 2M Gaussians, 800x800"):
   synthetic surface splats = MGAdapter restatement on a bumpy icosphere level 7 -> 1 966 080 Gaussians, 800x800,
@@ -59,7 +60,55 @@ def parse():
     ap.add_argument("--rccl-world1", action="store_true",
                     help="diagnostic: run the step with EVERY collective of the multi-GPU path through RCCL on a one-rank process group "
                          "(sharded prefilter + its communicator, two-phase gradient all-reduce, graph replay beside them)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the gradients the last timed step returned as DIR/grad_<name>.npy (float32, at most "
+                         "64 MB in all: per-Gaussian gradients are cut to one fixed, seeded sample of rows, listed in DIR/gaussian_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and 6 * args.cubemap_res ** 2 * 3 * 4 > DUMP_LIMIT_BYTES // 2:
+        ap.error("--dump-outputs: the cubemap gradient alone would take more than half of the 64 MB")
+    return args
+
+
+DUMP_LIMIT_BYTES = 60_000_000       # array data; with the .npy headers the files stay below 64 MB (10^6 or 2^20 bytes)
+
+
+def dump_outputs(out_dir, grads, n_gauss):
+    """--dump-outputs: `grads` (host float32 arrays) -> out_dir/grad_<name>.npy.  Arrays with one row per Gaussian share one
+    sample of rows (seeded, so the same for every run of the same workload) sized to keep the files within DUMP_LIMIT_BYTES."""
+    import numpy as np
+    arrs = {f"grad_{k}": v for k, v in grads.items()}
+    per_g = [k for k, a in arrs.items() if a.ndim >= 1 and a.shape[0] == n_gauss]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        rest = total - sum(arrs[k].nbytes for k in per_g)
+        row_bytes = sum(arrs[k].nbytes // n_gauss for k in per_g) + 8          # (+ the row index, float64)
+        n_rows = (DUMP_LIMIT_BYTES - rest) // row_bytes
+        assert n_rows >= 1, "--dump-outputs: no room left for per-Gaussian rows"
+        rows = np.sort(np.random.default_rng(20240101).permutation(n_gauss)[:n_rows])
+        arrs = {k: (a[rows] if k in per_g else a) for k, a in arrs.items()}
+        arrs["gaussian_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+
+
+def scene_mesh_to_splats(dev):
+    """The HIP MGAdapter on vertex normals summed on the host in a fixed order: the scene, and so every input of the step, is
+    the same bits in every run (the HIP vertex-normal kernel sums the face normals with float atomics, in no fixed order)."""
+    from geosplatting_amd.mesh import mesh_to_splats
+
+    def build(v, f):
+        p = v[f]                                                               # [F,3 corners,3]
+        fn = torch.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+        raw = torch.zeros_like(v).index_add_(0, f.reshape(-1), fn.repeat_interleave(3, dim=0))
+        l = raw.norm(dim=-1, keepdim=True)
+        vn = torch.where(l > 1e-10, raw / l.clamp_min(1e-10), torch.tensor([0.0, 0.0, 1.0]))
+        with torch.no_grad():
+            sp, normals = mesh_to_splats(v.to(dev), f.to(dev), vn.to(dev).contiguous())
+        return sp.means.cpu(), sp.scales.cpu(), sp.quats.cpu(), sp.opacities.cpu(), normals.cpu()
+    return build
 
 
 def algorithmic_bytes_per_view(N, V, I, P, E):
@@ -496,7 +545,7 @@ def main():
     if world != args.gpus and rank == 0:
         print(f"[bench] warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
     torch.manual_seed(1)
-    scene = syn.sphere_scene(args.level, seed=1, cubemap_res=args.cubemap_res, device=dev)
+    scene = syn.sphere_scene(args.level, seed=1, cubemap_res=args.cubemap_res, mesh_to_splats_fn=scene_mesh_to_splats(dev))
     N = scene.splats.num
     strong = not args.weak
     views_total = (args.views_total or args.views) if strong else args.views * world
@@ -508,7 +557,7 @@ def main():
     ups = [(torch.rand(args.res, args.res, 4, generator=g) * 2 - 1).to(dev) for _ in range(max(1, len(cams)))]
 
     def one_step():
-        step(cams, lambda i, img: ups[i], all_reduce=use_coll)
+        return step(cams, lambda i, img: ups[i], all_reduce=use_coll)
 
     n_settle = 0
     if args.settle_seconds > 0 and len(cams) > 0:          # clocks / allocator / capacity settle; identical on every rank (fixed step count)
@@ -548,11 +597,15 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step returned (views into the gradient bucket, which the steps below overwrite): copied now
+    dumped = None
+    if args.dump_outputs and rank == 0 and len(cams) > 0:
+        dumped = {k: v.detach().float().cpu().numpy() for k, v in last[0].items()}
     # capacity protocol: the timed steps ran without any (V, I) read-back if a capacity was known before them (default: learnt in
     # the warm-up); an overflow in any of them would make the number invalid -- checked here, outside the timed region
     cap_ok = graphed.check() if graphed is not None else step.poll_capacity(wait=True)
@@ -621,6 +674,9 @@ def main():
     dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     views_per_s = views_total * args.steps / dt
+
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, N)
 
     # ---------------- measurements for the roofline objects (rank 0, one representative view)
     result = None
