@@ -1,6 +1,6 @@
 // gs_project.hip -- per-Gaussian stages of the rasterizer half of the path (gfx950):
 //   A1  fused projection + cull + anti-alias compensation, packed by a single-pass chained scan
-//   A1' opacity*compensation and colour gather
+//   A1' opacity*compensation and colour gather (or, for gs_project_fwd_vis_ex, spherical-harmonics colours / 'classic' opacities)
 //   A2  tiles-per-Gaussian, inclusive tile cumsum, key/value emission
 //   A4  per-tile offsets
 //   A7  projection backward + gather backward
@@ -34,6 +34,220 @@ extern "C" int gs_version(void) { return 100; }
 #include "gs_project_dev.h"
 #pragma clang fp contract(off)
 
+// ---------------------------------------------------------------------------------------------------
+// Spherical-harmonics colour of one Gaussian, gsplat 1.4 semantics (rendering.py with sh_degree set, packed, one camera):
+//   dir = normalize(mean - campos), campos = inverse(viewmat)[:3, 3] = -R^T t (rigid view matrix),
+//   c   = sum_{k < (d+1)^2} basis_k(dir) * coeffs[k, :]   (the real SH basis of 3DGS, gsplat's polynomial "fast" form),
+//   rgb = max(c + 0.5, 0).
+// Coefficients k >= (d+1)^2 of a row of K are not read.  Degrees 0..3.  A colour, not a sort key: contraction ON here.
+__device__ __forceinline__ void sh_campos(const GsCam& cam, float* cp)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cp[i] = -(cam.R[0 * 3 + i] * cam.t[0] + cam.R[1 * 3 + i] * cam.t[1] + cam.R[2 * 3 + i] * cam.t[2]);
+}
+
+template <int DEG>
+__device__ __forceinline__ void sh_basis(float x, float y, float z, float* b)
+{
+#pragma clang fp contract(fast)
+    b[0] = 0.2820947917738781f;
+    if constexpr (DEG >= 1) {
+        b[1] = -0.48860251190292f * y; b[2] = 0.48860251190292f * z; b[3] = -0.48860251190292f * x;
+    }
+    if constexpr (DEG >= 2) {
+        const float z2 = z * z, fTmp0B = -1.092548430592079f * z, fC1 = x * x - y * y, fS1 = 2.f * x * y;
+        b[4] = 0.5462742152960395f * fS1;
+        b[5] = fTmp0B * y;
+        b[6] = 0.9461746957575601f * z2 - 0.3153915652525201f;
+        b[7] = fTmp0B * x;
+        b[8] = 0.5462742152960395f * fC1;
+        if constexpr (DEG >= 3) {
+            const float fTmp0C = -2.285228997322329f * z2 + 0.4570457994644658f, fTmp1B = 1.445305721320277f * z;
+            const float fC2 = x * fC1 - y * fS1, fS2 = x * fS1 + y * fC1;
+            b[9] = -0.5900435899266435f * fS2;
+            b[10] = fTmp1B * fS1;
+            b[11] = fTmp0C * y;
+            b[12] = z * (1.865881662950577f * z2 - 1.119528997770346f);
+            b[13] = fTmp0C * x;
+            b[14] = fTmp1B * fC1;
+            b[15] = -0.5900435899266435f * fC2;
+        }
+    }
+}
+
+// v_xyz += sum_k vb[k] * d basis_k / d(x, y, z)  (x, y, z taken as independent: the normalisation is chained by the caller)
+template <int DEG>
+__device__ __forceinline__ void sh_basis_vjp(float x, float y, float z, const float* vb, float& vx, float& vy, float& vz)
+{
+#pragma clang fp contract(fast)
+    if constexpr (DEG >= 1) {
+        const float C1 = 0.48860251190292f;
+        vx += -C1 * vb[3]; vy += -C1 * vb[1]; vz += C1 * vb[2];
+    }
+    if constexpr (DEG >= 2) {
+        const float A = 1.092548430592079f, B = 0.5462742152960395f;
+        vx += A * y * vb[4] - A * z * vb[7] + 2.f * B * x * vb[8];
+        vy += A * x * vb[4] - A * z * vb[5] - 2.f * B * y * vb[8];
+        vz += -A * y * vb[5] + 2.f * 0.9461746957575601f * z * vb[6] - A * x * vb[7];
+        if constexpr (DEG >= 3) {
+            const float E = -0.5900435899266435f, F = 1.445305721320277f, G = -2.285228997322329f, H0 = 0.4570457994644658f;
+            const float xx = x * x, yy = y * y, zz = z * z;
+            const float fTmp0C = G * zz + H0;
+            vx += E * 6.f * x * y * vb[9] + F * 2.f * y * z * vb[10] + fTmp0C * vb[13] + F * 2.f * x * z * vb[14]
+                + E * 3.f * (xx - yy) * vb[15];
+            vy += E * 3.f * (xx - yy) * vb[9] + F * 2.f * x * z * vb[10] + fTmp0C * vb[11] - F * 2.f * y * z * vb[14]
+                - E * 6.f * x * y * vb[15];
+            vz += F * 2.f * x * y * vb[10] + 2.f * G * z * y * vb[11] + (3.f * 1.865881662950577f * zz - 1.119528997770346f) * vb[12]
+                + 2.f * G * z * x * vb[13] + F * (xx - yy) * vb[14];
+        }
+    }
+}
+
+// the (d+1)^2 * 3 leading floats of a coefficient row; vec: every row starts 16-byte aligned (K * 3 % 4 == 0, aligned base)
+template <int NF>
+__device__ __forceinline__ void sh_load_row(const float* __restrict__ row, bool vec, float* co)
+{
+    if (vec) {
+#pragma unroll
+        for (int i = 0; i < NF / 4; ++i) {
+            const float4 q = *reinterpret_cast<const float4*>(row + 4 * i);
+            co[4 * i] = q.x; co[4 * i + 1] = q.y; co[4 * i + 2] = q.z; co[4 * i + 3] = q.w;
+        }
+#pragma unroll
+        for (int i = NF / 4 * 4; i < NF; ++i) co[i] = row[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) co[i] = row[i];
+    }
+}
+
+// dir (unnormalised), its unit vector and 1/|dir|
+__device__ __forceinline__ void sh_dir(const GsCam& cam, const float* mean, float& x, float& y, float& z, float& inorm)
+{
+#pragma clang fp contract(fast)
+    float cp[3];
+    sh_campos(cam, cp);
+    const float dx = mean[0] - cp[0], dy = mean[1] - cp[1], dz = mean[2] - cp[2];
+    inorm = rsqrtf(dx * dx + dy * dy + dz * dz);
+    x = dx * inorm; y = dy * inorm; z = dz * inorm;
+}
+
+template <int DEG>
+__device__ __forceinline__ void sh_color_deg(float x, float y, float z, const float* co, float* c)
+{
+#pragma clang fp contract(fast)
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    float b[NB];
+    sh_basis<DEG>(x, y, z, b);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float acc = b[0] * co[ch];
+#pragma unroll
+        for (int k = 1; k < NB; ++k) acc += b[k] * co[3 * k + ch];
+        c[ch] = acc;                                      // before the + 0.5 and the clamp
+    }
+}
+
+template <int DEG>
+__device__ __forceinline__ void sh_color_row(const GsCam& cam, const float* mean, const float* __restrict__ row, bool vec, float* rgb)
+{
+    constexpr int NF = (DEG + 1) * (DEG + 1) * 3;
+    float co[NF], c[3];
+    sh_load_row<NF>(row, vec, co);
+    float x = 0.f, y = 0.f, z = 0.f, inorm = 0.f;
+    if constexpr (DEG >= 1) sh_dir(cam, mean, x, y, z, inorm);
+    sh_color_deg<DEG>(x, y, z, co, c);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rgb[ch] = fmaxf(c[ch] + 0.5f, 0.0f);
+}
+
+__device__ __forceinline__ bool sh_row_vec(const float* sh_coeffs, int sh_K)
+{
+    return (sh_K * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(sh_coeffs) & 15) == 0;
+}
+
+__device__ __forceinline__ void sh_color(const GsCam& cam, const float* mean, const float* __restrict__ row, int sh_K, int degree,
+                                         float* rgb)
+{
+    const bool vec = sh_row_vec(row, sh_K);
+    switch (degree) {
+    case 0:  sh_color_row<0>(cam, mean, row, vec, rgb); break;
+    case 1:  sh_color_row<1>(cam, mean, row, vec, rgb); break;
+    case 2:  sh_color_row<2>(cam, mean, row, vec, rgb); break;
+    default: sh_color_row<3>(cam, mean, row, vec, rgb); break;
+    }
+}
+
+// Backward of one Gaussian's SH colour: v_rgb = the compositor's colour gradient.  Writes the whole coefficient row
+// g_row[K * 3] (basis_k * v_c where the clamp passed -- torch's clamp_min rule, c + 0.5 >= 0 -- zero for k >= (d+1)^2) and adds the
+// direction term (chained through the normalisation) to v_mean.  visible == false writes a zero row.
+template <int DEG>
+__device__ __forceinline__ void sh_color_bwd_row(const GsCam& cam, const float* mean, const float* __restrict__ row, int sh_K, bool vec,
+                                                 bool visible, const float* v_rgb, float* __restrict__ g_row, float* v_mean)
+{
+#pragma clang fp contract(fast)
+    constexpr int NB = (DEG + 1) * (DEG + 1), NF = NB * 3;
+    float g[NF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) g[i] = 0.0f;
+    if (visible) {
+        float co[NF], c[3], b[NB];
+        sh_load_row<NF>(row, vec, co);
+        float x = 0.f, y = 0.f, z = 0.f, inorm = 0.f;
+        if constexpr (DEG >= 1) sh_dir(cam, mean, x, y, z, inorm);
+        sh_color_deg<DEG>(x, y, z, co, c);
+        sh_basis<DEG>(x, y, z, b);
+        float vc[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) vc[ch] = (c[ch] + 0.5f >= 0.0f) ? v_rgb[ch] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < NB; ++k)
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) g[3 * k + ch] = b[k] * vc[ch];
+        if constexpr (DEG >= 1) {
+            float vb[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) vb[k] = co[3 * k] * vc[0] + co[3 * k + 1] * vc[1] + co[3 * k + 2] * vc[2];
+            float vx = 0.f, vy = 0.f, vz = 0.f;
+            sh_basis_vjp<DEG>(x, y, z, vb, vx, vy, vz);
+            const float dotp = vx * x + vy * y + vz * z;
+            v_mean[0] += (vx - dotp * x) * inorm;
+            v_mean[1] += (vy - dotp * y) * inorm;
+            v_mean[2] += (vz - dotp * z) * inorm;
+        }
+    }
+    const int nf = sh_K * 3;
+    if (vec) {
+#pragma unroll
+        for (int i = 0; i < NF / 4; ++i)
+            *reinterpret_cast<float4*>(g_row + 4 * i) = make_float4(g[4 * i], g[4 * i + 1], g[4 * i + 2], g[4 * i + 3]);
+#pragma unroll
+        for (int i = NF / 4 * 4; i < NF; ++i) g_row[i] = g[i];
+        int i = NF;
+        for (; i < nf && (i & 3); ++i) g_row[i] = 0.0f;
+        for (; i + 4 <= nf; i += 4) *reinterpret_cast<float4*>(g_row + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (; i < nf; ++i) g_row[i] = 0.0f;
+    } else {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) g_row[i] = g[i];
+        for (int i = NF; i < nf; ++i) g_row[i] = 0.0f;
+    }
+}
+
+__device__ __forceinline__ void sh_color_bwd(const GsCam& cam, const float* mean, const float* __restrict__ row, int sh_K, int degree,
+                                             bool visible, const float* v_rgb, float* __restrict__ g_row, float* v_mean)
+{
+    const bool vec = sh_row_vec(row, sh_K) && (reinterpret_cast<uintptr_t>(g_row) & 15) == 0;
+    switch (degree) {
+    case 0:  sh_color_bwd_row<0>(cam, mean, row, sh_K, vec, visible, v_rgb, g_row, v_mean); break;
+    case 1:  sh_color_bwd_row<1>(cam, mean, row, sh_K, vec, visible, v_rgb, g_row, v_mean); break;
+    case 2:  sh_color_bwd_row<2>(cam, mean, row, sh_K, vec, visible, v_rgb, g_row, v_mean); break;
+    default: sh_color_bwd_row<3>(cam, mean, row, sh_K, vec, visible, v_rgb, g_row, v_mean); break;
+    }
+}
+
+// A1 + A1' (the statements are in gs_project_fwd_body.inc): project_fwd_kernel is the plain instance, project_fwd_ex_kernel<SH, CLASSIC>
+// the variants of gs_project_fwd_vis_ex.
 
 __global__ void __launch_bounds__(GS_PROJ_BLOCK)
 project_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict__ quats,
@@ -48,127 +262,28 @@ project_fwd_kernel(int N, const float* __restrict__ means, const float* __restri
                    int32_t* __restrict__ packed_index,
                    unsigned* __restrict__ ctrl, u64* __restrict__ desc, int n_chunks, int64_t* __restrict__ counts, float4* __restrict__ vis)
 {
-    __shared__ int s_chunk;
-    __shared__ int s_wv[GS_PROJ_WAVES];
-    __shared__ int s_wi[GS_PROJ_WAVES];
-    __shared__ long long s_base[2];
+    constexpr bool SH = false, CLASSIC = false;           // the <false, false> instance of project_fwd_ex_kernel
+    [[maybe_unused]] const float* const sh_coeffs = nullptr;
+    [[maybe_unused]] const int sh_K = 0, sh_degree = -1;
+#include "gs_project_fwd_body.inc"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_chunk = (int)atomicAdd(ctrl, 1u);
-    __syncthreads();
-    const int chunk = s_chunk;
-    const int n = chunk * GS_PROJ_BLOCK + tid;
-
-    u64* agg_v = desc;
-    u64* agg_i = desc + n_chunks;
-    u64* pre_v = desc + 2 * (size_t)n_chunks;
-    u64* pre_i = desc + 3 * (size_t)n_chunks;
-
-    GsCam cam = load_cam(viewmat, K);
-    ProjFwd p;
-    p.valid = false; p.radius = 0;
-    int ntiles = 0;
-    int tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
-    if (n < N) {
-        float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
-        float4 q = *reinterpret_cast<const float4*>(quats + 4 * (size_t)n);
-        float quat[4] = { q.x, q.y, q.z, q.w };
-        float scale[3] = { scales[3 * (size_t)n], scales[3 * (size_t)n + 1], scales[3 * (size_t)n + 2] };
-        p = project_exact(cam, mean, quat, scale, (float)W, (float)H, eps2d, near_plane, far_plane, radius_clip);
-        if (p.valid) {
-            tile_range_exact(p.m2x, p.m2y, p.radius, tile_size, tile_w, tile_h, tx0, ty0, tx1, ty1);
-            ntiles = (tx1 - tx0) * (ty1 - ty0);
-        }
-    }
-
-    // ---- block-level scan of (valid, ntiles)
-    const u64 bal = __ballot(p.valid);
-    const int v_excl_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    int i_incl = ntiles;
-    i_incl = gs_wave_incl_scan(i_incl);
-    if (lane == 63) { s_wv[wave] = __popcll(bal); s_wi[wave] = i_incl; }
-    __syncthreads();
-    int v_before = 0, i_before = 0, aggV = 0, aggI = 0;
-#pragma unroll
-    for (int w = 0; w < GS_PROJ_WAVES; ++w) {
-        if (w < wave) { v_before += s_wv[w]; i_before += s_wi[w]; }
-        aggV += s_wv[w]; aggI += s_wi[w];
-    }
-
-    // ---- decoupled look-back across chunks (wave 0)
-    if (wave == 0) {
-        long long baseV = 0, baseI = 0;
-        if (chunk > 0) {
-            if (lane == 0) { desc_store(&agg_v[chunk], (u64)aggV); desc_store(&agg_i[chunk], (u64)aggI); }
-            int pos = chunk - 1;
-            for (;;) {
-                const int idx = pos - lane;
-                bool isP = idx < 0;           // virtual predecessors before chunk 0: prefix 0
-                bool isA = false;
-                u64 pv = 0, pi = 0, av = 0, ai = 0;
-                if (idx >= 0) {
-                    int spins = 0;
-                    for (;;) {
-                        pv = desc_load(&pre_v[idx]); pi = desc_load(&pre_i[idx]);
-                        isP = (pv & pi & GS_VALID_BIT) != 0;
-                        if (isP) break;
-                        av = desc_load(&agg_v[idx]); ai = desc_load(&agg_i[idx]);
-                        isA = (av & ai & GS_VALID_BIT) != 0;
-                        if (isA) break;
-                        if (++spins > GS_SPIN_LIMIT) { atomicExch(ctrl + 1, 1u); isA = true; av = ai = 0; break; }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                }
-                const u64 pmask = __ballot(isP);
-                const int first = pmask ? __builtin_ctzll(pmask) : 64;
-                long long cv = 0, ci = 0;
-                if (lane <= first) {
-                    cv = (long long)((isP ? pv : av) & ~GS_VALID_BIT);
-                    ci = (long long)((isP ? pi : ai) & ~GS_VALID_BIT);
-                }
-                baseV += wave_sum_i64(cv);
-                baseI += wave_sum_i64(ci);
-                if (pmask) break;
-                pos -= 64;
-            }
-        }
-        if (lane == 0) {
-            desc_store(&pre_i[chunk], (u64)(baseI + aggI));
-            desc_store(&pre_v[chunk], (u64)(baseV + aggV));
-            s_base[0] = baseV; s_base[1] = baseI;
-            if (chunk == n_chunks - 1) { counts[0] = baseV + aggV; counts[1] = baseI + aggI; }
-        }
-    }
-    __syncthreads();
-    const long long baseV = s_base[0], baseI = s_base[1];
-
-    if (n < N) {
-        const long long slot = baseV + v_before + v_excl_wave;
-        if (packed_index) packed_index[n] = p.valid ? (int32_t)slot : -1;
-        if (p.valid) {
-            gaussian_ids[slot] = n;
-            radii[slot] = p.radius;
-            *reinterpret_cast<float2*>(means2d + 2 * slot) = make_float2(p.m2x, p.m2y);
-            depths[slot] = p.depth;
-            conics[3 * slot] = p.ca; conics[3 * slot + 1] = p.cb; conics[3 * slot + 2] = p.cc;
-            compensations[slot] = p.comp;
-            opacities_packed[slot] = opacities[n] * p.comp;
-            tiles_per_gauss[slot] = ntiles;
-            cum_tiles[slot] = baseI + i_before + i_incl;
-            if (colors_packed) {
-                for (int k = 0; k < D; ++k) colors_packed[slot * D + k] = colors[(size_t)n * D + k];
-            }
-            if (vis) {                                       // the compositor's per-visible record, straight from the registers
-                float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-                if (colors && D <= 3) {
-                    c0 = colors[(size_t)n * D];
-                    if (D > 1) c1 = colors[(size_t)n * D + 1];
-                    if (D > 2) c2 = colors[(size_t)n * D + 2];
-                }
-                gs_write_vis_record(vis + 4 * slot, p.m2x, p.m2y, p.ca, p.cb, p.cc, opacities[n] * p.comp, c0, c1, c2);
-            }
-        }
-    }
+template <bool SH, bool CLASSIC>
+__global__ void __launch_bounds__(GS_PROJ_BLOCK)
+project_fwd_ex_kernel(int N, const float* __restrict__ means, const float* __restrict__ quats,
+                      const float* __restrict__ scales, const float* __restrict__ opacities,
+                      const float* __restrict__ colors, int D, const float* __restrict__ sh_coeffs, int sh_K, int sh_degree,
+                      const float* __restrict__ viewmat,
+                      const float* __restrict__ K, int W, int H, int tile_size, int tile_w, int tile_h,
+                      float eps2d, float near_plane, float far_plane, float radius_clip,
+                      int32_t* __restrict__ gaussian_ids, int32_t* __restrict__ radii, float* __restrict__ means2d,
+                      float* __restrict__ depths, float* __restrict__ conics, float* __restrict__ compensations,
+                      float* __restrict__ opacities_packed, float* __restrict__ colors_packed,
+                      int32_t* __restrict__ tiles_per_gauss, int64_t* __restrict__ cum_tiles,
+                      int32_t* __restrict__ packed_index,
+                      unsigned* __restrict__ ctrl, u64* __restrict__ desc, int n_chunks, int64_t* __restrict__ counts, float4* __restrict__ vis)
+{
+#include "gs_project_fwd_body.inc"
 }
 
 extern "C" size_t gs_project_ws_bytes(int N)
@@ -352,6 +467,7 @@ __device__ __forceinline__ int find_slot(const int32_t* __restrict__ gids, int V
     return (lo < V && gids[lo] == n) ? lo : -1;
 }
 
+
 __global__ void __launch_bounds__(256)
 project_bwd_kernel(int N, GsCount vc, int D, const float* __restrict__ means, const float* __restrict__ quats,
                    const float* __restrict__ scales, const float* __restrict__ opacities,
@@ -362,45 +478,25 @@ project_bwd_kernel(int N, GsCount vc, int D, const float* __restrict__ means, co
                    float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
                    float* __restrict__ v_opacities, float* __restrict__ v_colors, int accumulate)
 {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const int V = (int)gs_count(vc);
-    const int v = find_slot(gaussian_ids, V, N, n);
-    float g_mean[3] = { 0, 0, 0 }, g_quat[4] = { 0, 0, 0, 0 }, g_scale[3] = { 0, 0, 0 }, g_op = 0.0f;
-    if (v >= 0) {
-        const GsCam cam = load_cam(viewmat, K);
-        const float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
-        const float4 q4 = *reinterpret_cast<const float4*>(quats + 4 * (size_t)n);
-        const float scale[3] = { scales[3 * (size_t)n], scales[3 * (size_t)n + 1], scales[3 * (size_t)n + 2] };
-        const float* __restrict__ rec = v_packed + (size_t)v * rec_stride;   // {xy(2), conic(3), opacity, colors(D)}
-        ProjGrad pg;
-        project_bwd_one(cam, mean, q4, scale, opacities[n], (float)W, (float)H, eps2d, conics[3 * (size_t)v], conics[3 * (size_t)v + 1],
-                        conics[3 * (size_t)v + 2], compensations[v], rec[0], rec[1], rec[2], rec[3], rec[4], rec[5],
-                        v_depths ? v_depths[v] : 0.0f, pg);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { g_mean[k] = pg.mean[k]; g_scale[k] = pg.scale[k]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g_quat[k] = pg.quat[k];
-        g_op = pg.op;
-    }
-    if (accumulate) {          // += into persistent gradient buffers (several views per step); culled Gaussians add nothing
-        if (v >= 0) {
-            v_means[3 * (size_t)n] += g_mean[0]; v_means[3 * (size_t)n + 1] += g_mean[1]; v_means[3 * (size_t)n + 2] += g_mean[2];
-            float4 q = *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n);
-            q.x += g_quat[0]; q.y += g_quat[1]; q.z += g_quat[2]; q.w += g_quat[3];
-            *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n) = q;
-            v_scales[3 * (size_t)n] += g_scale[0]; v_scales[3 * (size_t)n + 1] += g_scale[1]; v_scales[3 * (size_t)n + 2] += g_scale[2];
-            v_opacities[n] += g_op;
-        }
-    } else {
-        v_means[3 * (size_t)n] = g_mean[0]; v_means[3 * (size_t)n + 1] = g_mean[1]; v_means[3 * (size_t)n + 2] = g_mean[2];
-        *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n) = make_float4(g_quat[0], g_quat[1], g_quat[2], g_quat[3]);
-        v_scales[3 * (size_t)n] = g_scale[0]; v_scales[3 * (size_t)n + 1] = g_scale[1]; v_scales[3 * (size_t)n + 2] = g_scale[2];
-        v_opacities[n] = g_op;
-    }
-    if (v_colors) {             // per-view quantity (feeds the shading backward): always a plain write
-        for (int k = 0; k < D; ++k) v_colors[(size_t)n * D + k] = (v >= 0) ? v_packed[(size_t)v * rec_stride + 6 + k] : 0.0f;
-    }
+    constexpr bool SH = false, CLASSIC = false;           // the <false, false> instance of project_bwd_ex_kernel
+    [[maybe_unused]] const float* const sh_coeffs = nullptr;
+    [[maybe_unused]] float* const g_sh_coeffs = nullptr;
+    [[maybe_unused]] const int sh_K = 0, sh_degree = -1;
+#include "gs_project_bwd_body.inc"
+}
+
+template <bool SH, bool CLASSIC>
+__global__ void __launch_bounds__(256)
+project_bwd_ex_kernel(int N, GsCount vc, int D, const float* __restrict__ means, const float* __restrict__ quats,
+                      const float* __restrict__ scales, const float* __restrict__ opacities,
+                      const float* __restrict__ viewmat, const float* __restrict__ K, int W, int H, float eps2d,
+                      const int32_t* __restrict__ gaussian_ids, const float* __restrict__ conics,
+                      const float* __restrict__ compensations, const float* __restrict__ v_packed, int rec_stride,
+                      const float* __restrict__ v_depths, const float* __restrict__ sh_coeffs, int sh_K, int sh_degree,
+                      float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
+                      float* __restrict__ v_opacities, float* __restrict__ v_colors, float* __restrict__ g_sh_coeffs, int accumulate)
+{
+#include "gs_project_bwd_body.inc"
 }
 
 static int project_bwd_impl(int N, GsCount vc, int D, const float* means, const float* quats, const float* scales,
@@ -443,4 +539,81 @@ extern "C" int gs_project_bwd_cap(int N, const int64_t* counts_dev, int D, const
     return project_bwd_impl(N, GsCount{ N, (const long long*)counts_dev }, D, means, quats, scales, opacities, viewmat, K, W, H, eps2d,
                             gaussian_ids, conics, compensations, v_packed, rec_stride, v_depths, v_means, v_quats, v_scales, v_opacities,
                             v_colors, accumulate, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// A1 / A7 with spherical-harmonics colours and / or gsplat's 'classic' rasterize mode (include/geosplat_hip.h).
+#define GS_PROJ_FLAGS_KNOWN (GS_PROJ_CLASSIC)
+
+static int check_sh_args(int D, const float* colors, const float* sh_coeffs, int sh_K, int sh_degree, int flags)
+{
+    GS_CHECK_ARG((flags & ~GS_PROJ_FLAGS_KNOWN) == 0, "unknown flags");
+    GS_CHECK_ARG(sh_degree >= -1 && sh_degree <= 3, "sh_degree must be -1 (plain colours) or 0..3");
+    if (sh_degree >= 0) {
+        GS_CHECK_ARG(sh_coeffs != nullptr && colors == nullptr && D == 3, "SH colours: sh_coeffs given, colors NULL, D == 3");
+        GS_CHECK_ARG(sh_K >= (sh_degree + 1) * (sh_degree + 1), "sh_K < (sh_degree + 1)^2");
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_project_fwd_vis_ex(int N, const float* means, const float* quats, const float* scales,
+                                     const float* opacities, const float* colors, int D, const float* sh_coeffs, int sh_K,
+                                     int sh_degree, int flags, const float* viewmat, const float* K, int W, int H, int tile_size,
+                                     float eps2d, float near_plane, float far_plane, float radius_clip, int32_t* gaussian_ids,
+                                     int32_t* radii, float* means2d, float* depths, float* conics, float* compensations,
+                                     float* opacities_packed, float* colors_packed, int32_t* tiles_per_gauss, int64_t* cum_tiles,
+                                     int32_t* packed_index, float* vis_records, void* ws, size_t ws_bytes, int64_t* counts,
+                                     void* stream)
+{
+    if (int rc = check_sh_args(D, colors, sh_coeffs, sh_K, sh_degree, flags)) return rc;
+    const bool sh = sh_degree >= 0, classic = (flags & GS_PROJ_CLASSIC) != 0;
+    if (!sh && !classic)
+        return gs_project_fwd_vis(N, means, quats, scales, opacities, colors, D, viewmat, K, W, H, tile_size, eps2d, near_plane,
+                                  far_plane, radius_clip, gaussian_ids, radii, means2d, depths, conics, compensations,
+                                  opacities_packed, colors_packed, tiles_per_gauss, cum_tiles, packed_index, vis_records, ws,
+                                  ws_bytes, counts, stream);
+    GS_CHECK_ARG(N >= 0 && W > 0 && H > 0 && tile_size > 0, "bad sizes");
+    GS_CHECK_ARG(counts != nullptr && ws != nullptr, "counts/ws must not be NULL");
+    if (sh) GS_CHECK_ARG(colors_packed != nullptr, "SH colours need colors_packed [N,3]");
+    else    GS_CHECK_ARG((colors == nullptr) == (colors_packed == nullptr), "colors and colors_packed go together");
+    if (ws_bytes < gs_project_ws_bytes(N)) { gs_set_error("gs_project_fwd_vis_ex: workspace too small"); return GS_ENOSPC; }
+    hipStream_t s = (hipStream_t)stream;
+    GS_CHECK_HIP(gs_zero_async(ws, gs_project_ws_bytes(N), s));
+    GS_CHECK_HIP(gs_zero_async(counts, 2 * sizeof(int64_t), s));
+    if (N == 0) return GS_OK;
+    const int n_chunks = (N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK;
+    const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
+    unsigned* ctrl = (unsigned*)ws;
+    u64* desc = (u64*)((char*)ws + 16);
+    auto kern = sh ? (classic ? project_fwd_ex_kernel<true, true> : project_fwd_ex_kernel<true, false>) : project_fwd_ex_kernel<false, true>;
+    hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(GS_PROJ_BLOCK), 0, s, N, means, quats, scales, opacities, colors, D, sh_coeffs,
+                       sh_K, sh_degree, viewmat, K, W, H, tile_size, tile_w, tile_h, eps2d, near_plane, far_plane, radius_clip,
+                       gaussian_ids, radii, means2d, depths, conics, compensations, opacities_packed, colors_packed, tiles_per_gauss,
+                       cum_tiles, packed_index, ctrl, desc, n_chunks, counts, (float4*)vis_records);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+extern "C" int gs_project_bwd_ex(int N, int V, int D, const float* means, const float* quats, const float* scales,
+                                 const float* opacities, const float* viewmat, const float* K, int W, int H, float eps2d,
+                                 const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                                 const float* v_packed, int rec_stride, const float* v_depths, const float* sh_coeffs, int sh_K,
+                                 int sh_degree, int flags, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                                 float* v_colors, float* g_sh_coeffs, int accumulate, void* stream)
+{
+    if (int rc = check_sh_args(D, nullptr, sh_coeffs, sh_K, sh_degree, flags)) return rc;
+    const bool sh = sh_degree >= 0, classic = (flags & GS_PROJ_CLASSIC) != 0;
+    if (!sh && !classic)
+        return gs_project_bwd(N, V, D, means, quats, scales, opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations,
+                              v_packed, rec_stride, v_depths, v_means, v_quats, v_scales, v_opacities, v_colors, accumulate, stream);
+    GS_CHECK_ARG(N >= 0 && V >= 0 && V <= N, "bad sizes");
+    if (sh) GS_CHECK_ARG(g_sh_coeffs != nullptr && v_colors == nullptr, "SH colours: g_sh_coeffs given, v_colors NULL");
+    if (N == 0) return GS_OK;
+    auto kern = sh ? (classic ? project_bwd_ex_kernel<true, true> : project_bwd_ex_kernel<true, false>) : project_bwd_ex_kernel<false, true>;
+    hipLaunchKernelGGL(kern, dim3(gs_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, N, GsCount{ V, nullptr }, D, means, quats,
+                       scales, opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations, v_packed,
+                       rec_stride > 0 ? rec_stride : ((6 + D) + 15) / 16 * 16, v_depths, sh_coeffs, sh_K, sh_degree, v_means, v_quats,
+                       v_scales, v_opacities, v_colors, g_sh_coeffs, accumulate);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
 }

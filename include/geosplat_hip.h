@@ -18,6 +18,9 @@
  *          rfstudio/model/gsplat.py:334-355 (also :240-261, :151-172; rfstudio/model/geosplat.py:276-295)
  *   gs_raster_bwd / gs_project_bwd
  *        = the autograd backward of that call, reached from rfstudio/optim/optimizer.py:107
+ *   gs_project_fwd_vis_ex / gs_project_bwd_ex
+ *        = the same stages with spherical-harmonics colours and rasterize_mode='classic', as GSplatter calls
+ *          gsplat.rasterization (rfstudio/model/gsplat.py:23-36, :209-214, :304-309)
  *   gs_shade_fwd / gs_shade_bwd
  *        = RenderableAttrs.splat arithmetic rfstudio/model/geosplat.py:80-122 including the two
  *          `dr.texture` calls (:93-98 and rfstudio/graphics/_mesh/_texture.py:596-611)
@@ -86,6 +89,26 @@ int gs_project_fwd_vis(int N, const float* means, const float* quats, const floa
                        float* compensations, float* opacities_packed, float* colors_packed,
                        int32_t* tiles_per_gauss, int64_t* cum_tiles, int32_t* packed_index, float* vis_records,
                        void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+
+/* gsplat 1.4 `rasterization(..., sh_degree=d, rasterize_mode='classic')`, packed, one camera: the configuration of the reference's
+ * GSplatter (rfstudio/model/gsplat.py:23-36; colours assembled at :209-214 and :304-309, trained by
+ * rfstudio/trainer/gsplat_trainer.py).  gs_project_fwd_vis plus two options:
+ *   sh_degree in 0..3: colours from spherical harmonics.  sh_coeffs [N, sh_K, 3], sh_K >= (sh_degree+1)^2 (coefficients beyond are
+ *     ignored), colors must be NULL and D == 3; for every VISIBLE Gaussian, dir = normalize(mean - campos) with
+ *     campos = inverse(viewmat)[:3, 3], c = sum_k basis_k(dir) * coeffs[k] (the real SH basis of 3DGS in gsplat's polynomial form),
+ *     colors_packed [N,3] (required) and the records receive max(c + 0.5, 0).  sh_degree == -1: plain colours as before.
+ *   flags & GS_PROJ_CLASSIC: opacities_packed = opacities[g] (no anti-alias compensation factor); the eps2d blur, radii, culling
+ *     and tile counts are unchanged, compensations is still written.
+ * With sh_degree == -1 and flags == 0 this is gs_project_fwd_vis. */
+#define GS_PROJ_CLASSIC 1
+int gs_project_fwd_vis_ex(int N, const float* means, const float* quats, const float* scales, const float* opacities,
+                          const float* colors, int D, const float* sh_coeffs, int sh_K, int sh_degree, int flags,
+                          const float* viewmat, const float* K, int W, int H, int tile_size,
+                          float eps2d, float near_plane, float far_plane, float radius_clip,
+                          int32_t* gaussian_ids, int32_t* radii, float* means2d, float* depths, float* conics,
+                          float* compensations, float* opacities_packed, float* colors_packed,
+                          int32_t* tiles_per_gauss, int64_t* cum_tiles, int32_t* packed_index, float* vis_records,
+                          void* ws, size_t ws_bytes, int64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------ A2 (emit) ---------------------- */
 /* isect_ids[i] = (tile_id << 32) | float_bits(depth), flatten_ids[i] = packed index; emission order =
@@ -267,6 +290,19 @@ int gs_project_bwd(int N, int V, int D, const float* means, const float* quats, 
                    const float* v_packed, int rec_stride /* 0 = gs_raster_grad_stride(D) */, const float* v_depths,
                    float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                    int accumulate, void* stream);
+
+/* gs_project_bwd for gs_project_fwd_vis_ex's options (the same sh_coeffs / sh_K / sh_degree / flags as the forward):
+ *   sh_degree in 0..3: D == 3 (the record's colour gradient), v_colors must be NULL and g_sh_coeffs [N, sh_K, 3] is fully written
+ *     (never accumulated): basis_k(dir) * v_c where the clamp passed (c + 0.5 >= 0, torch's clamp_min rule), 0 for k >= (d+1)^2,
+ *     for clamped channels and for culled Gaussians; the direction term goes through the normalisation into v_means.
+ *   flags & GS_PROJ_CLASSIC: v_opacities = v_opacity_packed, and the compensation contributes no gradient to the covariance.
+ * With sh_degree == -1 and flags == 0 this is gs_project_bwd. */
+int gs_project_bwd_ex(int N, int V, int D, const float* means, const float* quats, const float* scales,
+                      const float* opacities, const float* viewmat, const float* K, int W, int H, float eps2d,
+                      const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                      const float* v_packed, int rec_stride, const float* v_depths, const float* sh_coeffs, int sh_K,
+                      int sh_degree, int flags, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                      float* v_colors, float* g_sh_coeffs, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------ S1..S3 ------------------------- */
 /* Split-sum pyramid description (host struct, device pointers inside). */
