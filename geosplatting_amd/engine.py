@@ -13,9 +13,10 @@ Order of work per step (all on the current HIP stream, kernels in libgeosplat_hi
 from __future__ import annotations
 
 import collections
+import contextlib
 import os
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -65,6 +66,31 @@ def _auto_tail_schedule(n_views: int):
     return sched + [2]
 
 
+@dataclass
+class _Geometry:
+    """What RenderStep._geometry hands to the records and views phases of a step."""
+    scales_act: Tensor; opac_act: Tensor                  # the once-per-step exp / sigmoid activations
+    i_cap: Optional[int]                                  # intersection capacity per view; None = exact mode
+    key_bits: int; key_base: int                          # binning keys of the step's views
+    status: Optional[Tensor]                              # the device status word the fronts report into
+    tight: bool                                           # tile rectangles clipped to the {alpha >= 1/255} extents
+    early: Dict[int, Tuple[Tensor, Tensor]]               # view index -> (flatten_ids, isect_offsets) binned under the prefilter
+
+
+@dataclass
+class _Views:
+    """What RenderStep._views hands to _finish."""
+    b: Dict[str, Tensor]                                  # the gradient bucket's segments
+    images: Optional[List[Tensor]]
+    g_base: Tensor; g_levels: List[Tensor]; g_flat: Tensor   # texel gradients summed over the views (g_flat: all of them)
+    env: TextureSplitSum
+    sharded: bool; world: int; all_reduce: bool
+    main: Optional[torch.cuda.Stream]                     # the caller's stream (capture_views: set at every replay)
+    pstream: Optional[torch.cuda.Stream]                  # the per-Gaussian gradients become final on this stream (None: on main)
+    tail_job: Optional[dict]                              # the last tail launch, left to _chunked_tail
+    captured: bool = False                                # recorded into a graph: its tensors live in the graph's private pool
+
+
 class RenderStep:
     def __init__(self, params: PathParams, min_roughness: float = 0.1, max_metallic: float = 1.0, mode: str = "pbr",
                  tone_type: str = "naive", prefilter: bool = True, fused: bool = True, fg_lut: Optional[Tensor] = None):
@@ -78,7 +104,7 @@ class RenderStep:
         self._cam_cache: Dict[tuple, tuple] = {}
         self._side_stream = None
         self._tail_stream = None
-        # capacity protocol state (see _step_fused / poll_capacity)
+        # capacity protocol state (see _geometry / poll_capacity)
         self._use_capacity = os.environ.get("GEOSPLAT_CAPACITY", "1") != "0"
         self._key_lo = self._key_hi = None     # depth-bit range seen so far (asynchronous read-back): sizes the 24-bit binning keys
         self._key32 = os.environ.get("GEOSPLAT_KEY_BITS", "24") == "32"   # forced by a key-range overflow, or by the environment
@@ -145,12 +171,95 @@ class RenderStep:
         """Forget every cached (view matrix, K, position) triple: for callers that rewrite DEVICE-resident poses behind autograd's back."""
         self._cam_cache.clear()
 
-    def _step_fused(self, cameras, upstream, all_reduce, keep_images, _env=None, _stop_after_views=False, _geo_only=False, _geo=None,
-                    _rec_only=False, _rec=None):
-        """Same arithmetic as the autograd path, driven directly through the C-ABI: every tail launch ADDS into the flat gradient
-        bucket, the exp / sigmoid activations of GSplatter.render_rgba (rfstudio/model/gsplat.py:336-339) are applied once per step
-        and chained once per step (their Jacobians do not depend on the view), and the prefilter backward runs once on the texel
-        gradients summed over the views.
+    def _geometry(self, cameras, bin_first: bool) -> _Geometry:
+        """First phase of a step: what does not need the pyramid -- activations, streams, key width -- and, with `bin_first` in
+        capacity mode, the GEOMETRY of the first view (projection, keys, binning: gs_front_fwd without records) on a front stream, so
+        that it runs UNDER the prefilter forward instead of behind it (the step used to start its first compositor 0.9 ms after the
+        prefilter ended)."""
+        p = self.p
+        dev = p.means.device
+        scales_act = p.scales.detach().exp()
+        opac_act = torch.sigmoid(p.opacities.detach()).squeeze(-1).contiguous()
+        main = torch.cuda.current_stream(dev)
+        if self._use_capacity and self._status is None:      # zero-filled on the main stream BEFORE the side streams fork from it
+            self._status = torch.zeros(4, dtype=torch.int64, device=dev)
+        if self._side_stream is None:
+            self._side_stream = [L.shared_stream(dev, "front0"), L.shared_stream(dev, "front1")]
+        # tile rectangles clipped to the {alpha >= 1/255} extents (GEOSPLAT_TIGHT_TILES=0: gsplat's squares): 18 % fewer intersections
+        # on the bench scene, identical pixels (gs_front_fwd; the engine never returns gsplat's `meta`)
+        tight = os.environ.get("GEOSPLAT_TIGHT_TILES", "1") != "0"
+        # binning keys: 24 bits once the depth range of earlier views is known (front.binning_keys); a view outside the range is
+        # reported through the status word (poll_capacity) and the engine falls back to 32-bit keys
+        i_cap = self._i_cap if self._use_capacity else None
+        key_bits, key_base = F.binning_keys(self._key_lo, self._key_hi) if (i_cap is not None and not self._key32) else (32, 0)
+        status = self._status if (key_bits == 24 or self._use_capacity) else None
+        geo = _Geometry(scales_act, opac_act, i_cap, key_bits, key_base, status, tight, {})
+        if bin_first and i_cap is not None and len(cameras) > 0:
+            # (the geometry of ONE view: of two, beside the prefilter, costs more than it hides -- 563 against 580 views/s)
+            side = self._side_stream[0]
+            ev_a = torch.cuda.Event(); ev_a.record(main)
+            cam_t = self._camera_tensors(cameras[0])
+            side.wait_event(ev_a)
+            with torch.cuda.stream(side):
+                fr = self._front(geo, cameras[0], cam_t, None, records=False)
+                binned, _, _ = F.bin_stage(fr, i_cap, self._status, prepare=False)
+            self._seen_counts.append((fr.host_counts, fr.event))
+            geo.early[0] = (binned["flatten_ids"], binned["isect_offsets"])
+            for t in (scales_act, opac_act):
+                t.record_stream(side)
+        return geo
+
+    def _front(self, geo: _Geometry, cam: Camera, cam_t, e, records: bool = True, binning: bool = True) -> F.Front:
+        """front_stage of one view on the current stream: records=False: geometry only; binning=False: records only."""
+        p = self.p
+        keys = (geo.key_base, geo.key_bits, geo.status) if binning else (0, 32, None)
+        return F.front_stage(p.means.detach(), p.quats.detach(), geo.scales_act, geo.opac_act, p.normals.detach(), p.kd.detach(),
+                             p.ks.detach(), *cam_t, e, cam.width, cam.height, self.min_roughness, self.max_metallic, _MODE[self.mode],
+                             *keys, want_packed_index=records, records=records, binning=binning, tight_tiles=geo.tight)
+
+    def _env_args(self, env: TextureSplitSum):
+        """(detached pyramid, its GsEnv struct) for the kernels."""
+        env_d = TextureSplitSum(env.base.detach(), [l.detach().contiguous() for l in env.levels], env.min_roughness, env.max_roughness)
+        return env_d, _make_env(get_fg_lut(self.p.means.device) if self.fg_lut is None else self.fg_lut, env_d)
+
+    def _records(self, cameras, geo: _Geometry, env: TextureSplitSum) -> Dict[int, F.Front]:
+        """capture_views: the RECORDS (shading) of the views whose geometry came from the geometry graph, as a graph of their own --
+        it needs the pyramid but not the binning, so it replays BESIDE the rest of the geometry graph (projection keys, five radix
+        passes, emission: 0.25 ms per view) instead of behind it.  Returns the fronts by view index, for _views."""
+        _, e = self._env_args(env)
+        return {j: self._front(geo, cameras[j], self._camera_tensors(cameras[j]), e, binning=False) for j in sorted(geo.early)}
+
+    def _pyramid(self, sharded: bool, world: int) -> TextureSplitSum:
+        """The pyramid of this step: the prefilter forward (sharded over the ranks: splitsum.py), or without the prefilter in the step
+        the one filtered once."""
+        if not self.prefilter:
+            if self._static_env is None:
+                with torch.no_grad():
+                    self._static_env = as_splitsum(self.p.cubemap)
+            return self._static_env
+        cubemap = self.p.cubemap.detach()
+        if sharded:
+            import torch.distributed as dist
+            return as_splitsum_sharded(cubemap, dist.get_rank(), world, self._prefilter_group())
+        with torch.no_grad():
+            return as_splitsum(cubemap)
+
+    def _sharding(self, all_reduce: bool):
+        """(world, sharded): S5 sharded over the ranks (each applies 1/world of every level's tiles, all-reduce of the disjoint
+        pieces): splitsum.py (collectives_active(): more than one rank, or the one-rank RCCL run of GEOSPLAT_COLLECTIVES_AT_WORLD1=1)"""
+        import torch.distributed as dist
+        world = dist.get_world_size() if (all_reduce and dist.is_available() and dist.is_initialized()) else 1
+        sharded = (self.prefilter and all_reduce and collectives_active() and os.environ.get("GEOSPLAT_SHARD_PREFILTER", "1") != "0"
+                   and can_shard_prefilter(int(self.p.cubemap.shape[1]), world))
+        return world, sharded
+
+    def _views(self, cameras, upstream, all_reduce, keep_images, geo: _Geometry, env: Optional[TextureSplitSum] = None,
+               recs: Optional[Dict[int, F.Front]] = None) -> _Views:
+        """Second phase of a step: the zero fill, the pyramid (`env`: already filtered, capture_views) and every view up to its last
+        tail launch.  Same arithmetic as the autograd path, driven directly through the C-ABI: every tail launch ADDS into the flat
+        gradient bucket, the exp / sigmoid activations of GSplatter.render_rgba (rfstudio/model/gsplat.py:336-339) are applied once
+        per step and chained once per step (their Jacobians do not depend on the view), and the prefilter backward runs once on the
+        texel gradients summed over the views (_finish).  `recs`: the fronts of _records, by view index.
 
         HIP streams of a step: two FRONT streams run the memory / latency-bound front of every view (gs_front_fwd, the binning, the
         record stream: ~22 short kernels, none of which fills the chip), the fronts of consecutive views alternating between them
@@ -164,78 +273,13 @@ class RenderStep:
         f32 = torch.float32
         st = L.stream
         mode, tone = _MODE[self.mode], _TONE[self.tone_type]
-        cubemap = p.cubemap.detach()
-        import torch.distributed as dist
-        world = dist.get_world_size() if (all_reduce and dist.is_available() and dist.is_initialized()) else 1
-        # S5 sharded over the ranks (each applies 1/world of every level's tiles, all-reduce of the disjoint pieces): splitsum.py
-        # (collectives_active(): more than one rank, or the one-rank RCCL run of GEOSPLAT_COLLECTIVES_AT_WORLD1=1)
-        sharded = (self.prefilter and all_reduce and collectives_active() and os.environ.get("GEOSPLAT_SHARD_PREFILTER", "1") != "0"
-                   and can_shard_prefilter(int(cubemap.shape[1]), world))
-        # ---- what does not need the pyramid comes first: activations, streams, key width -- and, in capacity mode, the GEOMETRY of
-        # the first view (projection, keys, binning: gs_front_fwd without records) on a front stream, so that it runs UNDER the
-        # prefilter forward instead of behind it (the step used to start its first compositor 0.9 ms after the prefilter ended)
-        if _geo is not None:                                 # (capture_views: the geometry phase of this step ran as its own graph)
-            scales_act, opac_act = _geo["scales_act"], _geo["opac_act"]
-        else:
-            scales_act = p.scales.detach().exp()
-            opac_act = torch.sigmoid(p.opacities.detach()).squeeze(-1).contiguous()
+        world, sharded = self._sharding(all_reduce)
+        scales_act, opac_act = geo.scales_act, geo.opac_act
         means, quats = p.means.detach(), p.quats.detach()
         normals, kd, ks = p.normals.detach(), p.kd.detach(), p.ks.detach()
         main = torch.cuda.current_stream(dev)
-        if self._use_capacity and self._status is None:      # zero-filled on the main stream BEFORE the side streams fork from it
-            self._status = torch.zeros(4, dtype=torch.int64, device=dev)
-        if self._side_stream is None:
-            self._side_stream = [L.shared_stream(dev, "front0"), L.shared_stream(dev, "front1")]
         sides = self._side_stream
-        # tile rectangles clipped to the {alpha >= 1/255} extents (GEOSPLAT_TIGHT_TILES=0: gsplat's squares): 18 % fewer intersections
-        # on the bench scene, identical pixels (gs_front_fwd; the engine never returns gsplat's `meta`)
-        tight = os.environ.get("GEOSPLAT_TIGHT_TILES", "1") != "0"
-        # binning keys: 24 bits (three depth passes instead of four) once the depth range of earlier views is known -- key = depth
-        # bits - key_base with half an octave of room below the smallest depth seen; a view outside the range is reported through
-        # the status word (poll_capacity) and the engine falls back to 32-bit keys
-        key_bits, key_base = 32, 0
-        if self._use_capacity and self._i_cap is not None and not self._key32 and self._key_lo is not None:
-            base = max(0, self._key_lo - (1 << 22))
-            if self._key_hi - base < (1 << 24) - (1 << 21):
-                key_bits, key_base = 24, base
-        i_cap = self._i_cap if self._use_capacity else None
-        status = self._status if (key_bits == 24 or self._use_capacity) else None
-        seen = []                                            # (pinned counts, event) of this step's views
-        early = {}                                           # view index -> (flatten_ids, isect_offsets) binned under the prefilter
-        if _geo is not None:
-            early = _geo["early"]
-        elif i_cap is not None and (_env is None or _geo_only) and self.prefilter and len(cameras) > 0:
-            # (the geometry of ONE view: of two, beside the prefilter, costs more than it hides -- 563 against 580 views/s)
-            ev_a = torch.cuda.Event(); ev_a.record(main)
-            vm_0, K_0, cp_0 = self._camera_tensors(cameras[0])
-            sides[0].wait_event(ev_a)
-            with torch.cuda.stream(sides[0]):
-                fr_g = F.front_stage(means, quats, scales_act, opac_act, normals, kd, ks, vm_0, K_0, cp_0, None, cameras[0].width,
-                                     cameras[0].height, self.min_roughness, self.max_metallic, mode, key_base, key_bits, status,
-                                     records=False, tight_tiles=tight)
-                gstate, _, _ = F.bin_stage(fr_g, i_cap, self._status, prepare=False)
-            seen.append((fr_g.host_counts, fr_g.event))
-            early[0] = (gstate["flatten_ids"], gstate["isect_offsets"])
-            for t in (scales_act, opac_act):
-                t.record_stream(sides[0])
-        if _geo_only:
-            for sd in sides:
-                main.wait_stream(sd)                         # (a captured phase: every forked stream joins before the capture ends)
-            self._seen_counts.extend(seen)
-            return dict(early=early, scales_act=scales_act, opac_act=opac_act)
-        if _rec_only:
-            # capture_views: the RECORDS (shading) of the views whose geometry came from the geometry graph, as a graph of their own --
-            # it needs the pyramid but not the binning, so it replays BESIDE the rest of the geometry graph (projection keys, five
-            # radix passes, emission: 0.25 ms per view) instead of behind it
-            env_r = TextureSplitSum(_env.base.detach(), [l.detach().contiguous() for l in _env.levels], _env.min_roughness, _env.max_roughness)
-            e_r = _make_env(get_fg_lut(dev) if self.fg_lut is None else self.fg_lut, env_r)
-            recs = {}
-            for j in sorted(early):
-                cam = cameras[j]
-                vm, K, cam_pos = self._camera_tensors(cam)
-                recs[j] = F.front_stage(means, quats, scales_act, opac_act, normals, kd, ks, vm, K, cam_pos, e_r, cam.width, cam.height,
-                                        self.min_roughness, self.max_metallic, mode, want_packed_index=True, binning=False, tight_tiles=tight)
-            return dict(recs=recs, e=e_r, env_d=env_r)
+        i_cap, early = geo.i_cap, geo.early
         # ONE fill, issued before the prefilter: the bucket, the activation-gradient accumulators and the texel-gradient accumulators
         # share an allocation
         cres = int(p.cubemap.shape[1])
@@ -247,23 +291,9 @@ class RenderStep:
         b = self.bucket.unpack()
         g_scales_act = sc[0].view(N, 3); g_opac_act = sc[1]
         exposure = p.exposure.detach().reshape(1).contiguous()
-        if _env is not None:
-            env = _env                                       # the pyramid of this step, already filtered (capture_views)
-        elif self.prefilter:
-            if sharded:
-                env = as_splitsum_sharded(cubemap, dist.get_rank(), world, self._prefilter_group())
-            else:
-                with torch.no_grad():
-                    env = as_splitsum(cubemap)
-        else:
-            if self._static_env is None:
-                with torch.no_grad():
-                    self._static_env = as_splitsum(p.cubemap)
-            env = self._static_env
-        env_d = TextureSplitSum(env.base.detach(), [l.detach().contiguous() for l in env.levels], env.min_roughness,
-                                env.max_roughness)
-        lut = get_fg_lut(dev) if self.fg_lut is None else self.fg_lut
-        e = _make_env(lut, env_d)
+        if env is None:
+            env = self._pyramid(sharded, world)
+        env_d, e = self._env_args(env)
         # texel-gradient accumulators: one flat buffer behind the base + level gradients (the sharded prefilter sums them over the
         # ranks in ONE all-reduce).  (Two sets with the first half's prefilter backward under the remaining compositor work were
         # measured: the backward is linear, splitting it doubles it, the overlap does not pay that back.)
@@ -298,18 +328,12 @@ class RenderStep:
         tail_job = None
 
         def start_view(cam, j):                              # S1-S3 + A1; (V, I) travel to the host asynchronously
-            vm, K, cam_pos = self._camera_tensors(cam)
+            cam_t = self._camera_tensors(cam)
             side = sides[j % len(sides)]
-            if _rec is not None and j in _rec["recs"]:       # (capture_views: the records graph has run)
-                return _rec["recs"][j], j, side
-            with torch.cuda.stream(side):
-                if j in early:                               # binned under the prefilter: only the records (shading) are still missing
-                    fr = F.front_stage(means, quats, scales_act, opac_act, normals, kd, ks, vm, K, cam_pos, e, cam.width, cam.height,
-                                       self.min_roughness, self.max_metallic, mode, want_packed_index=True, binning=False, tight_tiles=tight)
-                else:
-                    fr = F.front_stage(means, quats, scales_act, opac_act, normals, kd, ks, vm, K, cam_pos, e, cam.width, cam.height,
-                                       self.min_roughness, self.max_metallic, mode, key_base, key_bits, status, want_packed_index=True,
-                                       tight_tiles=tight)
+            if recs is not None and j in recs:               # (capture_views: the records graph has run)
+                return recs[j], j, side
+            with torch.cuda.stream(side):                    # (binned under the prefilter: only the records (shading) are still missing)
+                fr = self._front(geo, cam, cam_t, e, binning=j not in early)
             return fr, j, side
 
         # Capacity protocol (include/geosplat_hip.h): once the engine has seen the intersection counts of a step, the later
@@ -320,14 +344,11 @@ class RenderStep:
             fr, j, side = item
             with torch.cuda.stream(side):
                 if i_cap is not None:
-                    seen.append((fr.host_counts, fr.event))
+                    self._seen_counts.append((fr.host_counts, fr.event))
                 state, V, I = F.bin_stage(fr, i_cap, self._status, binned=early.get(j))
                 if i_cap is None:
                     self._exact_max_i = max(self._exact_max_i, I)
-                    rng = F.depth_range(fr.host_counts)
-                    if rng is not None:
-                        self._key_lo = rng[0] if self._key_lo is None else min(self._key_lo, rng[0])
-                        self._key_hi = rng[1] if self._key_hi is None else max(self._key_hi, rng[1])
+                    self._key_lo, self._key_hi = F.learn_depth_range(self._key_lo, self._key_hi, fr.host_counts)
                     F.release_counts4(fr.host_counts)
                 # the packed gradient records of this view, zeroed HERE (front stream, under the compositor of the previous view)
                 state["v_packed"] = torch.zeros(max(V, 1), lib.gs_raster_grad_stride(3), dtype=f32, device=dev)
@@ -419,7 +440,6 @@ class RenderStep:
             if keep_images:
                 images.append(img)
         main.wait_stream(tail)
-        self._seen_counts.extend(seen)                       # entries of earlier steps the host has not looked at yet stay pending
         if i_cap is not None:                                # the overflow word follows the step to the host, asynchronously
             if torch.cuda.is_current_stream_capturing():      # a replayed graph refreshes ONE pinned buffer; replay.check() reads it
                 if self._status_host is None:
@@ -444,53 +464,52 @@ class RenderStep:
             if pstream is not None:
                 for t in (scales_act, opac_act):
                     t.record_stream(pstream)
-        ctx = dict(b=b, images=(images if keep_images else None), g_base=g_base, g_levels=g_levels, g_flat=g_flat, env=env, sharded=sharded,
-                   world=world, all_reduce=all_reduce, main=main, pstream=pstream, tail_job=tail_job)
-        if _stop_after_views:                                 # (a captured views segment: every forked stream joins before the capture ends)
-            if pstream is not None:
-                main.wait_stream(pstream)
-                ctx["pstream"] = None
-            return ctx
-        return self._finish(ctx)
+        return _Views(b, images if keep_images else None, g_base, g_levels, g_flat, env, sharded, world, all_reduce, main, pstream,
+                      tail_job)
 
-    def _finish(self, ctx):
+    def _step(self, cameras, upstream, all_reduce, keep_images):
+        """One whole step: geometry (the first view binned under the prefilter), views, _finish."""
+        geo = self._geometry(cameras, bin_first=self.prefilter)
+        return self._finish(self._views(cameras, upstream, all_reduce, keep_images, geo))
+
+    def _finish(self, ctx: _Views):
         """What follows the views of a step: gradient all-reduce (its per-Gaussian part under the prefilter backward) and the
         prefilter backward on the texel gradients summed over the views (and, sharded, over the ranks)."""
         import torch.distributed as dist
-        b, images, g_base, g_levels, g_flat, env = (ctx[k] for k in ("b", "images", "g_base", "g_levels", "g_flat", "env"))
-        sharded, world, all_reduce, main = (ctx[k] for k in ("sharded", "world", "all_reduce", "main"))
-        pstream = ctx.get("pstream")                          # the per-Gaussian gradients become final on this stream (None: on main)
-        chunked = ctx.get("tail_job") is not None
+        b, env, main = ctx.b, ctx.env, ctx.main
+        pstream = ctx.pstream                                 # the per-Gaussian gradients become final on this stream (None: on main)
+        chunked = ctx.tail_job is not None
         if chunked:                                           # last tail in Gaussian-range chunks, each summed over the ranks as it ends
             pstream = self._chunked_tail(ctx)
             main.wait_stream(self._tail_stream)               # the texel gradients are complete behind the last chunk's shading half
         head_stream = pstream if pstream is not None else main
-        if sharded:
+        if ctx.sharded:
             grp = self._prefilter_group()
-            dist.all_reduce(g_flat, op=dist.ReduceOp.SUM, group=grp)             # texel gradients of ALL views: needed by every share
+            dist.all_reduce(ctx.g_flat, op=dist.ReduceOp.SUM, group=grp)         # texel gradients of ALL views: needed by every share
             if not chunked:
                 start_head, _ = self.bucket.all_reduce_split("cubemap")
                 with torch.cuda.stream(head_stream):
                     start_head()                                # per-Gaussian segments: communication stream, default communicator
-            g_cube = as_splitsum_backward_sharded(g_base, g_levels, dist.get_rank(), world, grp, min_roughness=env.min_roughness,
-                                                  max_roughness=env.max_roughness)
+            g_cube = as_splitsum_backward_sharded(ctx.g_base, ctx.g_levels, dist.get_rank(), ctx.world, grp,
+                                                  min_roughness=env.min_roughness, max_roughness=env.max_roughness)
             b["cubemap"].copy_(g_cube)                          # identical on every rank: not reduced again
             if pstream is not None:
                 main.wait_stream(pstream)
             self.bucket.all_reduce_names(["exposure"])          # queues behind the head on the communication stream, then joins it
-            return b, images
-        start_head, finish = self.bucket.all_reduce_split("cubemap") if all_reduce else ((lambda: None), (lambda: None))
+            return b, ctx.images
+        start_head, finish = self.bucket.all_reduce_split("cubemap") if ctx.all_reduce else ((lambda: None), (lambda: None))
         if not chunked:
             with torch.cuda.stream(head_stream):
                 start_head()
         if self.prefilter:                                      # (the finest level's transposed apply writes the bucket's slice itself)
-            as_splitsum_backward(g_base, g_levels, min_roughness=env.min_roughness, max_roughness=env.max_roughness, out=b["cubemap"])
+            as_splitsum_backward(ctx.g_base, ctx.g_levels, min_roughness=env.min_roughness, max_roughness=env.max_roughness,
+                                 out=b["cubemap"])
         if pstream is not None:
             main.wait_stream(pstream)
         finish()
-        return b, images
+        return b, ctx.images
 
-    def _chunked_tail(self, ctx):
+    def _chunked_tail(self, ctx: _Views):
         """The last tail launch of a step with collectives, in `n_chunks` Gaussian ranges: shading half of chunk k on the tail stream,
         its projection half + the activation chain of those rows on a front stream behind it, and -- as soon as they are final -- the
         all-reduce of exactly those rows of the seven per-Gaussian segments on the communication stream (GradBucket.all_reduce_rows),
@@ -498,9 +517,9 @@ class RenderStep:
         chunk is the same launch on pointers moved to the range's first row.  With one view per rank (BASELINE config 4) the 149 MB
         all-reduce is otherwise fully exposed behind a 0.33 ms tail; here all but the last quarter of it runs under the tail.
         Returns the stream on which the per-Gaussian gradients became final."""
-        job = ctx["tail_job"]
+        job = ctx.tail_job
         lib = L.lib()
-        b = ctx["b"]
+        b = ctx.b
         self.chunked_tails += 1
         (views, means, quats, scales_act, opac_act, normals, kd, ks, e, eg, mr, mm, mode, g_means, g_quats, g_scales_act, g_opac_act,
          g_normals, g_kd, g_ks) = job["targs"]
@@ -509,8 +528,7 @@ class RenderStep:
         bounds = [min(N, ((N * k // C_ + 1023) // 1024) * 1024) for k in range(C_)] + [N]
         tail, pstream = self._tail_stream, self._side_stream[0]
         names = [k for k in PARAM_NAMES if k not in ("cubemap", "exposure")]
-        tail.wait_stream(ctx["main"])                         # (behind the last compositor backward; a captured views segment: behind its replay)
-        captured = ctx.get("captured", False)
+        tail.wait_stream(ctx.main)                            # (behind the last compositor backward; a captured views segment: behind its replay)
         for c in range(C_):
             n0, n1 = bounds[c], bounds[c + 1]
             if n1 <= n0:
@@ -530,13 +548,58 @@ class RenderStep:
                         "gs_activation_chain")
                 ev_c = torch.cuda.Event(); ev_c.record(pstream)
             self.bucket.all_reduce_rows(names, n0, n1, after=ev_c)
-        if not captured:                                      # (a captured segment's tensors live in the graph's private pool)
+        if not ctx.captured:                                  # (a captured segment's tensors live in the graph's private pool)
             for tv in views:
                 for t in tv[:6]:
                     t.record_stream(tail); t.record_stream(pstream)
             for t in (scales_act, opac_act, g_scales_act, g_opac_act):
                 t.record_stream(tail); t.record_stream(pstream)
         return pstream
+
+    def _capture(self, n_pinned: int, record):
+        """What capture() and capture_views() share.  `record(phase)` issues the work to be captured, each graph's share of it under
+        `with phase():`.  It runs once eagerly on a side stream -- the allocator warm-up torch.cuda.graph asks for -- and once more
+        with every phase() a new graph (the later graphs share the first one's memory pool).  Returns (what that second run returned,
+        the graphs, check): check() synchronises and returns False if a view of the last replay exceeded the capacity OR left the
+        depth range of the 24-bit binning keys baked into the graphs; they are then stale and `check.stale` is set."""
+        dev = self.p.means.device
+        F.reserve_pinned(n_pinned)                             # pinned buffers cannot be allocated while a stream is capturing
+        if self._status is None:
+            self._status = torch.zeros(4, dtype=torch.int64, device=dev)
+        if self._status_host is None:
+            self._status_host = torch.zeros(4, dtype=torch.int64).pin_memory()
+        warm = torch.cuda.Stream(device=dev)
+        warm.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(warm):
+            record(contextlib.nullcontext)
+        torch.cuda.current_stream(dev).wait_stream(warm)
+        torch.cuda.synchronize(dev)
+        self.poll_capacity(_internal=True)                    # an overflow of the warm-up step stays pending for the caller's next poll
+        graphs = []
+
+        def phase():
+            graphs.append(torch.cuda.CUDAGraph())
+            return torch.cuda.graph(graphs[-1], pool=graphs[0].pool() if len(graphs) > 1 else None)
+        out = record(phase)
+        counts = [hc for hc, _ in self._seen_counts]          # refreshed by every replay (D2H copies are graph nodes)
+        self._seen_counts = []
+        self._status_event = None
+        cap = self._i_cap
+        status_host = self._status_host
+
+        def check() -> bool:
+            torch.cuda.synchronize(dev)
+            worst = max([int(hc[1]) for hc in counts] + [0])
+            overflow = int(status_host[0]) != 0 or int(status_host[3]) != 0 or worst > cap
+            if overflow:
+                check.stale = True
+                self.truncated_steps += 1
+                self._key32 = self._key32 or int(status_host[3]) != 0
+                self._exact_max_i = max(self._exact_max_i, worst, int(status_host[1]))
+                self._status.zero_(); status_host.zero_()
+            return not overflow
+        check.stale = False
+        return out, graphs, check
 
     def capture(self, cameras: List[Camera], upstream: Callable[[int, Tensor], Tensor], keep_images: bool = False):
         """One fused step over a FIXED camera list recorded into a HIP graph (torch.cuda.CUDAGraph): possible because in
@@ -552,50 +615,17 @@ class RenderStep:
             raise RuntimeError("capture() needs the fused path")
         if self._i_cap is None:
             raise RuntimeError("capture() needs a known capacity: run one eager step and poll_capacity(wait=True) first")
-        from .rasterization import _pinned_pool
-        dev = self.p.means.device
-        while len(_pinned_pool) < 2 * len(cameras) + 2:       # pinned buffers cannot be allocated while a stream is capturing
-            _pinned_pool.append(torch.empty(2, dtype=torch.int64).pin_memory())
-        F.reserve_pinned(2 * len(cameras) + 2)
-        if self._status is None:
-            self._status = torch.zeros(4, dtype=torch.int64, device=dev)
-        if self._status_host is None:
-            self._status_host = torch.zeros(4, dtype=torch.int64).pin_memory()
-        warm = torch.cuda.Stream(device=dev)
-        warm.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(warm):                          # (allocator warm-up on a side stream, as torch.cuda.graph asks)
-            self._step_fused(cameras, upstream, False, keep_images)
-        torch.cuda.current_stream(dev).wait_stream(warm)
-        torch.cuda.synchronize(dev)
-        self.poll_capacity(_internal=True)                    # an overflow of the warm-up step stays pending for the caller's next poll
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self._step_fused(cameras, upstream, False, keep_images)
-        counts = [hc for hc, _ in self._seen_counts]          # refreshed by every replay (D2H copies are graph nodes)
-        self._seen_counts = []
-        self._status_event = None
-        cap = self._i_cap
-        status_host = self._status_host
 
-        stale = [False]
+        def record(phase):
+            with phase():
+                return self._step(cameras, upstream, False, keep_images)
+        out, (graph,), check = self._capture(2 * len(cameras) + 2, record)
 
         def replay():
-            if stale[0]:
+            if check.stale:
                 raise RuntimeError("this captured step overflowed its capacity / key range (check() returned False): capture() again")
             graph.replay()
             return out
-
-        def check() -> bool:
-            torch.cuda.synchronize(dev)
-            worst = max([int(hc[1]) for hc in counts] + [0])
-            overflow = int(status_host[0]) != 0 or int(status_host[3]) != 0 or worst > cap
-            if overflow:
-                stale[0] = True
-                self.truncated_steps += 1
-                self._key32 = self._key32 or int(status_host[3]) != 0
-                self._exact_max_i = max(self._exact_max_i, worst, int(status_host[1]))
-                self._status.zero_(); status_host.zero_()
-            return not overflow
         replay.check = check
         replay.graph = graph
         return replay
@@ -614,25 +644,9 @@ class RenderStep:
             raise RuntimeError("capture_views() needs the fused path with the prefilter in the step")
         if self._i_cap is None:
             raise RuntimeError("capture_views() needs a known capacity: run one eager step and poll_capacity(wait=True) first")
-        import torch.distributed as dist
-        from .rasterization import _pinned_pool
         dev = self.p.means.device
-        while len(_pinned_pool) < 2 * len(cameras) + 2:       # pinned buffers cannot be allocated while a stream is capturing
-            _pinned_pool.append(torch.empty(2, dtype=torch.int64).pin_memory())
-        F.reserve_pinned(2 * len(cameras) + 2)
-        if self._status_host is None:
-            self._status_host = torch.zeros(4, dtype=torch.int64).pin_memory()
-        world = dist.get_world_size() if (all_reduce and dist.is_available() and dist.is_initialized()) else 1
-        sharded = (all_reduce and collectives_active() and os.environ.get("GEOSPLAT_SHARD_PREFILTER", "1") != "0"
-                   and can_shard_prefilter(int(self.p.cubemap.shape[1]), world))
-
-        def filter_env():
-            cubemap = self.p.cubemap.detach()
-            if sharded:
-                return as_splitsum_sharded(cubemap, dist.get_rank(), world, self._prefilter_group())
-            with torch.no_grad():
-                return as_splitsum(cubemap)
-        first = filter_env()
+        world, sharded = self._sharding(all_reduce)
+        first = self._pyramid(sharded, world)
         pyramid = TextureSplitSum(first.base.detach().clone(), [l.detach().clone() for l in first.levels], first.min_roughness,
                                   first.max_roughness)
         slots = [pyramid.base] + list(pyramid.levels)
@@ -646,66 +660,48 @@ class RenderStep:
         # The last tail launch and every collective stay eager (_finish): its Gaussian-range chunks are summed over the ranks while the
         # next chunk is computed.
         two = os.environ.get("GEOSPLAT_GEO_GRAPH", "1") != "0"
-        F.reserve_pinned(6 * len(cameras) + 2)                 # (the geometry and records fronts carry their own count read-backs)
-        warm = torch.cuda.Stream(device=dev)
-        warm.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(warm):                          # (allocator warm-up on a side stream, as torch.cuda.graph asks)
-            geo = self._step_fused(cameras, upstream, all_reduce, keep_images, _geo_only=True) if two else None
-            rec = self._step_fused(cameras, upstream, all_reduce, keep_images, _env=pyramid, _geo=geo, _rec_only=True) if two else None
-            self._step_fused(cameras, upstream, all_reduce, keep_images, _env=pyramid, _stop_after_views=True, _geo=geo, _rec=rec)
-        torch.cuda.current_stream(dev).wait_stream(warm)
-        torch.cuda.synchronize(dev)
-        self.poll_capacity(_internal=True)                    # an overflow of the warm-up step stays pending for the caller's next poll
-        geo_graph, geo, rec_graph, rec = None, None, None, None
-        if two:
-            geo_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(geo_graph):
-                geo = self._step_fused(cameras, upstream, all_reduce, keep_images, _geo_only=True)
-            rec_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(rec_graph, pool=geo_graph.pool()):
-                rec = self._step_fused(cameras, upstream, all_reduce, keep_images, _env=pyramid, _geo=geo, _rec_only=True)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=geo_graph.pool() if two else None):
-            ctx = self._step_fused(cameras, upstream, all_reduce, keep_images, _env=pyramid, _stop_after_views=True, _geo=geo, _rec=rec)
-        geo_stream = L.shared_stream(dev, "geo") if two else None
-        counts = [hc for hc, _ in self._seen_counts]          # refreshed by every replay (D2H copies are graph nodes)
-        self._seen_counts = []
-        self._status_event = None
-        cap = self._i_cap
-        status_host = self._status_host
-        ctx["main"] = None
-        ctx["captured"] = True
 
-        stale = [False]
+        def record(phase):                                     # (a captured phase: every forked stream joins before the capture ends)
+            geo = recs = None
+            if two:
+                with phase():
+                    geo = self._geometry(cameras, bin_first=True)
+                    for sd in self._side_stream:
+                        torch.cuda.current_stream(dev).wait_stream(sd)
+                with phase():
+                    recs = self._records(cameras, geo, pyramid)
+            with phase():
+                if geo is None:
+                    geo = self._geometry(cameras, bin_first=False)
+                ctx = self._views(cameras, upstream, all_reduce, keep_images, geo, env=pyramid, recs=recs)
+                if ctx.pstream is not None:
+                    ctx.main.wait_stream(ctx.pstream)
+                    ctx.pstream = None
+            return ctx
+        # (the geometry and records fronts carry their own count read-backs)
+        ctx, graphs, check = self._capture(6 * len(cameras) + 2, record)
+        geo_graph, rec_graph, graph = graphs if two else (None, None, graphs[0])
+        geo_stream = L.shared_stream(dev, "geo") if two else None
+        ctx.main = None
+        ctx.captured = True
 
         def step():
-            if stale[0]:
+            if check.stale:
                 raise RuntimeError("these captured views overflowed their capacity / key range (check() returned False): capture_views() again")
             cur = torch.cuda.current_stream(dev)
             if two:
                 geo_stream.wait_stream(cur)                    # (the parameters of this step are final on the caller's stream)
                 with torch.cuda.stream(geo_stream):
                     geo_graph.replay()
-            env = filter_env()
+            env = self._pyramid(sharded, world)
             torch._foreach_copy_(slots, [env.base] + list(env.levels))
             if two:
-                rec_graph.replay()                             # shading of the views: beside the geometry graph
+                # shading of the views: beside the geometry graph (nothing orders it behind the activations the geometry graph writes)
+                rec_graph.replay()
                 cur.wait_stream(geo_stream)
             graph.replay()
-            ctx["main"] = cur
+            ctx.main = cur
             return self._finish(ctx)
-
-        def check() -> bool:
-            torch.cuda.synchronize(dev)
-            worst = max([int(hc[1]) for hc in counts] + [0])
-            overflow = int(status_host[0]) != 0 or int(status_host[3]) != 0 or worst > cap
-            if overflow:
-                stale[0] = True
-                self.truncated_steps += 1
-                self._key32 = self._key32 or int(status_host[3]) != 0
-                self._exact_max_i = max(self._exact_max_i, worst, int(status_host[1]))
-                self._status.zero_(); status_host.zero_()
-            return not overflow
         step.check = check
         step.graph = graph
         step.geo_graph = geo_graph
@@ -739,18 +735,17 @@ class RenderStep:
         step (stage1.py does); bench.py reports `truncated_steps`."""
         ok = True
         max_i, self._exact_max_i = self._exact_max_i, 0
-        for hc, ev in self._seen_counts:
-            if hc is None:
-                continue
+        still = []
+        for hc, ev in self._seen_counts:                      # front_stage's pinned {V, I, ~min depth bits, max depth bits}
             if wait:
                 ev.synchronize()
             if ev.query():
                 max_i = max(max_i, int(hc[1]))
-                if hc.numel() == 4:                             # fused front: {V, I, ~min depth bits, max depth bits}
-                    rng = F.depth_range(hc)
-                    if rng is not None:
-                        self._key_lo = rng[0] if self._key_lo is None else min(self._key_lo, rng[0])
-                        self._key_hi = rng[1] if self._key_hi is None else max(self._key_hi, rng[1])
+                self._key_lo, self._key_hi = F.learn_depth_range(self._key_lo, self._key_hi, hc)
+                F.release_counts4(hc)
+            else:
+                still.append((hc, ev))
+        self._seen_counts = still
         while self._status_pending:                           # eager steps, oldest first; each snapshot is inspected exactly once
             snap, ev_s = self._status_pending[0]
             if wait:
@@ -777,16 +772,6 @@ class RenderStep:
                 self._status.zero_(); self._status_host.zero_()
             if self._status_event.query():
                 self._status_event = None
-        from .rasterization import _pinned_pool
-        still = []
-        for hc, ev in self._seen_counts:
-            if hc is None:
-                continue
-            if ev.query():
-                (F.release_counts4 if hc.numel() == 4 else _pinned_pool.append)(hc)
-            else:
-                still.append((hc, ev))
-        self._seen_counts = still
         if self._use_capacity and max_i > 0:
             want = ((int(max_i * self._cap_margin) + 65535) // 65536) * 65536
             if self._i_cap is None or want > self._i_cap or max_i > self._i_cap:
@@ -805,7 +790,7 @@ class RenderStep:
             self._throttle()                                 # first: the step that just left the window has finished, its word is readable
             self.poll_capacity(_internal=True)               # non-blocking: counts / overflow words of the finished steps (an overflow
                                                              # seen here is kept for the caller's next poll_capacity())
-            out = self._step_fused(cameras, upstream, all_reduce, keep_images)
+            out = self._step(cameras, upstream, all_reduce, keep_images)
             if self._in_flight is not None:
                 ev = torch.cuda.Event(); ev.record()
                 self._in_flight.append(ev)

@@ -84,6 +84,26 @@ def depth_range(host_counts: Tensor):
     return 0xffffffff - int(host_counts[2]), int(host_counts[3])
 
 
+def learn_depth_range(lo: Optional[int], hi: Optional[int], host_counts: Tensor):
+    """The depth-bit range (lo, hi) seen so far (None, None: nothing yet), widened by a finished view's pinned counts."""
+    rng = depth_range(host_counts)
+    if rng is None:
+        return lo, hi
+    return (rng[0] if lo is None else min(lo, rng[0])), (rng[1] if hi is None else max(hi, rng[1]))
+
+
+def binning_keys(lo: Optional[int], hi: Optional[int]):
+    """(key_bits, key_base) of the binning keys for the depth-bit range (lo, hi) seen so far: 24-bit keys (three depth passes instead
+    of four) -- key = depth bits - key_base with half an octave of room below the smallest depth seen -- while the range fits, else
+    32-bit keys.  A view outside the range is reported through the status word (word 3)."""
+    if lo is None:
+        return 32, 0
+    base = max(0, lo - (1 << 22))
+    if hi - base < (1 << 24) - (1 << 21):
+        return 24, base
+    return 32, 0
+
+
 def bin_stage(fr: Front, i_cap: Optional[int], status: Optional[Tensor], prepare: bool = True, binned=None):
     """A2-A4 + the compositor's record stream for a front; exact mode (i_cap None) waits for that view's (V, I) -- the one host
     synchronisation of the forward, as upstream; capacity mode sizes everything by (N, i_cap) and reads the counts on the device.

@@ -93,10 +93,7 @@ class _Capacity:
         r = max(i, 1) / float(max(n, 1))
         if self.ratio is None or r > self.ratio:
             self.ratio = r
-        rng = F.depth_range(host_counts)
-        if rng is not None:
-            self.key_lo = rng[0] if self.key_lo is None else min(self.key_lo, rng[0])
-            self.key_hi = rng[1] if self.key_hi is None else max(self.key_hi, rng[1])
+        self.key_lo, self.key_hi = F.learn_depth_range(self.key_lo, self.key_hi, host_counts)
 
     def i_cap(self, n: int) -> Optional[int]:
         if self.ratio is None:
@@ -107,14 +104,8 @@ class _Capacity:
         return ((want + gran - 1) // gran) * gran
 
     def keys(self) -> Tuple[int, int]:
-        """(key_bits, key_base) for the next view: 24-bit keys (three depth passes instead of four) with half an octave of room
-        below the smallest depth seen, while the range seen fits."""
-        if self.key32 or self.key_lo is None:
-            return 32, 0
-        base = max(0, self.key_lo - (1 << 22))
-        if self.key_hi - base < (1 << 24) - (1 << 21):
-            return 24, base
-        return 32, 0
+        """(key_bits, key_base) for the next view (front.binning_keys)."""
+        return (32, 0) if self.key32 else F.binning_keys(self.key_lo, self.key_hi)
 
 
 _states: Dict[int, _DeviceState] = {}
