@@ -49,11 +49,13 @@ def view_matrix(c2w: Tensor) -> Tensor:
     """world->camera 4x4 in OpenCV convention (rfstudio/graphics/_cameras.py:299-314)."""
     R = c2w[..., :3, :3]
     T = c2w[..., :3, 3:4]
-    R = R * torch.tensor([1.0, -1.0, -1.0], device=R.device, dtype=R.dtype)
+    # no host data may reach a device pose: a tensor built from a host list (or a host scalar assigned into it) is a pageable
+    # host-to-device copy, which blocks the host until the stream has drained.  Columns y and z are negated, entries filled.
+    R = torch.cat((R[..., :1], -R[..., 1:]), dim=-1)
     R_inv = R.transpose(-1, -2)
     T_inv = R_inv @ -T
     out = c2w.new_zeros(c2w.shape[:-2] + (4, 4))
-    out[..., 3, 3] = 1.0
+    out[..., 3, 3].fill_(1.0)
     out[..., :3, :3] = R_inv
     out[..., :3, 3:4] = T_inv
     return out
@@ -61,7 +63,8 @@ def view_matrix(c2w: Tensor) -> Tensor:
 
 def intrinsic_matrix(fx, fy, cx, cy, device=None, dtype=torch.float32) -> Tensor:
     K = torch.zeros(3, 3, device=device, dtype=dtype)
-    K[0, 0] = fx; K[1, 1] = fy; K[0, 2] = cx; K[1, 2] = cy; K[2, 2] = 1.0
+    for (r, c), v in (((0, 0), fx), ((1, 1), fy), ((0, 2), cx), ((1, 2), cy), ((2, 2), 1.0)):
+        K[r, c].fill_(v)                       # (`K[r, c] = v` would copy a host scalar: a synchronisation)
     return K
 
 

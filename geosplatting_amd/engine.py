@@ -143,12 +143,15 @@ class RenderStep:
             self.bucket = GradBucket(params.shapes(), params.means.device, comm_stream=self.bucket.comm_stream)
 
     # ------------------------------------------------------------------------------------------------- fused path
-    def _camera_tensors(self, cam: Camera):
+    def _camera_tensors(self, cam: Camera, stream: torch.cuda.Stream):
         """Device copies of (view matrix, K, camera position) of a camera, cached per POSE TENSOR: the entry keeps a reference to
         `cam.c2w` (so CPython cannot recycle its id while the entry lives) together with the tensor's version counter (an
         in-place update of the pose bumps it) and the intrinsics -- a hit therefore costs no device-to-host copy and no
         synchronisation, also for device-resident cameras and inside a graph capture; a training loop that builds new Camera
-        objects every step simply misses.  Bounded, oldest entry evicted."""
+        objects every step simply misses.  Bounded, oldest entry evicted.
+        A miss builds the tensors on `stream`, the front stream that reads them first, which must already be ordered behind the
+        caller's stream (a device-resident pose may have been written there); the other front stream waits for them (as
+        viewbatch.camera_tensors)."""
         c2w = cam.c2w
         key = id(c2w)
         intr = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.width), int(cam.height))
@@ -162,8 +165,13 @@ class RenderStep:
         dev = self.p.means.device
         if len(self._cam_cache) >= 1024:
             self._cam_cache.pop(next(iter(self._cam_cache)))
-        tensors = (cam.view_matrix.to(dev, torch.float32).contiguous(), cam.intrinsic_matrix.to(dev, torch.float32).contiguous(),
-                   c2w.detach()[:, 3].to(dev, torch.float32).contiguous())
+        with torch.cuda.stream(stream):
+            tensors = (cam.view_matrix.to(dev, torch.float32).contiguous(), cam.intrinsic_matrix.to(dev, torch.float32).contiguous(),
+                       c2w.detach()[:, 3].to(dev, torch.float32).contiguous())
+            ev = torch.cuda.Event(); ev.record(stream)
+        for sd in self._side_stream:
+            if sd is not stream:
+                sd.wait_event(ev)
         self._cam_cache[key] = (c2w, c2w._version, intr, tensors, fp)
         return tensors
 
@@ -171,15 +179,23 @@ class RenderStep:
         """Forget every cached (view matrix, K, position) triple: for callers that rewrite DEVICE-resident poses behind autograd's back."""
         self._cam_cache.clear()
 
-    def _geometry(self, cameras, bin_first: bool) -> _Geometry:
+    def _activations(self, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
+        """The once-per-step exp / sigmoid activations of the scales and opacities on the current stream (into `out` if given)."""
+        p = self.p
+        if out is None:
+            return p.scales.detach().exp(), torch.sigmoid(p.opacities.detach()).squeeze(-1).contiguous()
+        torch.exp(p.scales.detach(), out=out[0])
+        torch.sigmoid(p.opacities.detach().squeeze(-1), out=out[1])
+        return out
+
+    def _geometry(self, cameras, bin_first: bool, act: Optional[Tuple[Tensor, Tensor]] = None) -> _Geometry:
         """First phase of a step: what does not need the pyramid -- activations, streams, key width -- and, with `bin_first` in
         capacity mode, the GEOMETRY of the first view (projection, keys, binning: gs_front_fwd without records) on a front stream, so
         that it runs UNDER the prefilter forward instead of behind it (the step used to start its first compositor 0.9 ms after the
-        prefilter ended)."""
+        prefilter ended).  `act`: the activations, already computed (capture_views)."""
         p = self.p
         dev = p.means.device
-        scales_act = p.scales.detach().exp()
-        opac_act = torch.sigmoid(p.opacities.detach()).squeeze(-1).contiguous()
+        scales_act, opac_act = act if act is not None else self._activations()
         main = torch.cuda.current_stream(dev)
         if self._use_capacity and self._status is None:      # zero-filled on the main stream BEFORE the side streams fork from it
             self._status = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -198,8 +214,8 @@ class RenderStep:
             # (the geometry of ONE view: of two, beside the prefilter, costs more than it hides -- 563 against 580 views/s)
             side = self._side_stream[0]
             ev_a = torch.cuda.Event(); ev_a.record(main)
-            cam_t = self._camera_tensors(cameras[0])
             side.wait_event(ev_a)
+            cam_t = self._camera_tensors(cameras[0], side)      # (behind ev_a: a device-resident pose is final on the caller's stream)
             with torch.cuda.stream(side):
                 fr = self._front(geo, cameras[0], cam_t, None, records=False)
                 binned, _, _ = F.bin_stage(fr, i_cap, self._status, prepare=False)
@@ -227,7 +243,8 @@ class RenderStep:
         it needs the pyramid but not the binning, so it replays BESIDE the rest of the geometry graph (projection keys, five radix
         passes, emission: 0.25 ms per view) instead of behind it.  Returns the fronts by view index, for _views."""
         _, e = self._env_args(env)
-        return {j: self._front(geo, cameras[j], self._camera_tensors(cameras[j]), e, binning=False) for j in sorted(geo.early)}
+        cur = torch.cuda.current_stream(self.p.means.device)
+        return {j: self._front(geo, cameras[j], self._camera_tensors(cameras[j], cur), e, binning=False) for j in sorted(geo.early)}
 
     def _pyramid(self, sharded: bool, world: int) -> TextureSplitSum:
         """The pyramid of this step: the prefilter forward (sharded over the ranks: splitsum.py), or without the prefilter in the step
@@ -327,9 +344,11 @@ class RenderStep:
         defer_tail = all_reduce and collectives_active() and n_chunks > 1 and N >= 4096
         tail_job = None
 
+        cam_ts = {}
+
         def start_view(cam, j):                              # S1-S3 + A1; (V, I) travel to the host asynchronously
-            cam_t = self._camera_tensors(cam)
             side = sides[j % len(sides)]
+            cam_t = cam_ts[j] = self._camera_tensors(cam, side)     # (a miss: built on `side`, which has forked from the caller's stream)
             if recs is not None and j in recs:               # (capture_views: the records graph has run)
                 return recs[j], j, side
             with torch.cuda.stream(side):                    # (binned under the prefilter: only the records (shading) are still missing)
@@ -362,7 +381,7 @@ class RenderStep:
         proj = [start_view(cameras[j], j) for j in range(min(2, n_views))]   # prologue: A(0), A(1), B1(0)
         binned = bin_view(proj.pop(0)) if n_views else None
         for i, cam in enumerate(cameras):
-            vm, K, cam_pos = self._camera_tensors(cam)
+            vm, K, cam_pos = cam_ts.pop(i)
             W, H = cam.width, cam.height
             s, V, I, ev = binned
             main.wait_event(ev)
@@ -559,7 +578,8 @@ class RenderStep:
     def _capture(self, n_pinned: int, record):
         """What capture() and capture_views() share.  `record(phase)` issues the work to be captured, each graph's share of it under
         `with phase():`.  It runs once eagerly on a side stream -- the allocator warm-up torch.cuda.graph asks for -- and once more
-        with every phase() a new graph (the later graphs share the first one's memory pool).  Returns (what that second run returned,
+        with every phase() a new graph (the later graphs share the first one's memory pool; phase(own_pool=True): a pool of its own,
+        for a graph that replays at the same time as another one).  Returns (what that second run returned,
         the graphs, check): check() synchronises and returns False if a view of the last replay exceeded the capacity OR left the
         depth range of the 24-bit binning keys baked into the graphs; they are then stale and `check.stale` is set."""
         dev = self.p.means.device
@@ -571,15 +591,15 @@ class RenderStep:
         warm = torch.cuda.Stream(device=dev)
         warm.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(warm):
-            record(contextlib.nullcontext)
+            record(lambda own_pool=False: contextlib.nullcontext())
         torch.cuda.current_stream(dev).wait_stream(warm)
         torch.cuda.synchronize(dev)
         self.poll_capacity(_internal=True)                    # an overflow of the warm-up step stays pending for the caller's next poll
         graphs = []
 
-        def phase():
+        def phase(own_pool: bool = False):
             graphs.append(torch.cuda.CUDAGraph())
-            return torch.cuda.graph(graphs[-1], pool=graphs[0].pool() if len(graphs) > 1 else None)
+            return torch.cuda.graph(graphs[-1], pool=graphs[0].pool() if (len(graphs) > 1 and not own_pool) else None)
         out = record(phase)
         counts = [hc for hc, _ in self._seen_counts]          # refreshed by every replay (D2H copies are graph nodes)
         self._seen_counts = []
@@ -659,20 +679,26 @@ class RenderStep:
         #   views graph   : record stream, compositor, loss cotangent, compositor backward, background tails -- behind both.
         # The last tail launch and every collective stay eager (_finish): its Gaussian-range chunks are summed over the ranks while the
         # next chunk is computed.
+        # The records graph reads the activations, and nothing orders it behind the geometry graph: they are computed on the caller's
+        # stream into these buffers BEFORE the geometry graph forks from it, and every graph only reads them.  It also runs while the
+        # geometry graph's temporaries are live, so it allocates from a pool of its own; the views graph, which replays behind both,
+        # shares the geometry graph's.
         two = os.environ.get("GEOSPLAT_GEO_GRAPH", "1") != "0"
+        act = (torch.empty_like(self.p.scales.detach()), torch.empty_like(self.p.opacities.detach().squeeze(-1)))
+        self._activations(act)
 
         def record(phase):                                     # (a captured phase: every forked stream joins before the capture ends)
             geo = recs = None
             if two:
                 with phase():
-                    geo = self._geometry(cameras, bin_first=True)
+                    geo = self._geometry(cameras, bin_first=True, act=act)
                     for sd in self._side_stream:
                         torch.cuda.current_stream(dev).wait_stream(sd)
-                with phase():
+                with phase(own_pool=True):
                     recs = self._records(cameras, geo, pyramid)
             with phase():
                 if geo is None:
-                    geo = self._geometry(cameras, bin_first=False)
+                    geo = self._geometry(cameras, bin_first=False, act=act)
                 ctx = self._views(cameras, upstream, all_reduce, keep_images, geo, env=pyramid, recs=recs)
                 if ctx.pstream is not None:
                     ctx.main.wait_stream(ctx.pstream)
@@ -689,15 +715,15 @@ class RenderStep:
             if check.stale:
                 raise RuntimeError("these captured views overflowed their capacity / key range (check() returned False): capture_views() again")
             cur = torch.cuda.current_stream(dev)
+            self._activations(act)                             # (read by all three graphs; the previous step's readers joined `cur`)
             if two:
-                geo_stream.wait_stream(cur)                    # (the parameters of this step are final on the caller's stream)
+                geo_stream.wait_stream(cur)                    # (the parameters and activations of this step are final on the caller's stream)
                 with torch.cuda.stream(geo_stream):
                     geo_graph.replay()
             env = self._pyramid(sharded, world)
             torch._foreach_copy_(slots, [env.base] + list(env.levels))
             if two:
-                # shading of the views: beside the geometry graph (nothing orders it behind the activations the geometry graph writes)
-                rec_graph.replay()
+                rec_graph.replay()                             # shading of the views: beside the geometry graph
                 cur.wait_stream(geo_stream)
             graph.replay()
             ctx.main = cur

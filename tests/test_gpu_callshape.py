@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import sphere_case
+from tests.util import compare_grads, sphere_case
 
 pytestmark = pytest.mark.gpu
 
@@ -55,18 +55,7 @@ def _run(sc, cams, ups, cuda, backward="one", subset=None, mode="pbr", tone="nai
     return [i.detach().clone() for i in imgs], {k: (None if v.grad is None else v.grad.detach().clone()) for k, v in lv.items()}
 
 
-def _compare(got, want, tol=2e-5):
-    for k, w in want.items():
-        a = got[k]
-        assert (a is None) == (w is None), k
-        if w is None:
-            continue
-        scale = float(w.abs().max())
-        if k == "quats" and want.get("scales") is not None:      # isotropic / flat splats: the rotation gradient is pure cancellation noise --
-            scale = max(scale, float(want["scales"].abs().max()))   # measured against the natural size of a covariance-perturbation gradient
-        err = float((a - w).abs().max()) / (scale + 1e-30)
-        print(f"  {k:10s} {err:.2e}")
-        assert err < (1e-4 if k in ("quats", "scales", "exposure") else tol), (k, err)
+_compare = compare_grads
 
 
 @pytest.mark.parametrize("mode,tone", [("pbr", "naive"), ("diffuse", "aces"), ("specular", "none")])

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests.util import same_step
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_VIEWS, RES, LEVEL = 4, 160, 3
@@ -79,12 +81,7 @@ def _engine(dev):
     return step, run
 
 
-def _same(ref, got):
-    for a, b in zip(ref[1], got[1]):
-        assert torch.equal(a, b)                                      # forward: same kernels on the same inputs
-    for k, w in ref[0].items():
-        scale = w.abs().max().item() + 1e-30
-        assert (got[0][k] - w).abs().max().item() / scale < 5e-5, k   # backward: order of the float atomics
+_same = same_step
 
 
 def test_capacity_protocol_equals_exact_mode():

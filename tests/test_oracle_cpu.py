@@ -47,6 +47,23 @@ def test_golden_cameras():
     assert np.allclose(cam_mod.view_matrix(c2w2).numpy(), g["lookat_view"], atol=1e-6)
 
 
+def test_view_matrix_and_intrinsics_keep_their_bits():
+    """view_matrix negates the y / z columns instead of multiplying by a host-built [1, -1, -1] (a pageable host-to-device copy,
+    i.e. a host synchronisation, for a device pose), intrinsic_matrix fills its entries one by one: the same bits as the products."""
+    g = torch.Generator().manual_seed(3)
+    c2w = torch.randn(5, 3, 4, generator=g)
+    R, T = c2w[..., :3, :3], c2w[..., :3, 3:4]
+    R_inv = (R * torch.tensor([1.0, -1.0, -1.0])).transpose(-1, -2)
+    want = torch.zeros(5, 4, 4)
+    want[..., 3, 3] = 1.0
+    want[..., :3, :3] = R_inv
+    want[..., :3, 3:4] = R_inv @ -T
+    assert torch.equal(cam_mod.view_matrix(c2w), want)
+    assert torch.equal(cam_mod.view_matrix(c2w[2]), want[2])
+    fx, fy, cx, cy = 1111.1111, 1111.2, 400.0, 399.7
+    assert torch.equal(cam_mod.intrinsic_matrix(fx, fy, cx, cy), torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]))
+
+
 def test_golden_math():
     g = gold("ref_math.npz")
     assert np.allclose(mesh_ref.safe_normalize(torch.tensor(g["v"])).numpy(), g["safe_normalize"], atol=1e-7)

@@ -44,3 +44,41 @@ def random_case(n, res, view=0, seed=1):
     sp = syn.random_splats(n, seed=seed)
     cam = orbit_cameras(4, 3.0, 30.0, res, res, hfov_degree=40.0)[view]
     return sp, cam
+
+
+N_VIEWS, RES, LEVEL = 4, 160, 3      # the small engine scene of the parallel / ordering tests
+
+
+def small_engine_scene():
+    """(scene, cameras, upstream cotangents on the host) of the small engine tests: level-3 sphere from the CPU restatement
+    (bit-identical Gaussians in every process), four 160 x 160 Blender-style views."""
+    sc = syn.sphere_scene(LEVEL, seed=2, cubemap_res=64, mesh_to_splats_fn=mesh_ref.scene_builder)
+    cams = syn.blender_cameras(N_VIEWS, RES, RES)
+    ups = [torch.rand(RES, RES, 4, generator=torch.Generator().manual_seed(50 + i)) * 2 - 1 for i in range(N_VIEWS)]
+    return sc, cams, ups
+
+
+def same_step(ref, got):
+    """Two runs of the same engine step, each (grads, images): images bit for bit (same kernels on the same inputs), gradients to
+    5e-5 of their largest magnitude (the order of the float atomics)."""
+    for a, b in zip(ref[1], got[1]):
+        assert torch.equal(a, b)
+    for k, w in ref[0].items():
+        scale = w.abs().max().item() + 1e-30
+        assert (got[0][k] - w).abs().max().item() / scale < 5e-5, k
+
+
+def compare_grads(got, want, tol=2e-5):
+    """Gradients of the fused paths against the op-by-op autograd decomposition (GEOSPLAT_SPLAT=ops): max-norm relative error
+    below `tol`, 1e-4 for quats / scales / exposure."""
+    for k, w in want.items():
+        a = got[k]
+        assert (a is None) == (w is None), k
+        if w is None:
+            continue
+        scale = float(w.abs().max())
+        if k == "quats" and want.get("scales") is not None:      # isotropic / flat splats: the rotation gradient is pure cancellation noise --
+            scale = max(scale, float(want["scales"].abs().max()))   # measured against the natural size of a covariance-perturbation gradient
+        err = float((a - w).abs().max()) / (scale + 1e-30)
+        print(f"  {k:10s} {err:.2e}")
+        assert err < (1e-4 if k in ("quats", "scales", "exposure") else tol), (k, err)
