@@ -196,15 +196,14 @@ __device__ void cube_fetch(const float* __restrict__ tex, int R, const float* d,
     }
 }
 
-// ---- wave-aggregated texel-gradient scatter ---------------------------------------------------------------
+// ---- texel-gradient scatter --------------------------------------------------------------------------------
 // Neighbouring Gaussians of a surface reflect into the same few texels of the coarse pyramid levels, so the
-// 64 lanes of a wave would send many fp32 atomics at identical addresses (the L2 serialises them: 1.26 ms of
-// the 1.3 ms shading backward at 2 M Gaussians).  Lanes that target the SAME address are summed in registers
-// (leader loop: broadcast the first pending address, ballot the matches, DPP-reduce, one lane commits);
-// incoherent lanes fall back to plain atomics after GS_AGG_ROUNDS leaders.
-#ifndef GS_AGG_ROUNDS
-#define GS_AGG_ROUNDS 0    // round 1 (permute commit): 0 / 1 / 2 / 6 rounds = 0.807 / 0.802 / 0.833 / 0.846 ms (kernel + glue); round 2 (LDS-staged commit, kernel alone): 0 / 1 rounds = 364 / 381 us
-#endif
+// 64 lanes of a wave send many fp32 atomics at identical addresses (the L2 serialises them: 1.26 ms of
+// the 1.3 ms shading backward at 2 M Gaussians in round 1).  Every lane commits its own contribution through the
+// row-pair commit below.  Summing the lanes that target the SAME address in registers first (leader loop: broadcast
+// the first pending address, ballot the matches, DPP-reduce, one lane commits) was measured and does not pay:
+// round 1 (permute commit): 0 / 1 / 2 / 6 leader rounds = 0.807 / 0.802 / 0.833 / 0.846 ms (kernel + glue);
+// round 2 (LDS-staged commit, kernel alone): 0 / 1 rounds = 364 / 381 us.
 template <bool XCD_LOCAL>
 __device__ __forceinline__ void gs_add_scoped(float* p, float v)
 {
@@ -239,11 +238,7 @@ __device__ __forceinline__ void wave_commit6_lds(float* stage, float* pa, float*
         const bool second = ch >= 3;
         float* base = (float*)sp[(second ? 64 : 0) + src];
         const float val = sv[ch * 64 + src];
-#ifndef GS_EXPERIMENT_NO_GLOBAL_TEXEL_ATOMICS
         if (base != nullptr) gs_add_scoped<XCD_LOCAL>(base + (second ? ch - 3 : ch), val);
-#else
-        if (base != nullptr && val == 123456.0f) base[0] = val;      /* timing experiment only */
-#endif
     }
 }
 
@@ -270,47 +265,17 @@ __device__ __forceinline__ void wave_commit6(float* pa, float* pb, const float (
         float val = x[0];
 #pragma unroll
         for (int c = 1; c < 6; ++c) val = (ch == c) ? x[c] : val;
-#ifndef GS_EXPERIMENT_NO_GLOBAL_TEXEL_ATOMICS
         if (base != nullptr) gs_add_scoped<XCD_LOCAL>(base + c3, val);
-#else
-        if (base != nullptr && val == 123456.0f) base[c3] = val;      /* timing experiment only */
-#endif
     }
 }
 
-// aggregate lanes that hit the same row pair (same first AND second texel), then commit transposed
+// commit one row pair per lane, transposed (a lane without one passes two null pointers)
 template <bool XCD_LOCAL>
-__device__ __forceinline__ void wave_agg_add6(float* pa, float* pb, const float (&v)[6], float* stage = nullptr)
+__device__ __forceinline__ void wave_add6(float* pa, float* pb, const float (&v)[6], float* stage = nullptr)
 {
-    const int lane = (int)(threadIdx.x & 63);
-    unsigned long long ka = (unsigned long long)pa;
-    const unsigned long long kb = (unsigned long long)pb;
-    unsigned long long remaining = __ballot(pa != nullptr || pb != nullptr);
-    int singles = 0;
     float* enda = nullptr; float* endb = nullptr;
     float pv[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-    bool mine = (pa != nullptr || pb != nullptr);
-    for (int round = 0; round < GS_AGG_ROUNDS && remaining != 0ull && singles < 2; ++round) {
-        const int leader = __builtin_ctzll(remaining);
-        const unsigned long long la = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(ka >> 32), leader) << 32) |
-                                      (unsigned)__builtin_amdgcn_readlane((int)(unsigned)ka, leader);
-        const unsigned long long lb = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(kb >> 32), leader) << 32) |
-                                      (unsigned)__builtin_amdgcn_readlane((int)(unsigned)kb, leader);
-        const bool same = mine && ka == la && kb == lb;
-        const unsigned long long m = __ballot(same);
-        float s[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) s[c] = gs_wave_sum(same ? v[c] : 0.0f);
-        if (lane == leader) {
-            enda = pa; endb = pb;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) pv[c] = s[c];
-        }
-        if (same) mine = false;
-        remaining &= ~m;
-        singles = (__popcll(m) == 1) ? singles + 1 : 0;
-    }
-    if (mine) {                                        // not aggregated: commit the lane's own contribution
+    if (pa != nullptr || pb != nullptr) {
         enda = pa; endb = pb;
 #pragma unroll
         for (int c = 0; c < 6; ++c) pv[c] = v[c];
@@ -335,7 +300,7 @@ __device__ __forceinline__ void cube_scatter_wave(float* grad_tex, const CubeFp&
             p[j] = on ? grad_tex + (size_t)fp.idx[i] * 3 : nullptr;
             v[3 * j] = g[0] * w; v[3 * j + 1] = g[1] * w; v[3 * j + 2] = g[2] * w;
         }
-        wave_agg_add6<XCD_LOCAL>(p[0], p[1], v, stage);
+        wave_add6<XCD_LOCAL>(p[0], p[1], v, stage);
     }
 }
 
@@ -374,14 +339,10 @@ __device__ __forceinline__ void wave_commit6_lds_tagged(float* stage, float* pa,
             const unsigned long long tagged = sp[(second ? 64 : 0) + src];
             float* base = (float*)(tagged & ~1ull);
             const float val = sv[ch * 64 + src];
-#ifndef GS_EXPERIMENT_NO_GLOBAL_TEXEL_ATOMICS
             if (base != nullptr) {
                 float* dst = base + (second ? ch - 3 : ch);
                 if (tagged & 1ull) gs_atomic_add_xcd(dst, val); else gs_atomic_add(dst, val);
             }
-#else
-            if (base != nullptr && val == 123456.0f) base[0] = val;      /* timing experiment only */
-#endif
         }
     }
 }

@@ -573,9 +573,7 @@ struct TailViewsDev { TailViewDev v[GS_TAIL_MAX_VIEWS]; int n; };
 //                             LDS texel copies; writes v_means (its view-direction part), v_normals, v_kd, v_ks
 //   tail_proj_pairs_kernel  : A7; no LDS but the camera table; ADDS its part to v_means, writes v_quats, v_scales, v_opacities
 // Price: the 64-byte gradient record and the packed slot of a pair are read by both (+1.1 GB per 8-view step).
-#ifndef GS_TAILP_BLOCK
 #define GS_TAILP_BLOCK 1024        // sixteen waves per CU on one set of LDS texel copies
-#endif
 struct TailViewLds {
     unsigned long long vis, v_packed, packed_index;
     float cam[16];                 // R[9], t[3], fx, fy, cx, cy

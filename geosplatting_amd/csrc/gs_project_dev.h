@@ -150,9 +150,8 @@ __device__ __forceinline__ void tile_range_exact(float mx, float my, int radius,
 // Every descriptor word is an aligned 8-byte granule written by one relaxed agent-scope atomic store and
 // read with relaxed agent-scope atomic loads (L1-bypassing, the "data is the flag" hand-off): no fence is
 // needed because nothing but the granule itself crosses workgroups.
-#ifndef GS_PROJ_BLOCK
 #define GS_PROJ_BLOCK 512         // chunk of the chained scan = workgroup (alone: 1024 is 10 % faster than 256; under the three-stream overlap of the engine the 1024-thread blocks wait for residency next to the LDS-heavy compositor blocks: 512 -> +3 % views/s); 256 -> 1024 quarters the same-address ticket
-#endif                             // atomics and descriptor traffic of the look-back: 0.185 -> 0.135 ms (stage incl. glue)
+                                   // atomics and descriptor traffic of the look-back: 0.185 -> 0.135 ms (stage incl. glue)
 #define GS_PROJ_WAVES (GS_PROJ_BLOCK / 64)
 #define GS_VALID_BIT  (1ull << 63)
 #define GS_SPIN_LIMIT (1 << 22)

@@ -26,10 +26,6 @@
 
 #define GS_TILE 16
 #define GS_ALPHA_MIN (1.0f / 255.0f)
-#ifndef GS_BWD_ROW_COMMIT
-#define GS_BWD_ROW_COMMIT 0      // 1 = every DPP row commits its own partial sums (no cross-row exchange): measured 2.2x SLOWER --
-                                 // the kernel sits at the memory-side atomic request rate (~4 requests per survivor already)
-#endif
 
 // Diagnostic build only (scripts/raster_stats.py compiles this file with -DGS_RASTER_STATS into a scratch .so):
 // counts wave-batches, ballot survivors and evaluated/valid lane-pairs.  Never defined in the product library.
@@ -111,35 +107,9 @@ extern "C" int gs_raster_timeline_read(unsigned long long* host, int n_blocks, i
 
 // ---------------------------------------------------------------------------------------------------
 // stream build: rec0 = {mx, my, 0.5a, b}, rec1 = {0.5c, opacity, hx, hy}, rec2 = {c0, c1, c2, bits(g)}
-// (hx < 0 marks "can never reach alpha_min").  One thread per sorted intersection.
-__global__ void __launch_bounds__(256)
-build_stream_kernel(GsCount ic, int D, const int32_t* __restrict__ flatten_ids, const float* __restrict__ means2d,
-                    const float* __restrict__ conics, const float* __restrict__ opacities,
-                    const float* __restrict__ colors, float4* __restrict__ rec0, float4* __restrict__ rec1,
-                    float4* __restrict__ rec2)
-{
-    const int n_isects = (int)gs_count(ic);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_isects) return;
-    const int g = flatten_ids[i];
-    const float2 m = *reinterpret_cast<const float2*>(means2d + 2 * (size_t)g);
-    const float ca = conics[3 * (size_t)g], cb = conics[3 * (size_t)g + 1], cc = conics[3 * (size_t)g + 2];
-    const float op = opacities[g];
-    float hx = -1.0f, hy = -1.0f;
-    if (!alpha_extent(ca, cb, cc, op, hx, hy)) { hx = -1.0f; hy = -1.0f; }
-    rec0[i] = make_float4(m.x, m.y, 0.5f * ca, cb);
-    rec1[i] = make_float4(0.5f * cc, op, hx, hy);
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-    if (D <= 3) {
-        c0 = colors[(size_t)g * D];
-        if (D > 1) c1 = colors[(size_t)g * D + 1];
-        if (D > 2) c2 = colors[(size_t)g * D + 2];
-    }
-    rec2[i] = make_float4(c0, c1, c2, __int_as_float(g));
-}
-
-// Same stream from the PACKED per-visible records written by gs_pack_visible (3 aligned 16-byte gathers per
-// intersection instead of 8 scalar ones: the gather, not the 48-byte store, bounds this kernel).
+// (hx < 0 marks "can never reach alpha_min").  One thread per sorted intersection, gathering the PACKED per-visible
+// records written by gs_pack_visible (3 aligned 16-byte gathers per intersection instead of 8 scalar ones: the gather,
+// not the 48-byte store, bounds this kernel).
 __global__ void __launch_bounds__(256)
 build_stream_packed_kernel(GsCount ic, const int32_t* __restrict__ flatten_ids, const float4* __restrict__ vis,
                            float4* __restrict__ rec0, float4* __restrict__ rec1, float4* __restrict__ rec2)
@@ -282,13 +252,6 @@ __device__ __forceinline__ void active_rect_i(unsigned long long act, int& xmin,
     ymin = __builtin_ctzll(act) >> 3; ymax = (63 - __builtin_clzll(act)) >> 3;
 }
 
-#ifndef GS_WALK_PAIRS
-#define GS_WALK_PAIRS 1           // packed candidate PAIRS popped per lane and trip in the forward walk
-#endif
-#ifndef GS_LANES_EXACT_MASK
-#define GS_LANES_EXACT_MASK 1
-#endif
-
 // 64-bit mask (bit y*8+x) of the quadrant pixels whose centre can lie inside the record's {alpha >= 1/255} set, clipped to
 // the active rectangle.  A SUPERSET is all that is needed (every popped pair is tested exactly); the tighter it is, the
 // shorter the per-pixel lists: the bounding rectangle of a thin diagonal ellipse holds twice the pixels of the ellipse.
@@ -303,7 +266,7 @@ __device__ __forceinline__ unsigned long long record_pixel_mask(bool ok, float m
     const float x0f = (float)xmin, x1f = (float)xmax;
     if (!ok) return 0ull;
     const int y0 = ymin, y1 = ymax;
-    if (!GS_LANES_EXACT_MASK || !(ha > 1e-12f)) {                            // the active rectangle (degenerate conics)
+    if (!(ha > 1e-12f)) {                                                    // the active rectangle (degenerate conics)
         const unsigned colmask = ((2u << xmax) - 1u) & ~((1u << xmin) - 1u);
         const unsigned rep = colmask * 0x01010101u;
         const unsigned long long rows = (~0ull >> (8 * (7 - y1))) & (~0ull << (8 * y0));
@@ -442,10 +405,7 @@ __device__ __forceinline__ void raw_drain(RawBatch& a, RawBatch& b, RawBatch& c)
 }
 __device__ __forceinline__ void raw_wait(RawBatch& b)
 {
-#ifndef GS_RAW_WAIT
-#define GS_RAW_WAIT "s_waitcnt vmcnt(6)"
-#endif
-    asm volatile(GS_RAW_WAIT : "+v"(b.r0), "+v"(b.r1), "+v"(b.r2) : : "memory");
+    asm volatile("s_waitcnt vmcnt(6)" : "+v"(b.r0), "+v"(b.r1), "+v"(b.r2) : : "memory");
 }
 
 // centre and half-extent (pixel-centre coordinates) of the bounding rectangle of the active lanes of a quadrant wave
@@ -527,10 +487,7 @@ struct ToneBwd { int mode; const float* exposure; const float* render; const flo
 // lies behind its own termination (5 % of the popped candidates) -- see raster_bwd_log_kernel.
 struct CullLog { int32_t* idx; unsigned long long* mask; int32_t* count; };
 
-#ifndef GS_WIN_Q_SLOTS
-#define GS_WIN_Q_SLOTS 192
-#endif
-static constexpr int GS_WIN_Q = GS_WIN_Q_SLOTS;
+static constexpr int GS_WIN_Q = 192;
 static constexpr int GS_WIN_Q_BYTES = GS_WIN_Q * (16 + 16 + 8 + 4);
 
 __device__ __forceinline__ int win_wrap(int s) { return s >= GS_WIN_Q ? s - GS_WIN_Q : s; }
@@ -813,10 +770,7 @@ raster_fwd_window_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
 // registers (dx = mx - px is a function of the pixel index), from which the nine gradients follow:
 //     v_xy = (2 ha Mx + b My, b Mx + 2 hc My),  v_conic = (Mxx/2, Mxy, Myy/2),  v_opacity = -M0 / opacity.
 // The sums are exact per-lane fp32 FMAs in pixel order: the per-(quadrant, Gaussian) result is deterministic.
-#ifndef GS_PAIR_CAP_N
-#define GS_PAIR_CAP_N 448
-#endif
-static constexpr int GS_PAIR_CAP = GS_PAIR_CAP_N;                       // pair slots per dense batch (records beyond wait for the next one)
+static constexpr int GS_PAIR_CAP = 448;                                 // pair slots per dense batch (records beyond wait for the next one)
 template <int CD>
 struct Lanes2Lds {
     static constexpr int NV = 6 + CD;
@@ -842,15 +796,6 @@ raster_bwd_lanes2_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
     constexpr int NV = 6 + CD;
     constexpr int RPI = 64 / NV;
     extern __shared__ __align__(16) unsigned char gs_lds_raw[];
-#ifdef GS_EXP_SKIP_HEAVY
-    if ((int)blockIdx.x < GS_EXP_SKIP_HEAVY) return;
-#endif
-#ifdef GS_EXP_ONLY_HEAVY
-    if ((int)blockIdx.x >= GS_EXP_ONLY_HEAVY) return;
-#endif
-#ifdef GS_EXP_PRIO
-    if ((int)blockIdx.x < GS_EXP_PRIO) __builtin_amdgcn_s_setprio(3);
-#endif
     const int tile = tile_order[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int tx = tile % tile_w, ty = tile / tile_w;
@@ -1203,10 +1148,7 @@ raster_bwd_lanes2_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
 // transposes, scans, reduction set-up and commit), and the kernel ends at 169 M VALU wave instructions against 152 M: 0.43 ms alone
 // (0.45 with the chunks decoupled through carried state and late pulls) against 0.385, 671-684 against 698-702 views/s.  LDS bank
 // conflicts were NOT the reason (20.0 M against 20.8 M conflict cycles, rocprofv3 --pmc).
-#ifndef GS_LOG_PAIR_SLOTS
-#define GS_LOG_PAIR_SLOTS 790
-#endif
-static constexpr int GS_LOG_PAIR_CAP = GS_LOG_PAIR_SLOTS;                       // + two spare slots (stores of lanes without a candidate land in [790])
+static constexpr int GS_LOG_PAIR_CAP = 790;                                     // + two spare slots (stores of lanes without a candidate land in [790])
 #ifndef GS_LOG_ASSIST_MAX                                         //   + 64 bytes: the pixels of an assisted walk trip
 #define GS_LOG_ASSIST_MAX 16                                      // walk trips with at most this many busy pixels are ASSISTED (0: never)
 #endif
@@ -1386,7 +1328,7 @@ raster_bwd_log_kernel(int W, int H, int tile_w, int n_tiles, int D, const int32_
 #endif
             if (__ballot(list != 0ull) != 0ull) do {
                 GS_STAT(6, 1);
-#if defined(GS_RASTER_STATS) && !defined(GS_RASTER_PHASES) && !defined(GS_HIST_REDUCTION)
+#if defined(GS_RASTER_STATS) && !defined(GS_RASTER_PHASES)
                 { const int na = __popcll(__ballot(list != 0ull));
 #pragma unroll
                   for (int k = 0; k < 8; ++k) walk_hist[k] += (na > 8 * k && na <= 8 * k + 8) ? 1 : 0; }
@@ -1565,11 +1507,6 @@ raster_bwd_log_kernel(int W, int H, int tile_w, int n_tiles, int D, const int32_
                 v2f m1 = (v2f)(0.0f), m2 = (v2f)(0.0f), c01 = (v2f)(0.0f);
                 if (__ballot(m != 0ull) != 0ull) do {                 // (rotated by hand: the while form copied all nine accumulators every trip)
                     GS_STAT2(7, 1);
-#if defined(GS_RASTER_STATS) && !defined(GS_RASTER_PHASES) && defined(GS_HIST_REDUCTION)      /* bank 3 counts the REDUCTION's trips instead */
-                    { const int na = __popcll(__ballot(m != 0ull));
-#pragma unroll
-                      for (int k = 0; k < 8; ++k) walk_hist[k] += (na > 8 * k && na <= 8 * k + 8) ? 1 : 0; }
-#endif
 #ifdef GS_RASTER_PHASES
                     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_raster_stats[7], 1ull);
 #endif
@@ -1623,11 +1560,7 @@ raster_bwd_log_kernel(int W, int H, int tile_w, int n_tiles, int D, const int32_
                         const float v = stage[j * NV + k];
                         if (v != 0.0f) {
                             const int g = __float_as_int(qc[j].w);
-#ifndef GS_EXP_NOATOMIC
                             gs_atomic_add(v_packed + (size_t)g * rec_stride + k, v);
-#else
-                            if (v == 123456.0f) v_packed[(size_t)g * rec_stride + k] = v;      /* timing experiment only */
-#endif
                         }
                     }
                 }
@@ -1702,30 +1635,29 @@ static RasterWs carve(void* ws, int64_t n_isects, int V, int tiles)
     return r;
 }
 
-// Capacity protocol: while a *_cap entry point is on the stack, the kernels launched by the functions below read the actual
-// intersection count from device memory (counts_dev = {V, I} as written by gs_project_fwd) and treat the scalar as a capacity.
-static thread_local const long long* t_counts_dev = nullptr;
-struct CountsScope {
-    explicit CountsScope(const int64_t* c) { t_counts_dev = (const long long*)c; }
-    ~CountsScope() { t_counts_dev = nullptr; }
+// What a compositor launch takes besides its plain arguments, all zero by default:
+//   * counts: the capacity protocol (*_cap, *_tone*): the kernels read the actual intersection count from device memory
+//     (counts = {V, I} as written by gs_project_fwd) and treat the scalar as a capacity;
+//   * tone_fwd / tone_bwd: the S4 tone map inside the compositor (gs_raster_*_tone*; zero = plain compositor);
+//   * log: the forward's cull log for the backward (gs_raster_*_log*).
+struct RasterOpts {
+    const int64_t* counts = nullptr;
+    ToneFwd tone_fwd = { 0, nullptr, nullptr };
+    ToneBwd tone_bwd = { 0, nullptr, nullptr, nullptr, nullptr };
+    CullLog log = { nullptr, nullptr, nullptr };
 };
-static GsCount isect_count(int64_t n) { return GsCount{ (long long)n, t_counts_dev ? t_counts_dev + 1 : nullptr }; }
-// The same mechanism for the tone-mapping variants: while a gs_raster_*_tone* entry point is on the stack the launches below hand
-// its ToneFwd / ToneBwd to the kernels (zero = plain compositor).
-static thread_local ToneFwd t_tone_fwd = { 0, nullptr, nullptr };
-static thread_local ToneBwd t_tone_bwd = { 0, nullptr, nullptr, nullptr, nullptr };
-static thread_local CullLog t_cull_log = { nullptr, nullptr, nullptr };
-struct CullLogScope { explicit CullLogScope(const CullLog& l) { t_cull_log = l; } ~CullLogScope() { t_cull_log = CullLog{ nullptr, nullptr, nullptr }; } };
-struct ToneFwdScope { explicit ToneFwdScope(const ToneFwd& t) { t_tone_fwd = t; } ~ToneFwdScope() { t_tone_fwd = ToneFwd{ 0, nullptr, nullptr }; } };
-struct ToneBwdScope { explicit ToneBwdScope(const ToneBwd& t) { t_tone_bwd = t; } ~ToneBwdScope() { t_tone_bwd = ToneBwd{ 0, nullptr, nullptr, nullptr, nullptr }; } };
+static GsCount isect_count(int64_t n, const RasterOpts& o)
+{
+    return GsCount{ (long long)n, o.counts ? (const long long*)o.counts + 1 : nullptr };
+}
 
 template <int CD>
 static int launch_fwd(int W, int H, int D, const RasterWs& ws, const float* colors, const float* background,
                       int64_t n_isects, const int32_t* offsets, float* render, float* alphas, int32_t* last_ids,
-                      hipStream_t s)
+                      hipStream_t s, const RasterOpts& o)
 {
     const int tile_w = (W + GS_TILE - 1) / GS_TILE, tile_h = (H + GS_TILE - 1) / GS_TILE;
-    if (t_tone_fwd.image && !(CD == 3 && D == 3 && background == nullptr)) {
+    if (o.tone_fwd.image && !(CD == 3 && D == 3 && background == nullptr)) {
         gs_set_error("gs_raster_composite_tone: needs D == 3 and no background");
         return GS_EINVAL;
     }
@@ -1737,8 +1669,8 @@ static int launch_fwd(int W, int H, int D, const RasterWs& ws, const float* colo
         if (lds > 64 * 1024)
             GS_CHECK_HIP(hipFuncSetAttribute((const void*)raster_fwd_window_kernel<CD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(raster_fwd_window_kernel<CD>, dim3(tile_w * tile_h), dim3(256), lds, s, W, H, tile_w, tile_w * tile_h, D,
-                           ws.order, ws.rec0, ws.rec1, ws.rec2, colors, background, isect_count(n_isects), offsets, render, alphas,
-                           last_ids, t_tone_fwd, t_cull_log, t_cull_log.count ? ws.bo : BwdOrder{ nullptr, nullptr });
+                           ws.order, ws.rec0, ws.rec1, ws.rec2, colors, background, isect_count(n_isects, o), offsets, render, alphas,
+                           last_ids, o.tone_fwd, o.log, o.log.count ? ws.bo : BwdOrder{ nullptr, nullptr });
         GS_CHECK_LAUNCH();
         return GS_OK;
     }
@@ -1761,27 +1693,8 @@ static int raster_check(const char* who, int W, int H, int tile_size, int D, int
 // that overlaps streams runs it next to the sort, away from the VALU-bound compositor).
 static int raster_prepare_impl(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
                                const float* opacities, const float* colors, const float* vis_records, int64_t n_isects,
-                               const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream);
-
-extern "C" int gs_raster_prepare(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
-                                 const float* opacities, const float* colors, int64_t n_isects, const int32_t* offsets,
-                                 const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream)
-{
-    return raster_prepare_impl(W, H, tile_size, D, V, means2d, conics, opacities, colors, nullptr, n_isects, offsets, flatten_ids,
-                               ws, ws_bytes, stream);
-}
-
-extern "C" int gs_raster_prepare_vis(int W, int H, int tile_size, int D, int V, const float* vis_records, int64_t n_isects,
-                                     const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(vis_records != nullptr || V == 0, "vis_records (written by gs_project_fwd_vis) must not be NULL");
-    return raster_prepare_impl(W, H, tile_size, D, V, nullptr, nullptr, nullptr, nullptr, vis_records, n_isects, offsets,
-                               flatten_ids, ws, ws_bytes, stream);
-}
-
-static int raster_prepare_impl(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
-                               const float* opacities, const float* colors, const float* vis_records, int64_t n_isects,
-                               const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream)
+                               const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream,
+                               const RasterOpts& o)
 {
     const int rc = raster_check("gs_raster_prepare", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
     if (rc != GS_OK) return rc;
@@ -1796,26 +1709,26 @@ static int raster_prepare_impl(int W, int H, int tile_size, int D, int V, const 
             GS_CHECK_LAUNCH();
             vis = r.vis;
         }
-        hipLaunchKernelGGL(build_stream_packed_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, isect_count(n_isects), flatten_ids,
+        hipLaunchKernelGGL(build_stream_packed_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, isect_count(n_isects, o), flatten_ids,
                            vis, r.rec0, r.rec1, r.rec2);
         GS_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, tiles, isect_count(n_isects), offsets, r.order, r.bo);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, tiles, isect_count(n_isects, o), offsets, r.order, r.bo);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
 
 // A5 proper on a prepared workspace
-extern "C" int gs_raster_composite(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
-                                   int64_t n_isects, const int32_t* offsets, float* render, float* alphas,
-                                   int32_t* last_ids, const void* ws, size_t ws_bytes, void* stream)
+static int raster_composite_impl(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
+                                 int64_t n_isects, const int32_t* offsets, float* render, float* alphas, int32_t* last_ids,
+                                 const void* ws, size_t ws_bytes, void* stream, const RasterOpts& o)
 {
     const int rc = raster_check("gs_raster_composite", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
     if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
     const RasterWs r = carve((void*)ws, n_isects, V, tiles);
-#define GS_FWD(CD) return launch_fwd<CD>(W, H, D, r, colors, background, n_isects, offsets, render, alphas, last_ids, s)
+#define GS_FWD(CD) return launch_fwd<CD>(W, H, D, r, colors, background, n_isects, offsets, render, alphas, last_ids, s, o)
     if (D <= 3) GS_FWD(3);
     if (D <= 4) GS_FWD(4);
     if (D <= 8) GS_FWD(8);
@@ -1824,34 +1737,23 @@ extern "C" int gs_raster_composite(int W, int H, int tile_size, int D, int V, co
 #undef GS_FWD
 }
 
-extern "C" int gs_raster_fwd(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
-                             const float* opacities, const float* colors, const float* background,
-                             int64_t n_isects, const int32_t* offsets, const int32_t* flatten_ids,
-                             float* render, float* alphas, int32_t* last_ids, void* ws, size_t ws_bytes, void* stream)
-{
-    const int rc = gs_raster_prepare(W, H, tile_size, D, V, means2d, conics, opacities, colors, n_isects, offsets, flatten_ids,
-                                     ws, ws_bytes, stream);
-    if (rc != GS_OK) return rc;
-    return gs_raster_composite(W, H, tile_size, D, V, colors, background, n_isects, offsets, render, alphas, last_ids, ws,
-                               ws_bytes, stream);
-}
-
 template <int CD>
 static int launch_bwd(int W, int H, int D, const RasterWs& ws, const float* colors, const float* background,
                       int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
-                      const float* v_render, const float* v_alphas, float* v_packed, int rec_stride, hipStream_t s)
+                      const float* v_render, const float* v_alphas, float* v_packed, int rec_stride, hipStream_t s,
+                      const RasterOpts& o)
 {
     const int tile_w = (W + GS_TILE - 1) / GS_TILE, tile_h = (H + GS_TILE - 1) / GS_TILE;
-    if (t_tone_bwd.v_image && !(CD == 3 && D == 3 && background == nullptr)) {
+    if (o.tone_bwd.v_image && !(CD == 3 && D == 3 && background == nullptr)) {
         gs_set_error("gs_raster_bwd_tone: needs D == 3 and no background");
         return GS_EINVAL;
     }
     if constexpr (CD <= 3) {                                  // colours travel in the record stream only for D <= 3
-        if (t_cull_log.idx) {                                   // the forward left its cull log: no fill, no masks
+        if (o.log.idx) {                                      // the forward left its cull log: no fill, no masks
             const size_t lds = gs_raster_lds(4 * (size_t)LogLds::WAVE_BYTES);
             hipLaunchKernelGGL(raster_bwd_log_kernel<CD>, dim3(tile_w * tile_h), dim3(256), lds, s, W, H, tile_w, tile_w * tile_h, D,
-                               ws.order, ws.rec0, ws.rec1, ws.rec2, background, isect_count(n_isects), offsets, alphas, last_ids,
-                               v_render, v_alphas, v_packed, rec_stride, t_tone_bwd, t_cull_log, ws.bo);
+                               ws.order, ws.rec0, ws.rec1, ws.rec2, background, isect_count(n_isects, o), offsets, alphas, last_ids,
+                               v_render, v_alphas, v_packed, rec_stride, o.tone_bwd, o.log, ws.bo);
             GS_CHECK_LAUNCH();
             return GS_OK;
         }
@@ -1862,8 +1764,8 @@ static int launch_bwd(int W, int H, int D, const RasterWs& ws, const float* colo
         if (lds > 64 * 1024)                           // > 64 KB of dynamic LDS needs the opt-in (per device: set on every such launch)
             GS_CHECK_HIP(hipFuncSetAttribute((const void*)raster_bwd_lanes2_kernel<CD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(raster_bwd_lanes2_kernel<CD>, dim3(tile_w * tile_h), dim3(256), lds, s, W, H, tile_w, tile_w * tile_h, D,
-                           ws.order, ws.rec0, ws.rec1, ws.rec2, colors, background, isect_count(n_isects), offsets, alphas, last_ids,
-                           v_render, v_alphas, v_packed, rec_stride, t_tone_bwd);
+                           ws.order, ws.rec0, ws.rec1, ws.rec2, colors, background, isect_count(n_isects, o), offsets, alphas, last_ids,
+                           v_render, v_alphas, v_packed, rec_stride, o.tone_bwd);
         GS_CHECK_LAUNCH();
         return GS_OK;
     }
@@ -1871,47 +1773,21 @@ static int launch_bwd(int W, int H, int D, const RasterWs& ws, const float* colo
 
 extern "C" int gs_raster_grad_stride(int D) { return ((6 + D) + 15) / 16 * 16; }
 
+// A6 on the workspace the forward wrote; zero: v_packed is cleared first (else the gradients are ADDED to it)
 static int raster_bwd_impl(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
                            int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
                            const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
-                           size_t ws_bytes, void* stream, bool zero);
-
-extern "C" int gs_raster_bwd(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
-                             int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
-                             const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
-                             size_t ws_bytes, void* stream)
+                           size_t ws_bytes, void* stream, bool zero, const RasterOpts& o)
 {
-    return raster_bwd_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas,
-                           v_packed, ws, ws_bytes, stream, true);
-}
-
-extern "C" int gs_raster_bwd_acc(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
-                                 int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
-                                 const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
-                                 size_t ws_bytes, void* stream)
-{
-    return raster_bwd_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas,
-                           v_packed, ws, ws_bytes, stream, false);
-}
-
-static int raster_bwd_impl(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
-                           int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
-                           const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
-                           size_t ws_bytes, void* stream, bool zero)
-{
-    GS_CHECK_ARG(W > 0 && H > 0 && V >= 0, "bad sizes");
-    GS_CHECK_ARG(tile_size == GS_TILE, "only tile_size=16 is built (rfstudio/model/gsplat.py:30)");
-    GS_CHECK_ARG(D >= 1 && D <= GS_MAX_CHANNELS, "1 <= D <= 32");
-    GS_CHECK_ARG(n_isects >= 0 && n_isects < (1ll << 31), "n_isects must fit int32");
-    GS_CHECK_ARG(ws != nullptr, "workspace (the stream written by gs_raster_fwd) must not be NULL");
-    if (ws_bytes < gs_raster_ws_bytes(n_isects, V, W, H, tile_size)) { gs_set_error("gs_raster_bwd: workspace too small"); return GS_ENOSPC; }
+    const int rc = raster_check("gs_raster_bwd", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
+    if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int rec_stride = gs_raster_grad_stride(D);
     if (V > 0 && zero) GS_CHECK_HIP(gs_zero_async(v_packed, sizeof(float) * (size_t)rec_stride * (size_t)V, s));
     if (n_isects == 0 || V == 0) return GS_OK;
     const int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
     const RasterWs r = carve((void*)ws, n_isects, V, tiles);
-#define GS_BWD(CD) return launch_bwd<CD>(W, H, D, r, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas, v_packed, rec_stride, s)
+#define GS_BWD(CD) return launch_bwd<CD>(W, H, D, r, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas, v_packed, rec_stride, s, o)
     if (D <= 3) GS_BWD(3);
     if (D <= 4) GS_BWD(4);
     if (D <= 8) GS_BWD(8);
@@ -1920,82 +1796,8 @@ static int raster_bwd_impl(int W, int H, int tile_size, int D, int V, const floa
 #undef GS_BWD
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Capacity-protocol variants (include/geosplat_hip.h): V_cap / n_isects_cap size the workspace and the grids, the actual counts
-// are read on the device from counts_dev = {V, I}; nothing here needs the host to know them.
-extern "C" int gs_raster_prepare_vis_cap(int W, int H, int tile_size, int D, int V_cap, const float* vis_records, int64_t n_isects_cap,
-                                         const int64_t* counts_dev, const int32_t* offsets, const int32_t* flatten_ids, void* ws,
-                                         size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
-    CountsScope sc(counts_dev);
-    return gs_raster_prepare_vis(W, H, tile_size, D, V_cap, vis_records, n_isects_cap, offsets, flatten_ids, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_raster_composite_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
-                                       int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, float* render,
-                                       float* alphas, int32_t* last_ids, const void* ws, size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
-    CountsScope sc(counts_dev);
-    return gs_raster_composite(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, render, alphas, last_ids, ws,
-                               ws_bytes, stream);
-}
-
-extern "C" int gs_raster_bwd_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
-                                 int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, const float* alphas,
-                                 const int32_t* last_ids, const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
-                                 size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
-    CountsScope sc(counts_dev);
-    return gs_raster_bwd(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, alphas, last_ids, v_render, v_alphas,
-                         v_packed, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_raster_bwd_acc_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
-                                     int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, const float* alphas,
-                                     const int32_t* last_ids, const float* v_render, const float* v_alphas, float* v_packed,
-                                     const void* ws, size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
-    CountsScope sc(counts_dev);
-    return gs_raster_bwd_acc(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, alphas, last_ids, v_render, v_alphas,
-                             v_packed, ws, ws_bytes, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Compositor with S4 inside (see ToneFwd / ToneBwd).  The plain outputs (render, alphas, last_ids) are written as well: the backward
-// needs them.  n_isects / V are exact counts, or capacities when counts_dev != NULL (capacity protocol, as the *_cap entry points).
-extern "C" int gs_raster_composite_tone(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
-                                        const int64_t* counts_dev, const int32_t* offsets, float* render, float* alphas,
-                                        int32_t* last_ids, int tone_mode, const float* exposure, float* image, const void* ws,
-                                        size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && image != nullptr, "bad tone mode / exposure / image");
-    CountsScope sc(counts_dev);
-    ToneFwdScope ts(ToneFwd{ tone_mode, exposure, (float4*)image });
-    return gs_raster_composite(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, render, alphas, last_ids, ws, ws_bytes, stream);
-}
-
-// v_packed is ACCUMULATED into (as gs_raster_bwd_acc), v_exposure too (one atomic per quadrant wave).
-extern "C" int gs_raster_bwd_tone_acc(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
-                                      const int64_t* counts_dev, const int32_t* offsets, const float* render, const float* alphas,
-                                      const int32_t* last_ids, int tone_mode, const float* exposure, const float* v_image,
-                                      float* v_packed, float* v_exposure, const void* ws, size_t ws_bytes, void* stream)
-{
-    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && v_image != nullptr && render != nullptr && v_exposure != nullptr,
-                 "bad tone mode / exposure / v_image / render / v_exposure");
-    CountsScope sc(counts_dev);
-    ToneBwdScope ts(ToneBwd{ tone_mode, exposure, render, (const float4*)v_image, v_exposure });
-    return gs_raster_bwd_acc(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, alphas, last_ids, nullptr, nullptr, v_packed, ws,
-                             ws_bytes, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// self-test hook: counts the floats with bit patterns in [lo_bits, hi_bits] for which gs_rcp_exact2 differs from IEEE division
 // ---- cull log (forward -> backward), see struct CullLog -----------------------------------------------------------------------
-static CullLog carve_log(void* log_ws, int64_t n_isects)
+static CullLog carve_log(const void* log_ws, int64_t n_isects)
 {
     const size_t n = n_isects > 0 ? (size_t)n_isects : 1;
     char* p = (char*)log_ws;
@@ -2013,6 +1815,145 @@ extern "C" size_t gs_raster_log_ws_bytes(int64_t n_isects, int W, int H, int til
     return align256(4 * n * sizeof(unsigned long long)) + align256(4 * n * sizeof(int32_t)) + align256(4 * tiles * sizeof(int32_t));
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Entry points (include/geosplat_hip.h): each checks its own arguments, says what the launch takes in a RasterOpts and calls
+// one of the three impls above.
+extern "C" int gs_raster_prepare(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
+                                 const float* opacities, const float* colors, int64_t n_isects, const int32_t* offsets,
+                                 const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream)
+{
+    return raster_prepare_impl(W, H, tile_size, D, V, means2d, conics, opacities, colors, nullptr, n_isects, offsets, flatten_ids,
+                               ws, ws_bytes, stream, RasterOpts{});
+}
+
+extern "C" int gs_raster_prepare_vis(int W, int H, int tile_size, int D, int V, const float* vis_records, int64_t n_isects,
+                                     const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(vis_records != nullptr || V == 0, "vis_records (written by gs_project_fwd_vis) must not be NULL");
+    return raster_prepare_impl(W, H, tile_size, D, V, nullptr, nullptr, nullptr, nullptr, vis_records, n_isects, offsets,
+                               flatten_ids, ws, ws_bytes, stream, RasterOpts{});
+}
+
+extern "C" int gs_raster_composite(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
+                                   int64_t n_isects, const int32_t* offsets, float* render, float* alphas,
+                                   int32_t* last_ids, const void* ws, size_t ws_bytes, void* stream)
+{
+    return raster_composite_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, render, alphas, last_ids, ws,
+                                 ws_bytes, stream, RasterOpts{});
+}
+
+extern "C" int gs_raster_fwd(int W, int H, int tile_size, int D, int V, const float* means2d, const float* conics,
+                             const float* opacities, const float* colors, const float* background,
+                             int64_t n_isects, const int32_t* offsets, const int32_t* flatten_ids,
+                             float* render, float* alphas, int32_t* last_ids, void* ws, size_t ws_bytes, void* stream)
+{
+    const int rc = raster_prepare_impl(W, H, tile_size, D, V, means2d, conics, opacities, colors, nullptr, n_isects, offsets,
+                                       flatten_ids, ws, ws_bytes, stream, RasterOpts{});
+    if (rc != GS_OK) return rc;
+    return raster_composite_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, render, alphas, last_ids, ws,
+                                 ws_bytes, stream, RasterOpts{});
+}
+
+extern "C" int gs_raster_bwd(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
+                             int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
+                             const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
+                             size_t ws_bytes, void* stream)
+{
+    return raster_bwd_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas,
+                           v_packed, ws, ws_bytes, stream, true, RasterOpts{});
+}
+
+extern "C" int gs_raster_bwd_acc(int W, int H, int tile_size, int D, int V, const float* colors, const float* background,
+                                 int64_t n_isects, const int32_t* offsets, const float* alphas, const int32_t* last_ids,
+                                 const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
+                                 size_t ws_bytes, void* stream)
+{
+    return raster_bwd_impl(W, H, tile_size, D, V, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas,
+                           v_packed, ws, ws_bytes, stream, false, RasterOpts{});
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Capacity-protocol variants (include/geosplat_hip.h): V_cap / n_isects_cap size the workspace and the grids, the actual counts
+// are read on the device from counts_dev = {V, I}; nothing here needs the host to know them.
+extern "C" int gs_raster_prepare_vis_cap(int W, int H, int tile_size, int D, int V_cap, const float* vis_records, int64_t n_isects_cap,
+                                         const int64_t* counts_dev, const int32_t* offsets, const int32_t* flatten_ids, void* ws,
+                                         size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
+    GS_CHECK_ARG(vis_records != nullptr || V_cap == 0, "vis_records (written by gs_project_fwd_vis) must not be NULL");
+    RasterOpts o;
+    o.counts = counts_dev;
+    return raster_prepare_impl(W, H, tile_size, D, V_cap, nullptr, nullptr, nullptr, nullptr, vis_records, n_isects_cap, offsets,
+                               flatten_ids, ws, ws_bytes, stream, o);
+}
+
+extern "C" int gs_raster_composite_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
+                                       int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, float* render,
+                                       float* alphas, int32_t* last_ids, const void* ws, size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
+    RasterOpts o;
+    o.counts = counts_dev;
+    return raster_composite_impl(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, render, alphas, last_ids, ws,
+                                 ws_bytes, stream, o);
+}
+
+extern "C" int gs_raster_bwd_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
+                                 int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, const float* alphas,
+                                 const int32_t* last_ids, const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
+                                 size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
+    RasterOpts o;
+    o.counts = counts_dev;
+    return raster_bwd_impl(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, alphas, last_ids, v_render, v_alphas,
+                           v_packed, ws, ws_bytes, stream, true, o);
+}
+
+extern "C" int gs_raster_bwd_acc_cap(int W, int H, int tile_size, int D, int V_cap, const float* colors, const float* background,
+                                     int64_t n_isects_cap, const int64_t* counts_dev, const int32_t* offsets, const float* alphas,
+                                     const int32_t* last_ids, const float* v_render, const float* v_alphas, float* v_packed,
+                                     const void* ws, size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev must not be NULL");
+    RasterOpts o;
+    o.counts = counts_dev;
+    return raster_bwd_impl(W, H, tile_size, D, V_cap, colors, background, n_isects_cap, offsets, alphas, last_ids, v_render, v_alphas,
+                           v_packed, ws, ws_bytes, stream, false, o);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Compositor with S4 inside (see ToneFwd / ToneBwd).  The plain outputs (render, alphas, last_ids) are written as well: the backward
+// needs them.  n_isects / V are exact counts, or capacities when counts_dev != NULL (capacity protocol, as the *_cap entry points).
+// The *_log variants also hand the forward's cull log to the backward (log_ws, gs_raster_log_ws_bytes).
+extern "C" int gs_raster_composite_tone(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
+                                        const int64_t* counts_dev, const int32_t* offsets, float* render, float* alphas,
+                                        int32_t* last_ids, int tone_mode, const float* exposure, float* image, const void* ws,
+                                        size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && image != nullptr, "bad tone mode / exposure / image");
+    RasterOpts o;
+    o.counts = counts_dev;
+    o.tone_fwd = ToneFwd{ tone_mode, exposure, (float4*)image };
+    return raster_composite_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, render, alphas, last_ids, ws, ws_bytes,
+                                 stream, o);
+}
+
+// v_packed is ACCUMULATED into (as gs_raster_bwd_acc), v_exposure too (one atomic per quadrant wave).
+extern "C" int gs_raster_bwd_tone_acc(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
+                                      const int64_t* counts_dev, const int32_t* offsets, const float* render, const float* alphas,
+                                      const int32_t* last_ids, int tone_mode, const float* exposure, const float* v_image,
+                                      float* v_packed, float* v_exposure, const void* ws, size_t ws_bytes, void* stream)
+{
+    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && v_image != nullptr && render != nullptr && v_exposure != nullptr,
+                 "bad tone mode / exposure / v_image / render / v_exposure");
+    RasterOpts o;
+    o.counts = counts_dev;
+    o.tone_bwd = ToneBwd{ tone_mode, exposure, render, (const float4*)v_image, v_exposure };
+    return raster_bwd_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, alphas, last_ids, nullptr, nullptr, v_packed, ws,
+                           ws_bytes, stream, false, o);
+}
+
 extern "C" int gs_raster_composite_tone_log(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
                                             const int64_t* counts_dev, const int32_t* offsets, float* render, float* alphas,
                                             int32_t* last_ids, int tone_mode, const float* exposure, float* image, const void* ws,
@@ -2020,9 +1961,13 @@ extern "C" int gs_raster_composite_tone_log(int W, int H, int tile_size, int V, 
 {
     GS_CHECK_ARG(log_ws != nullptr && tile_size == GS_TILE, "log_ws must not be NULL");
     if (log_bytes < gs_raster_log_ws_bytes(n_isects, W, H, tile_size)) { gs_set_error("gs_raster_composite_tone_log: log workspace too small"); return GS_ENOSPC; }
-    CullLogScope ls(carve_log(log_ws, n_isects));
-    return gs_raster_composite_tone(W, H, tile_size, V, colors, n_isects, counts_dev, offsets, render, alphas, last_ids, tone_mode, exposure,
-                                    image, ws, ws_bytes, stream);
+    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && image != nullptr, "bad tone mode / exposure / image");
+    RasterOpts o;
+    o.counts = counts_dev;
+    o.tone_fwd = ToneFwd{ tone_mode, exposure, (float4*)image };
+    o.log = carve_log(log_ws, n_isects);
+    return raster_composite_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, render, alphas, last_ids, ws, ws_bytes,
+                                 stream, o);
 }
 
 extern "C" int gs_raster_bwd_tone_log_acc(int W, int H, int tile_size, int V, const float* colors, int64_t n_isects,
@@ -2033,10 +1978,18 @@ extern "C" int gs_raster_bwd_tone_log_acc(int W, int H, int tile_size, int V, co
 {
     GS_CHECK_ARG(log_ws != nullptr && tile_size == GS_TILE, "log_ws must not be NULL");
     if (log_bytes < gs_raster_log_ws_bytes(n_isects, W, H, tile_size)) { gs_set_error("gs_raster_bwd_tone_log_acc: log workspace too small"); return GS_ENOSPC; }
-    CullLogScope ls(carve_log((void*)log_ws, n_isects));
-    return gs_raster_bwd_tone_acc(W, H, tile_size, V, colors, n_isects, counts_dev, offsets, render, alphas, last_ids, tone_mode, exposure,
-                                  v_image, v_packed, v_exposure, ws, ws_bytes, stream);
+    GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && v_image != nullptr && render != nullptr && v_exposure != nullptr,
+                 "bad tone mode / exposure / v_image / render / v_exposure");
+    RasterOpts o;
+    o.counts = counts_dev;
+    o.tone_bwd = ToneBwd{ tone_mode, exposure, render, (const float4*)v_image, v_exposure };
+    o.log = carve_log(log_ws, n_isects);
+    return raster_bwd_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, alphas, last_ids, nullptr, nullptr, v_packed, ws,
+                           ws_bytes, stream, false, o);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// self-test hook: counts the floats with bit patterns in [lo_bits, hi_bits] for which gs_rcp_exact2 differs from IEEE division
 
 __global__ void __launch_bounds__(256) selftest_rcp_kernel(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches)
 {

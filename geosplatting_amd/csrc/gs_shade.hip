@@ -67,7 +67,7 @@ shade_bwd_kernel(int N, const float* __restrict__ means, const float* __restrict
     // wave-private commit staging behind the private texel copies (640 floats per wave, see wave_commit6_lds); -1 = permute form
     float* const stage = eg.stage_off >= 0 ? s_grad + eg.stage_off + (threadIdx.x >> 6) * 640 : nullptr;
     const float cp[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
-    // wave-uniform trip count: every lane of a wave reaches the wave-aggregated scatter together
+    // wave-uniform trip count: every lane of a wave reaches the wave-wide scatter together
     const int n_iter = (N + (int)(gridDim.x * blockDim.x) - 1) / (int)(gridDim.x * blockDim.x);
     for (int it = 0; it < n_iter; ++it) {
         const int n = it * (int)(gridDim.x * blockDim.x) + blockIdx.x * blockDim.x + threadIdx.x;
@@ -164,7 +164,7 @@ shade_bwd_kernel(int N, const float* __restrict__ means, const float* __restrict
 
         }   // non-zero upstream gradient
         }   // live
-        // ---- texel gradients: LDS-private copies for the small levels, wave-aggregated atomics for the rest
+        // ---- texel gradients: LDS-private copies for the small levels, row-pair atomics (cube_scatter_wave) for the rest
         if (mode != GS_MODE_DIFFUSE) {
             const int l0 = scatter ? t.ls.l0 : 0, l1 = scatter ? t.ls.l1 : -1;
             const float w0 = (l1 < 0) ? 1.0f : 1.0f - t.ls.f;

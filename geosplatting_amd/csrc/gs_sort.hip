@@ -26,9 +26,8 @@
 
 #define RS_THREADS 256
 #define RS_WAVES 4
-#ifndef RS_ITEMS
 #define RS_ITEMS 8                        // per thread.  16 until the end of round 4: alone the passes take the same time, inside the
-#endif                                    // step the 22 KB blocks find room beside the compositor's (39 KB blocks did not): 659 -> 669
+                                          // step the 22 KB blocks find room beside the compositor's (39 KB blocks did not): 659 -> 669
                                           // views/s (4: 664, 12: 662)
 #define RS_TILE (RS_THREADS * RS_ITEMS)   // 2048 items per block
 #define RS_WCHUNK (64 * RS_ITEMS)         // 512 items per wave
@@ -311,10 +310,8 @@ __device__ __forceinline__ void tile_range_sorted(float mx, float my, int radius
 }
 
 #define EM_THREADS 256
-#ifndef EM_PER
-#define EM_PER 4
+#define EM_PER 4                             // ranks per thread (2 and 8 measured: DESIGN.md section 6)
 #define EM_LOOK 4                            // x 64 predecessors per look-back round
-#endif
 #define EM_TILE (EM_THREADS * EM_PER)        // ranks per block
 
 // tile rectangle of every visible Gaussian, packed (x0 | y0 << 16, x1 | y1 << 16): computed once in packed order (coalesced) so

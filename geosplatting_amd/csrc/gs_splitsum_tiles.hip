@@ -31,9 +31,6 @@
 
 typedef float gs_f2 __attribute__((ext_vector_type(2)));
 typedef float gs_f4 __attribute__((ext_vector_type(4)));
-#ifndef GS_TILE_DEPTH
-#define GS_TILE_DEPTH 4             // register sets of 8 rows in flight per wave (8: measured slower)
-#endif
 #define GS_TILE_ROW_PAD 8          // rows of a (block, face) list are padded to a multiple of this (zero weights): no tail branches
 
 // texel index of the image of (s, x, y) under the reflection m (bit k of m = flip world axis k).  Face (x, y) -> direction:
@@ -334,12 +331,8 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
                     const int xc = min(max(x, 0), R - 1), yc = min(max(y, 0), R - 1);
                     const int xm = mm.fx ? R - 1 - xc : xc, ym = mm.fy ? R - 1 - yc : yc;
                     const int idx = (face_base + ym) * R + xm;
-#ifdef GS_TILE_EXP_NOSTAGE
-                    p[u] = F3{ (float)idx, 1.0f, 2.0f }; a[u] = 1.0f;
-#else
                     p[u] = *reinterpret_cast<const F3*>(src + (size_t)idx * 3);
                     a[u] = scale[idx];
-#endif
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -361,14 +354,14 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
             const int a_l = bx.any ? ((bx.ymin - sg.y) * pitch + (bx.xmin - sg.x)) : 0;
             const int64_t r0 = row_begin[slot];
             const int4* dp = reinterpret_cast<const int4*>(desc + r0);
-            // EIGHT register sets of 8 rows each, used round-robin: the loads of chunk j + 7 are issued before chunk j is consumed and
-            // nothing is copied between the sets, so the wait in front of a chunk covers ITS loads only; seven younger chunks (56 rows,
-            // 14 KB per wave) stay in flight.  That depth is what the kernel lives on: every weight line is fetched from HBM by
-            // whichever of the eight mirror workgroups asks first and the other seven wait for the same fill, loads return in order,
-            // so EVERY chunk sees the full HBM latency (~2 us under load) -- with three chunks in flight a wave advanced one chunk
-            // per ~1500 cycles.  Weights are stored in row PAIRS ([row / 2][lane][2]): one 8-byte load per lane lands in an aligned
-            // register pair whose halves feed the packed FMAs directly.  A chunk index past the end is clamped to the last chunk
-            // (loaded again, not consumed): no branch around a load.  The row descriptors (scalar loads) run two chunks ahead.
+            // FOUR register sets of 8 rows each, used round-robin: the loads of chunk j + 3 are issued before chunk j is consumed and
+            // nothing is copied between the sets, so the wait in front of a chunk covers ITS loads only; three younger chunks (24 rows,
+            // 6 KB per wave) stay in flight.  Every weight line is fetched from HBM by whichever of the eight mirror workgroups asks
+            // first and the other seven wait for the same fill, loads return in order, so EVERY chunk sees the full HBM latency
+            // (~2 us under load).  Eight sets were measured slower (0.76 against 0.65 ms, profiles/r06_prefilter_removal.txt).
+            // Weights are stored in row PAIRS ([row / 2][lane][2]): one 8-byte load per lane lands in an aligned register pair whose
+            // halves feed the packed FMAs directly.  A chunk index past the end is clamped to the last chunk (loaded again, not
+            // consumed): no branch around a load.  The row descriptors (scalar loads) run four chunks ahead.
             const char* lds_b = reinterpret_cast<const char*>(s_src) + a_l * 16;
             // weight rows: UNIFORM base pointer (an SGPR pair, advanced with scalar adds) + the lane's 32-bit byte offset + an immediate
             // per row pair -- `global_load_dwordx2 v, v_lane8, s[base] offset:512 u` -- instead of four 64-bit vector additions per chunk
@@ -378,18 +371,8 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
             //  the LDS reads, so every chunk starts behind `s_waitcnt lgkmcnt(0)` -- 0.93 + 0.95 ms against 0.78 + 0.80: two more
             //  vector loads per chunk in a loop whose bound is the return order of its vector loads.  The scalar-base form of the
             //  weight loads above removes 25 of 35 64-bit vector additions and 60 scalar instructions: no change either.)
-#ifdef GS_TILE_EXP_NOW
-#define GS_TILE_WLOAD(P) (gs_f2{ 1.0f, (float)kk })
-#elif defined(GS_TILE_WLOAD_SC1)
-#define GS_TILE_WLOAD(P) (__builtin_bit_cast(gs_f2, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(P), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
-#else
 #define GS_TILE_WLOAD(P) (SHARED_ROWS ? *(P) : __builtin_nontemporal_load(P))
-#endif
-#ifdef GS_TILE_EXP_NODESC
-#define GS_TILE_DLOAD(D0, D1, KK) do { D0 = make_int4((KK) * 16, (KK) * 16 + 16, (KK) * 16 + 32, (KK) * 16 + 48); D1 = make_int4((KK) * 16 + 64, (KK) * 16 + 80, (KK) * 16 + 96, (KK) * 16 + 112); } while (0)
-#else
 #define GS_TILE_DLOAD(D0, D1, KK) do { D0 = dp[(KK) >> 2]; D1 = dp[((KK) >> 2) + 1]; } while (0)
-#endif
 #define GS_CHUNK_ROW(J) ((min((J), nj - 1) * K + part) * 8)
 #define GS_ROWS_LOAD(W, J)                                                                                          \
             do {                                                                                                    \
@@ -412,11 +395,7 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
             } while (0)
 #define GS_SEL_LO "op_sel_hi:[0,1,1]"
 #define GS_SEL_HI "op_sel:[1,0,0] op_sel_hi:[1,1,1]"
-#ifdef GS_TILE_EXP_NOLDS
-#define GS_LDS4(OFF) (gs_f4{ (float)(OFF), 1.0f, 2.0f, 3.0f })
-#else
 #define GS_LDS4(OFF) (*reinterpret_cast<const gs_f4*>(lds_b + (OFF)))
-#endif
 #define GS_ROWS_USE(W, D0, D1)                                                                                      \
             do {                                                                                                    \
                 const gs_f4 t0 = GS_LDS4(D0.x), t1 = GS_LDS4(D0.y), t2 = GS_LDS4(D0.z), t3 = GS_LDS4(D0.w),         \
@@ -427,77 +406,19 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
                 GS_ROW_FMA(W[3], t6, GS_SEL_LO); GS_ROW_FMA(W[3], t7, GS_SEL_HI);                                   \
             } while (0)
             // one step of the rotation: prefetch into the set that was consumed last, consume set WC with descriptor set (DA, DB),
-            // then refill that descriptor set for two chunks later
-#ifndef GS_DESC_AHEAD
-#define GS_DESC_AHEAD 4                      // descriptor sets in flight (scalar loads): 2 until round 6
-#endif
+            // then refill that descriptor set for four chunks later
 #define GS_STEP(WP, JP, WC, JC, DA, DB)                                                                             \
             do {                                                                                                    \
                 GS_ROWS_LOAD(WP, JP);                                                                               \
                 if ((JC) < nj) GS_ROWS_USE(WC, DA, DB);                                                             \
-                GS_DESC_LOAD(DA, DB, (JC) + GS_DESC_AHEAD);                                                         \
+                GS_DESC_LOAD(DA, DB, (JC) + 4);                                                                     \
             } while (0)
-#if GS_TILE_DEPTH == 8
-            gs_f2 w0[4], w1[4], w2[4], w3[4], w4[4], w5[4], w6[4], w7[4];
-            GS_ROWS_LOAD(w0, 0); GS_ROWS_LOAD(w1, 1); GS_ROWS_LOAD(w2, 2); GS_ROWS_LOAD(w3, 3);
-            GS_ROWS_LOAD(w4, 4); GS_ROWS_LOAD(w5, 5); GS_ROWS_LOAD(w6, 6);
-#if GS_DESC_AHEAD == 2
-            int4 a0, a1, b0, b1;
-            GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1);
-            for (int j = 0; j < nj; j += 8) {
-                GS_STEP(w7, j + 7, w0, j + 0, a0, a1);
-                GS_STEP(w0, j + 8, w1, j + 1, b0, b1);
-                GS_STEP(w1, j + 9, w2, j + 2, a0, a1);
-                GS_STEP(w2, j + 10, w3, j + 3, b0, b1);
-                GS_STEP(w3, j + 11, w4, j + 4, a0, a1);
-                GS_STEP(w4, j + 12, w5, j + 5, b0, b1);
-                GS_STEP(w5, j + 13, w6, j + 6, a0, a1);
-                GS_STEP(w6, j + 14, w7, j + 7, b0, b1);
-            }
-#elif GS_DESC_AHEAD == 4
-            // The row descriptors are SCALAR loads of 32 bytes per chunk from a list that every wave walks once: every second chunk
-            // misses the scalar cache, and with two sets in flight the miss (an L2 round trip) was exposed in front of most chunks --
-            // with the weight loads compiled out the kernel still took 70 % of its time (profiles/r06_prefilter_removal.txt).
-            int4 a0, a1, b0, b1, c0, c1, d0, d1;
-            GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1); GS_DESC_LOAD(c0, c1, 2); GS_DESC_LOAD(d0, d1, 3);
-            for (int j = 0; j < nj; j += 8) {
-                GS_STEP(w7, j + 7, w0, j + 0, a0, a1);
-                GS_STEP(w0, j + 8, w1, j + 1, b0, b1);
-                GS_STEP(w1, j + 9, w2, j + 2, c0, c1);
-                GS_STEP(w2, j + 10, w3, j + 3, d0, d1);
-                GS_STEP(w3, j + 11, w4, j + 4, a0, a1);
-                GS_STEP(w4, j + 12, w5, j + 5, b0, b1);
-                GS_STEP(w5, j + 13, w6, j + 6, c0, c1);
-                GS_STEP(w6, j + 14, w7, j + 7, d0, d1);
-            }
-#else
-            int4 a0, a1, b0, b1, c0, c1, d0, d1, e0, e1, f0, f1, g0, g1, h0, h1;
-            GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1); GS_DESC_LOAD(c0, c1, 2); GS_DESC_LOAD(d0, d1, 3);
-            GS_DESC_LOAD(e0, e1, 4); GS_DESC_LOAD(f0, f1, 5); GS_DESC_LOAD(g0, g1, 6); GS_DESC_LOAD(h0, h1, 7);
-            for (int j = 0; j < nj; j += 8) {
-                GS_STEP(w7, j + 7, w0, j + 0, a0, a1);
-                GS_STEP(w0, j + 8, w1, j + 1, b0, b1);
-                GS_STEP(w1, j + 9, w2, j + 2, c0, c1);
-                GS_STEP(w2, j + 10, w3, j + 3, d0, d1);
-                GS_STEP(w3, j + 11, w4, j + 4, e0, e1);
-                GS_STEP(w4, j + 12, w5, j + 5, f0, f1);
-                GS_STEP(w5, j + 13, w6, j + 6, g0, g1);
-                GS_STEP(w6, j + 14, w7, j + 7, h0, h1);
-            }
-#endif
-#else
+            // FOUR descriptor sets in flight (two until round 6).  The row descriptors are SCALAR loads of 32 bytes per chunk from a
+            // list that every wave walks once: every second chunk misses the scalar cache, and with two sets in flight the miss (an L2
+            // round trip) was exposed in front of most chunks -- with the weight loads compiled out the kernel still took 70 % of its
+            // time.  Four sets: -7 %; eight cost occupancy (106 SGPRs) and were slower (profiles/r06_prefilter_removal.txt).
             gs_f2 w0[4], w1[4], w2[4], w3[4];
             GS_ROWS_LOAD(w0, 0); GS_ROWS_LOAD(w1, 1); GS_ROWS_LOAD(w2, 2);
-#if GS_DESC_AHEAD == 2
-            int4 a0, a1, b0, b1;
-            GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1);
-            for (int j = 0; j < nj; j += 4) {
-                GS_STEP(w3, j + 3, w0, j + 0, a0, a1);
-                GS_STEP(w0, j + 4, w1, j + 1, b0, b1);
-                GS_STEP(w1, j + 5, w2, j + 2, a0, a1);
-                GS_STEP(w2, j + 6, w3, j + 3, b0, b1);
-            }
-#elif GS_DESC_AHEAD == 4
             int4 a0, a1, b0, b1, c0, c1, d0, d1;
             GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1); GS_DESC_LOAD(c0, c1, 2); GS_DESC_LOAD(d0, d1, 3);
             for (int j = 0; j < nj; j += 4) {
@@ -506,22 +427,6 @@ tile_apply_body(int wg /*workgroup of this level's launch*/, int R, int E, int b
                 GS_STEP(w1, j + 5, w2, j + 2, c0, c1);
                 GS_STEP(w2, j + 6, w3, j + 3, d0, d1);
             }
-#else
-            int4 a0, a1, b0, b1, c0, c1, d0, d1, e0, e1, f0, f1, g0, g1, h0, h1;
-            GS_DESC_LOAD(a0, a1, 0); GS_DESC_LOAD(b0, b1, 1); GS_DESC_LOAD(c0, c1, 2); GS_DESC_LOAD(d0, d1, 3);
-            GS_DESC_LOAD(e0, e1, 4); GS_DESC_LOAD(f0, f1, 5); GS_DESC_LOAD(g0, g1, 6); GS_DESC_LOAD(h0, h1, 7);
-            for (int j = 0; j < nj; j += 8) {
-                GS_STEP(w3, j + 3, w0, j + 0, a0, a1);
-                GS_STEP(w0, j + 4, w1, j + 1, b0, b1);
-                GS_STEP(w1, j + 5, w2, j + 2, c0, c1);
-                GS_STEP(w2, j + 6, w3, j + 3, d0, d1);
-                GS_STEP(w3, j + 7, w0, j + 4, e0, e1);
-                GS_STEP(w0, j + 8, w1, j + 5, f0, f1);
-                GS_STEP(w1, j + 9, w2, j + 6, g0, g1);
-                GS_STEP(w2, j + 10, w3, j + 7, h0, h1);
-            }
-#endif
-#endif
 #undef GS_STEP
 #undef GS_DESC_LOAD
 #undef GS_CHUNK_ROW
