@@ -21,8 +21,6 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-import ctypes as C
-
 from . import _lib as L
 from .cameras import Camera
 from .parallel import GradBucket, collectives_active
@@ -101,7 +99,7 @@ class RenderStep:
         self.fused = fused
         self.bucket = GradBucket(params.shapes(), params.means.device)
         self._static_env: Optional[TextureSplitSum] = None
-        self._cam_cache: Dict[tuple, tuple] = {}
+        self._cameras = F.CameraCache(params.means.device)
         self._side_stream = None
         self._tail_stream = None
         # capacity protocol state (see _geometry / poll_capacity)
@@ -143,41 +141,14 @@ class RenderStep:
             self.bucket = GradBucket(params.shapes(), params.means.device, comm_stream=self.bucket.comm_stream)
 
     # ------------------------------------------------------------------------------------------------- fused path
-    def _camera_tensors(self, cam: Camera, stream: torch.cuda.Stream):
-        """Device copies of (view matrix, K, camera position) of a camera, cached per POSE TENSOR: the entry keeps a reference to
-        `cam.c2w` (so CPython cannot recycle its id while the entry lives) together with the tensor's version counter (an
-        in-place update of the pose bumps it) and the intrinsics -- a hit therefore costs no device-to-host copy and no
-        synchronisation, also for device-resident cameras and inside a graph capture; a training loop that builds new Camera
-        objects every step simply misses.  Bounded, oldest entry evicted.
-        A miss builds the tensors on `stream`, the front stream that reads them first, which must already be ordered behind the
-        caller's stream (a device-resident pose may have been written there); the other front stream waits for them (as
-        viewbatch.camera_tensors)."""
-        c2w = cam.c2w
-        key = id(c2w)
-        intr = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.width), int(cam.height))
-        # host-resident poses also carry a content fingerprint (48 bytes): an in-place change that does not bump the version counter
-        # (`cam.c2w.data.copy_()`, a numpy-backed tensor written through numpy) cannot return stale matrices.  Device-resident poses
-        # rely on the version counter alone (a fingerprint would be a device-to-host copy); invalidate_cameras() drops everything.
-        fp = c2w.detach().numpy().tobytes() if c2w.device.type == "cpu" else None
-        hit = self._cam_cache.get(key)
-        if hit is not None and hit[0] is c2w and hit[1] == c2w._version and hit[2] == intr and hit[4] == fp:
-            return hit[3]
-        dev = self.p.means.device
-        if len(self._cam_cache) >= 1024:
-            self._cam_cache.pop(next(iter(self._cam_cache)))
-        with torch.cuda.stream(stream):
-            tensors = (cam.view_matrix.to(dev, torch.float32).contiguous(), cam.intrinsic_matrix.to(dev, torch.float32).contiguous(),
-                       c2w.detach()[:, 3].to(dev, torch.float32).contiguous())
-            ev = torch.cuda.Event(); ev.record(stream)
-        for sd in self._side_stream:
-            if sd is not stream:
-                sd.wait_event(ev)
-        self._cam_cache[key] = (c2w, c2w._version, intr, tensors, fp)
-        return tensors
+    @property
+    def _cam_cache(self):
+        """The camera cache's entries as {key: (pose, version, intrinsics, tensors, fingerprint)} (tests read them)."""
+        return {k: (e[0], e[1], k[3], e[2], e[3]) for k, e in self._cameras.entries.items()}
 
     def invalidate_cameras(self) -> None:
         """Forget every cached (view matrix, K, position) triple: for callers that rewrite DEVICE-resident poses behind autograd's back."""
-        self._cam_cache.clear()
+        self._cameras.clear()
 
     def _activations(self, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
         """The once-per-step exp / sigmoid activations of the scales and opacities on the current stream (into `out` if given)."""
@@ -200,7 +171,7 @@ class RenderStep:
         if self._use_capacity and self._status is None:      # zero-filled on the main stream BEFORE the side streams fork from it
             self._status = torch.zeros(4, dtype=torch.int64, device=dev)
         if self._side_stream is None:
-            self._side_stream = [L.shared_stream(dev, "front0"), L.shared_stream(dev, "front1")]
+            self._side_stream = F.front_streams(dev)
         # tile rectangles clipped to the {alpha >= 1/255} extents (GEOSPLAT_TIGHT_TILES=0: gsplat's squares): 18 % fewer intersections
         # on the bench scene, identical pixels (gs_front_fwd; the engine never returns gsplat's `meta`)
         tight = os.environ.get("GEOSPLAT_TIGHT_TILES", "1") != "0"
@@ -215,7 +186,7 @@ class RenderStep:
             side = self._side_stream[0]
             ev_a = torch.cuda.Event(); ev_a.record(main)
             side.wait_event(ev_a)
-            cam_t = self._camera_tensors(cameras[0], side)      # (behind ev_a: a device-resident pose is final on the caller's stream)
+            cam_t = self._cameras.get(cameras[0], side)
             with torch.cuda.stream(side):
                 fr = self._front(geo, cameras[0], cam_t, None, records=False)
                 binned, _, _ = F.bin_stage(fr, i_cap, self._status, prepare=False)
@@ -244,7 +215,7 @@ class RenderStep:
         passes, emission: 0.25 ms per view) instead of behind it.  Returns the fronts by view index, for _views."""
         _, e = self._env_args(env)
         cur = torch.cuda.current_stream(self.p.means.device)
-        return {j: self._front(geo, cameras[j], self._camera_tensors(cameras[j], cur), e, binning=False) for j in sorted(geo.early)}
+        return {j: self._front(geo, cameras[j], self._cameras.get(cameras[j], cur), e, binning=False) for j in sorted(geo.early)}
 
     def _pyramid(self, sharded: bool, world: int) -> TextureSplitSum:
         """The pyramid of this step: the prefilter forward (sharded over the ranks: splitsum.py), or without the prefilter in the step
@@ -314,13 +285,7 @@ class RenderStep:
         # texel-gradient accumulators: one flat buffer behind the base + level gradients (the sharded prefilter sums them over the
         # ranks in ONE all-reduce).  (Two sets with the first half's prefilter backward under the remaining compositor work were
         # measured: the backward is linear, splitting it doubles it, the overlap does not pay that back.)
-        sizes = [env_d.base.numel()] + [l.numel() for l in env_d.levels]
-        g_flat = sc[2] if sizes == tex_sizes else torch.zeros(sum(sizes), dtype=f32, device=dev)
-        parts = torch.split(g_flat, sizes)
-        g_base = parts[0].view_as(env_d.base); g_levels = [q.view_as(l) for q, l in zip(parts[1:], env_d.levels)]
-        eg = L.GsEnvGrad(); eg.base = g_base.data_ptr()
-        for i, g in enumerate(g_levels):
-            eg.levels[i] = g.data_ptr()
+        g_flat, g_base, g_levels, eg = F.texel_grads(env_d, sc[2])
         self.last_texel_grads = (g_base, g_levels)           # d loss / d pyramid of this step (summed over the local views): tests read it
         images = []
         tail = self._tail_stream
@@ -333,8 +298,7 @@ class RenderStep:
         # the tails of the views in ONE call per batch of views (gs_tail_bwd_multi_parts: the views of a Gaussian on adjacent lanes, its
         # gradients stored once).  The launches that are not the last run as BACKGROUND launches (parts + 4: half of the CUs) beside the
         # compositor of the following views, and the last one, alone on the GPU, covers 2 views instead of 8 (_auto_tail_schedule).
-        tb = os.environ.get("GEOSPLAT_TAIL_BATCH", "auto")                                       # "auto" or a schedule "3,4,1" (last repeats)
-        tail_sched = _auto_tail_schedule(len(cameras)) if tb == "auto" else [max(1, int(x)) for x in tb.split(",")]
+        tail_sched = F.tail_schedule(_auto_tail_schedule(len(cameras)))
         pending_tails = []
         n_tail_launches = 0
         pstream = None
@@ -348,7 +312,7 @@ class RenderStep:
 
         def start_view(cam, j):                              # S1-S3 + A1; (V, I) travel to the host asynchronously
             side = sides[j % len(sides)]
-            cam_t = cam_ts[j] = self._camera_tensors(cam, side)     # (a miss: built on `side`, which has forked from the caller's stream)
+            cam_t = cam_ts[j] = self._cameras.get(cam, side)
             if recs is not None and j in recs:               # (capture_views: the records graph has run)
                 return recs[j], j, side
             with torch.cuda.stream(side):                    # (binned under the prefilter: only the records (shading) are still missing)
@@ -388,29 +352,15 @@ class RenderStep:
             kev = self.kernel_events
             if kev is not None:
                 k0 = torch.cuda.Event(enable_timing=True); k0.record(main)
-            # compositor with S4 in its epilogue (`img` comes out of the same launch); it leaves its cull log (stream index + pixel mask
-            # of every record that entered a dense batch) for the backward of this view, which then neither culls nor builds masks
-            render = torch.empty(H, W, 3, dtype=f32, device=dev); alphas = torch.empty(H, W, dtype=f32, device=dev)
-            last_ids = torch.empty(H, W, dtype=torch.int32, device=dev)
-            img = torch.empty(H, W, 4, dtype=f32, device=dev)
-            rws = s["raster_ws"]
-            counts = L.ptr(s["counts"]) if i_cap is not None else None
-            log_ws = torch.empty(lib.gs_raster_log_ws_bytes(L.i64(I), W, H, 16), dtype=torch.uint8, device=dev)
-            L.check(lib.gs_raster_composite_tone_log(W, H, 16, V, None, L.i64(I), counts, L.ptr(s["isect_offsets"]), L.ptr(render),
-                                                     L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(img), L.ptr(rws),
-                                                     C.c_size_t(rws.numel()), L.ptr(log_ws), C.c_size_t(log_ws.numel()), st()),
-                    "gs_raster_composite_tone_log")
+            log_ws = F.log_ws(I, W, H, dev)
+            img, render, alphas, last_ids = F.composite_fwd(s, V, I, W, H, tone, exposure, log_ws)
             if kev is not None:
                 k1 = torch.cuda.Event(enable_timing=True); k1.record(main)
                 kev.append(("raster_fwd_kernel", k0, k1))
             v_img = upstream(i, img).contiguous()
-            v_packed = s["v_packed"]
             if kev is not None:
                 k2 = torch.cuda.Event(enable_timing=True); k2.record(main)
-            L.check(lib.gs_raster_bwd_tone_log_acc(W, H, 16, V, None, L.i64(I), counts, L.ptr(s["isect_offsets"]), L.ptr(render),
-                                                   L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(v_img), L.ptr(v_packed),
-                                                   L.ptr(b["exposure"]), L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(log_ws),
-                                                   C.c_size_t(log_ws.numel()), st()), "gs_raster_bwd_tone_log_acc")
+            F.composite_bwd(s, V, I, W, H, tone, exposure, render, alphas, last_ids, log_ws, v_img, b["exposure"])
             if kev is not None:
                 k3 = torch.cuda.Event(enable_timing=True); k3.record(main)
                 kev.append(("raster_bwd_kernel", k2, k3))
@@ -420,42 +370,19 @@ class RenderStep:
                 proj.append(start_view(cameras[i + 2], i + 2))
             binned = bin_view(proj.pop(0)) if i + 1 < n_views else None
             # gradient tail (A7 + S1-S3 backward: HBM / atomic-rate bound) on the tail stream, beside the compositor of the next views
-            pending_tails.append((vm, K, cam_pos, s["vis_records"], v_packed, s["packed_index"], W, H))
+            pending_tails.append((vm, K, cam_pos, s["vis_records"], s["v_packed"], s["packed_index"], W, H))
             last = i == n_views - 1
             if len(pending_tails) == tail_sched[min(n_tail_launches, len(tail_sched) - 1)] or last:
-                ev_r = torch.cuda.Event(); ev_r.record(main)
-                targs = (pending_tails, means, quats, scales_act, opac_act, normals, kd, ks, e, eg, self.min_roughness, self.max_metallic,
-                         mode, b["means"], b["quats"], g_scales_act, g_opac_act, b["normals"], b["kd"], b["ks"])
+                targs = (means, quats, scales_act, opac_act, normals, kd, ks, e, eg, self.min_roughness, self.max_metallic, mode,
+                         b["means"], b["quats"], g_scales_act, g_opac_act, b["normals"], b["kd"], b["ks"])
                 if last and defer_tail:
-                    tail_job = dict(targs=targs, accumulate=n_tail_launches > 0, n_chunks=n_chunks)
-                    if keep_images:
-                        images.append(img)
-                    continue
-                tev = self.tail_events if last else None
-                with torch.cuda.stream(tail):
-                    tail.wait_event(ev_r)
-                    if tev is not None:
-                        t0 = torch.cuda.Event(enable_timing=True); t0.record(tail)
-                    # (the LAST launch: its projection half on a front stream -- idle by then -- beside the prefilter backward, which
-                    #  needs only the shading half's texel gradients)
-                    F.tail_multi_stage(*targs, accumulate=n_tail_launches > 0, parts=1 if last else 7)
-                used = [tail]
-                if last:
-                    ev_sh = torch.cuda.Event(enable_timing=tev is not None); ev_sh.record(tail)
-                    pstream = sides[0]
-                    with torch.cuda.stream(pstream):
-                        pstream.wait_event(ev_sh)              # (v_means: the projection half adds to what the shading half stored)
-                        F.tail_multi_stage(*targs, accumulate=n_tail_launches > 0, parts=2)
-                        if tev is not None:
-                            t2 = torch.cuda.Event(enable_timing=True); t2.record(pstream)
-                            tev.append((t0, ev_sh, t2))
-                    used.append(pstream)
-                n_tail_launches += 1
-                for tv in pending_tails:
-                    for t in tv[:6]:
-                        for u in used:
-                            t.record_stream(u)
-                pending_tails = []
+                    tail_job = dict(targs=(pending_tails,) + targs, accumulate=n_tail_launches > 0, n_chunks=n_chunks)
+                else:
+                    used = F.tail_batch(pending_tails, targs, n_tail_launches > 0, last, tail, sides[0], self.tail_events)
+                    if last:
+                        pstream = used[1]
+                    n_tail_launches += 1
+                    pending_tails = []
             if keep_images:
                 images.append(img)
         main.wait_stream(tail)
@@ -610,12 +537,13 @@ class RenderStep:
         def check() -> bool:
             torch.cuda.synchronize(dev)
             worst = max([int(hc[1]) for hc in counts] + [0])
-            overflow = int(status_host[0]) != 0 or int(status_host[3]) != 0 or worst > cap
+            truncated, key32, need_i = F.status_overflow(status_host)
+            overflow = truncated or worst > cap
             if overflow:
                 check.stale = True
                 self.truncated_steps += 1
-                self._key32 = self._key32 or int(status_host[3]) != 0
-                self._exact_max_i = max(self._exact_max_i, worst, int(status_host[1]))
+                self._key32 = self._key32 or key32
+                self._exact_max_i = max(self._exact_max_i, worst, need_i)
                 self._status.zero_(); status_host.zero_()
             return not overflow
         check.stale = False
@@ -750,6 +678,15 @@ class RenderStep:
                 time.sleep(5e-5)
             self._in_flight.popleft()
 
+    def _note_status(self, word: Tensor):
+        """A host copy of the status word of a finished step: a truncated step is counted in `truncated_steps`, and a depth outside
+        the 24-bit key range means 32-bit keys from now on.  Returns (truncated, the intersection count it required)."""
+        truncated, key32, need_i = F.status_overflow(word)
+        if truncated:
+            self.truncated_steps += 1
+            self._key32 = self._key32 or key32
+        return truncated, need_i
+
     def poll_capacity(self, wait: bool = False, _internal: bool = False) -> bool:
         """Host side of the capacity protocol; never blocks unless `wait`.  Looks at what the earlier steps left in pinned memory:
         the per-view (V, I) counts set / raise the intersection capacity (1.25 x the largest count seen, rounded up to 64 Ki),
@@ -779,25 +716,19 @@ class RenderStep:
             if not ev_s.query():
                 break
             self._status_pending.popleft()
-            if int(snap[0]) != 0 or int(snap[3]) != 0:
-                ok = False
-                self.truncated_steps += 1
-                max_i = max(max_i, int(snap[1]))
-                if int(snap[3]) != 0:                          # a depth outside the 24-bit key range: 32-bit keys from now on
-                    self._key32 = True
+            truncated, need_i = self._note_status(snap)
+            if truncated:
+                ok, max_i = False, max(max_i, need_i)
             self._status_pool.append(snap)
         if self._status_event is not None:                    # the single buffer of a captured step (see capture / capture_views)
             if wait:
                 self._status_event.synchronize()
-            if self._status_event.query() and (int(self._status_host[0]) != 0 or int(self._status_host[3]) != 0):
-                ok = False
-                self.truncated_steps += 1
-                max_i = max(max_i, int(self._status_host[1]))
-                if int(self._status_host[3]) != 0:
-                    self._key32 = True
-                self._status.zero_(); self._status_host.zero_()
             if self._status_event.query():
                 self._status_event = None
+                truncated, need_i = self._note_status(self._status_host)
+                if truncated:
+                    ok, max_i = False, max(max_i, need_i)
+                    self._status.zero_(); self._status_host.zero_()
         if self._use_capacity and max_i > 0:
             want = ((int(max_i * self._cap_margin) + 65535) // 65536) * 65536
             if self._i_cap is None or want > self._i_cap or max_i > self._i_cap:

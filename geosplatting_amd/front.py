@@ -10,6 +10,7 @@ one 64-byte record, a 4-byte depth key and an 8-byte tile rectangle -- nothing e
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import torch
@@ -197,3 +198,143 @@ def tail_multi_stage(views, means: Tensor, quats: Tensor, scales: Tensor, opacit
                                   stride, L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opacities), L.ptr(g_normals), L.ptr(g_kd),
                                   L.ptr(g_ks), 1 if accumulate else 0, C.byref(env_grad_struct), L.ptr(priv),
                                   C.c_size_t(0 if priv is None else priv.numel()), L.stream()), "gs_tail_bwd_multi_parts")
+
+
+# ------------------------------------------------------------------------------------------------------------ both drivers
+# engine.RenderStep and the call shape (viewbatch) run the same chain per view: front_stage -> bin_stage -> composite_fwd ->
+# composite_bwd -> tail_batch, and share what follows.
+def front_streams(dev: torch.device):
+    """The two front streams of a device (L.shared_stream): the fronts of consecutive views alternate between them."""
+    return [L.shared_stream(dev, "front0"), L.shared_stream(dev, "front1")]
+
+
+class CameraCache:
+    """Device (view matrix, K, position) of cameras, cached by the pose's STORAGE ADDRESS, shape, stride and the intrinsics, checked
+    against its version counter and, for a host-resident pose, its 48 bytes (a write that bypasses the version counter cannot return
+    stale matrices; a device-resident pose relies on the version counter alone, clear() drops everything).  The entry keeps the pose
+    alive, so its address cannot be recycled; `cameras[i]` of a resident dataset -- a new tensor object every step over the same
+    storage -- hits.  A hit costs no copy and no synchronisation, also inside a graph capture.  Bounded, oldest entry evicted."""
+    MAX_ENTRIES = 4096
+
+    def __init__(self, dev: torch.device):
+        self.dev = dev
+        self.entries = {}                                   # key -> (pose, version, tensors, fingerprint)
+
+    def get(self, cam, stream: torch.cuda.Stream):
+        """A miss builds the tensors on `stream`, the front stream that reads them first -- behind the caller's stream if the pose is
+        device-resident (it may still be in flight there) -- and every other front stream waits for them."""
+        c2w = cam.c2w
+        intr = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.width), int(cam.height))
+        host = c2w.device.type == "cpu"
+        fp = c2w.detach().numpy().tobytes() if host else None
+        key = (c2w.data_ptr(), tuple(c2w.shape), tuple(c2w.stride()), intr)
+        hit = self.entries.get(key)
+        if hit is not None and hit[1] == c2w._version and hit[3] == fp:
+            return hit[2]
+        if len(self.entries) >= self.MAX_ENTRIES:
+            self.entries.pop(next(iter(self.entries)))
+        caller = torch.cuda.current_stream(self.dev)
+        if not host and stream != caller:
+            stream.wait_stream(caller)
+        with torch.cuda.stream(stream):
+            tensors = (cam.view_matrix.to(self.dev, torch.float32).contiguous(),
+                       cam.intrinsic_matrix.to(self.dev, torch.float32).contiguous(),
+                       c2w.detach()[:, 3].to(self.dev, torch.float32).contiguous())
+            ev = torch.cuda.Event(); ev.record(stream)
+        for f in front_streams(self.dev):
+            if f != stream:
+                f.wait_event(ev)
+        self.entries[key] = (c2w, c2w._version, tensors, fp)
+        return tensors
+
+    def clear(self) -> None:
+        self.entries.clear()
+
+
+def texel_grads(env, flat: Optional[Tensor] = None):
+    """(g_flat, g_base, g_levels, GsEnvGrad): texel-gradient accumulators of the pyramid `env` in ONE flat buffer -- `flat` (zeroed)
+    when its size fits, else zeros on the current stream."""
+    sizes = [env.base.numel()] + [l.numel() for l in env.levels]
+    if flat is None or flat.numel() != sum(sizes):
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=env.base.device)
+    parts = torch.split(flat, sizes)
+    g_base = parts[0].view_as(env.base)
+    g_levels = [q.view_as(l) for q, l in zip(parts[1:], env.levels)]
+    eg = L.GsEnvGrad(); eg.base = g_base.data_ptr()
+    for i, g in enumerate(g_levels):
+        eg.levels[i] = g.data_ptr()
+    return flat, g_base, g_levels, eg
+
+
+def log_ws(I: int, W: int, H: int, dev: torch.device) -> Tensor:
+    """The compositor's cull log of one view (what composite_fwd leaves for composite_bwd), on the current stream."""
+    return torch.empty(L.lib().gs_raster_log_ws_bytes(L.i64(I), W, H, 16), dtype=torch.uint8, device=dev)
+
+
+def composite_fwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Tensor, log: Tensor):
+    """Compositor + tone map (S4 in its epilogue) of a view binned by bin_stage on the current stream -> (img, render, alphas,
+    last_ids); it leaves its cull log (stream index + pixel mask of every record that entered a dense batch) in `log` for
+    composite_bwd, which then neither culls nor builds masks."""
+    dev = state["isect_offsets"].device
+    f32 = torch.float32
+    render = torch.empty(H, W, 3, dtype=f32, device=dev); alphas = torch.empty(H, W, dtype=f32, device=dev)
+    last_ids = torch.empty(H, W, dtype=torch.int32, device=dev); img = torch.empty(H, W, 4, dtype=f32, device=dev)
+    rws = state["raster_ws"]
+    L.check(L.lib().gs_raster_composite_tone_log(W, H, 16, V, None, L.i64(I), L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
+                                                 L.ptr(render), L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(img),
+                                                 L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(log), C.c_size_t(log.numel()), L.stream()),
+            "gs_raster_composite_tone_log")
+    return img, render, alphas, last_ids
+
+
+def composite_bwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Tensor, render: Tensor, alphas: Tensor,
+                  last_ids: Tensor, log: Tensor, v_img: Tensor, g_exp: Tensor) -> None:
+    """A6 + S4 backward on the current stream: ADDS into the view's gradient records (state["v_packed"]) and into `g_exp`."""
+    rws = state["raster_ws"]
+    L.check(L.lib().gs_raster_bwd_tone_log_acc(W, H, 16, V, None, L.i64(I), L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
+                                               L.ptr(render), L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(v_img),
+                                               L.ptr(state["v_packed"]), L.ptr(g_exp), L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(log),
+                                               C.c_size_t(log.numel()), L.stream()), "gs_raster_bwd_tone_log_acc")
+
+
+def tail_schedule(default):
+    """Views per tail launch of a backward pass, the last entry repeating: GEOSPLAT_TAIL_BATCH ("3,4,1"), or `default` ("auto")."""
+    tb = os.environ.get("GEOSPLAT_TAIL_BATCH", "auto")
+    return default if tb == "auto" else [max(1, int(x)) for x in tb.split(",")]
+
+
+def tail_batch(views, args, accumulate: bool, final: bool, tail: torch.cuda.Stream, proj: torch.cuda.Stream, tail_events=None):
+    """tail_multi_stage(views, *args) behind the caller's stream.  A BACKGROUND launch on `tail` (parts 7: half of the CUs, beside
+    the compositor of the following views), or the `final` batch of a backward pass: the shading half (parts 1) on `tail`, its
+    projection half (parts 2) behind it on `proj` -- a front stream, idle by then -- beside whatever the caller runs next, e.g. the
+    prefilter backward, which needs only the texel gradients; `tail_events` then gets (start, end of the shading half, end of the
+    projection half).  The per-view tensors are recorded on every stream used; returns those streams."""
+    timed = final and tail_events is not None
+    ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(tail.device))
+    tail.wait_event(ev)
+    with torch.cuda.stream(tail):
+        if timed:
+            t0 = torch.cuda.Event(enable_timing=True); t0.record(tail)
+        tail_multi_stage(views, *args, accumulate=accumulate, parts=1 if final else 7)
+    used = [tail]
+    if final:
+        ev_sh = torch.cuda.Event(enable_timing=timed); ev_sh.record(tail)
+        proj.wait_event(ev_sh)                              # (v_means: the projection half adds to what the shading half stored)
+        with torch.cuda.stream(proj):
+            tail_multi_stage(views, *args, accumulate=accumulate, parts=2)
+            if timed:
+                t2 = torch.cuda.Event(enable_timing=True); t2.record(proj)
+                tail_events.append((t0, ev_sh, t2))
+        used.append(proj)
+    for v in views:
+        for t in v[:6]:
+            for s in used:
+                t.record_stream(s)
+    return used
+
+
+def status_overflow(word: Tensor):
+    """Decode a host copy of the device status word {GS_ENOSPC or 0, largest required I, largest required V, depth outside the 24-bit
+    key range}: (truncated -- a view was composited from a truncated list, or with clamped keys --, needs_32bit_keys, required_I)."""
+    w = word.tolist()
+    return w[0] != 0 or w[3] != 0, w[3] != 0, w[1]

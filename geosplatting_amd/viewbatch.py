@@ -5,9 +5,9 @@ batch (rfstudio/model/geosplat.py:863-879) followed by ONE ``loss.backward()`` (
 what ``geosplatting_amd.RenderableAttrs.splat`` runs for that shape -- no engine object, no callback, nothing the trainer has to
 know about:
 
-  * every ``splat()`` call is ONE autograd node (``_SplatView``): forward = gs_front_fwd -> gs_isect_bin_front ->
-    gs_raster_prepare_vis (a front stream) -> gs_raster_composite_tone_log (the caller's stream); backward =
-    gs_raster_bwd_tone_log_acc into the view's 64-byte gradient records;
+  * every ``splat()`` call is ONE autograd node (``_SplatView``): forward = front.front_stage -> front.bin_stage (a front stream)
+    -> the record stream and front.composite_fwd (the caller's stream); backward = front.composite_bwd into the view's 64-byte
+    gradient records;
   * the views that read the SAME parameter tensors (same objects, same version counters) share a ``_Step``: activations once,
     one set of gradient buffers, and one ``_Gather`` node between the parameters and the views.  Autograd runs a node when all
     nodes that depend on it have run, so ``_Gather.backward`` executes exactly once per ``backward()``, AFTER the compositor
@@ -35,7 +35,6 @@ two calls with NO version bump in between is not seen -- call ``viewbatch.reset(
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import os
 import threading
 import warnings
@@ -62,12 +61,13 @@ class _DeviceState:
         # two front streams (+ the caller's stream + the tail stream = the four hardware queues HIP maps its streams onto by default:
         # a third front stream is 2 % faster alone in a process -- 608 against 596 views/s -- and 13 % SLOWER, 520 against 595, in a
         # process that holds other streams, where two of them then share a queue)
-        self.fronts = [L.shared_stream(dev, "front0"), L.shared_stream(dev, "front1")]
+        self.fronts = F.front_streams(dev)
         self.tail = L.shared_stream(dev, "tail")
         self.caps: "collections.OrderedDict[Tuple[int, int], _Capacity]" = collections.OrderedDict()   # by image size, least recently used first
         self.current: Optional["_Step"] = None   # the step new splat() calls may join
         self.unchecked = collections.deque()     # capacity-mode views whose counts nobody has looked at yet
-        self.cam_cache: Dict[tuple, tuple] = {}
+        self.cameras = F.CameraCache(dev)
+        self.cam_cache = self.cameras.entries    # (its entries: {key: (pose, version, tensors, fingerprint)}; tests read them)
         self.n_views = 0                         # views rendered so far (front stream round robin)
         self.lock = threading.RLock()            # forward runs on the caller's thread, backward on autograd's: both touch `unchecked`
 
@@ -125,35 +125,6 @@ def _use_capacity() -> bool:
     return os.environ.get("GEOSPLAT_CAPACITY", "1") != "0"
 
 
-def camera_tensors(st: _DeviceState, cam: Camera, stream: torch.cuda.Stream):
-    """Device (view matrix, K, position) of a camera, cached by the pose's STORAGE ADDRESS + version counter + intrinsics: the entry
-    keeps the pose tensor alive (its address cannot be recycled), an in-place update bumps the version, and `cameras[i]` of a
-    resident dataset -- a new tensor object every step over the same storage -- hits.  A miss builds the three tensors on `stream`
-    (a front stream: nothing on the caller's stream has to finish first) when the pose is host-resident; a device-resident pose
-    may still be in flight on the caller's stream, so its miss is ordered behind that stream."""
-    c2w = cam.c2w
-    intr = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.width), int(cam.height))
-    host = c2w.device.type == "cpu"
-    fp = c2w.detach().numpy().tobytes() if host else None              # 48 bytes: catches writes that bypass the version counter
-    key = (c2w.data_ptr(), tuple(c2w.shape), tuple(c2w.stride()), intr)
-    hit = st.cam_cache.get(key)
-    if hit is not None and hit[1] == c2w._version and hit[3] == fp:
-        return hit[2]
-    if len(st.cam_cache) >= 4096:
-        st.cam_cache.pop(next(iter(st.cam_cache)))
-    if not host:
-        stream.wait_stream(torch.cuda.current_stream(st.dev))
-    with torch.cuda.stream(stream):
-        tensors = (cam.view_matrix.to(st.dev, torch.float32).contiguous(), cam.intrinsic_matrix.to(st.dev, torch.float32).contiguous(),
-                   c2w.detach()[:, 3].to(st.dev, torch.float32).contiguous())
-        ev = torch.cuda.Event(); ev.record(stream)
-    for f in st.fronts:                                                 # whichever front stream uses the entry later: ordered behind its upload
-        if f is not stream:
-            f.wait_event(ev)
-    st.cam_cache[key] = (c2w, c2w._version, tensors, fp)
-    return tensors
-
-
 # ------------------------------------------------------------------------------------------------------------ the step
 class _View:
     __slots__ = ("cam", "W", "H", "V", "I", "state", "render", "alphas", "last_ids", "log_ws", "tone", "exposure", "exact", "cap",
@@ -188,23 +159,14 @@ class _Step:
             t, dev = self.t, self.st.dev
             N = t["means"].shape[0]
             z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            sizes = [self.env.base.numel()] + [l.numel() for l in self.env.levels]
-            g_flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)     # texel gradients: float atomics add into them
-            parts = torch.split(g_flat, sizes)
-            g_base = parts[0].view_as(self.env.base)
-            g_levels = [q.view_as(l) for q, l in zip(parts[1:], self.env.levels)]
-            eg = L.GsEnvGrad(); eg.base = g_base.data_ptr()
-            for i, gl in enumerate(g_levels):
-                eg.levels[i] = gl.data_ptr()
+            g_flat, g_base, g_levels, eg = F.texel_grads(self.env)
             self.g = dict(means=z(N, 3), quats=z(N, 4), scales_act=z(N, 3), opac_act=z(N), normals=z(N, 3), kd=z(N, 3), ks=z(N, 2),
                           g_flat=g_flat, base=g_base, levels=g_levels, eg=eg)
             self.n_tail = 0
-            tb = os.environ.get("GEOSPLAT_TAIL_BATCH", "auto")
-            n = sum(1 for v in self.views if not v.done)
             # batches of TWO views in this call shape (8 views: 2 + 2 + 2 in the background, 2 at the gather node): 612 views/s
             # against 598 for the engine's 3 + 3 + 2, 603 for one view per launch, 586 for one launch of 8 -- here the whole
             # compositor backward phase runs back to back, so smaller background launches keep up with it better
-            self.sched = [2] if tb == "auto" else [max(1, int(x)) for x in tb.split(",")]
+            self.sched = F.tail_schedule([2])
             ev = torch.cuda.Event(); ev.record()
             self.st.tail.wait_event(ev)                    # (the zero fill above)
             for f in self.st.fronts:
@@ -229,37 +191,19 @@ class _Step:
             self.discard_pass()
 
     def launch_tail(self, final: bool) -> None:
-        """A7 + S1-S3 backward of the pending views in one call pair on the tail stream; `final`: the last launch of this backward
-        pass (all CUs, its projection half on a front stream -- idle by now -- beside whatever the caller runs next, e.g. the
-        prefilter backward, which needs only the texel gradients)."""
+        """A7 + S1-S3 backward of the pending views in one batch (front.tail_batch); `final`: the last batch of this backward pass.
+        The views' buffers go back to the allocator."""
         views, self.pending = self.pending, []
         if not views:
             return
         st, t, g = self.st, self.t, self.g
         mr, mm, mode = self.cfg
-        main = torch.cuda.current_stream(st.dev)
-        tail = st.tail
-        ev = torch.cuda.Event(); ev.record(main)
-        tail.wait_event(ev)
         tv = [(v.cam[0], v.cam[1], v.cam[2], v.state["vis_records"], v.state["v_packed"], v.state["packed_index"], v.W, v.H) for v in views]
-        split = final
-        args = (tv, t["means"], t["quats"], self.scales_act, self.opac_act, t["normals"], t["kd"], t["ks"], self.e, g["eg"], mr, mm, mode,
+        args = (t["means"], t["quats"], self.scales_act, self.opac_act, t["normals"], t["kd"], t["ks"], self.e, g["eg"], mr, mm, mode,
                 g["means"], g["quats"], g["scales_act"], g["opac_act"], g["normals"], g["kd"], g["ks"])
-        with torch.cuda.stream(tail):
-            F.tail_multi_stage(*args, accumulate=self.n_tail > 0, parts=1 if split else (3 if final else 7))
-        used = [tail]
-        if split:
-            ev_sh = torch.cuda.Event(); ev_sh.record(tail)
-            ps = st.fronts[0]
-            ps.wait_event(ev_sh)                           # (v_means: the projection half adds to what the shading half stored)
-            with torch.cuda.stream(ps):
-                F.tail_multi_stage(*args, accumulate=self.n_tail > 0, parts=2)
-            used.append(ps)
+        used = F.tail_batch(tv, args, self.n_tail > 0, final, st.tail, st.fronts[0])
         self.n_tail += 1
         for v in views:
-            for x in (v.state["vis_records"], v.state["v_packed"], v.state["packed_index"]) + tuple(v.cam):
-                for s in used:
-                    x.record_stream(s)
             v.state = v.render = v.alphas = v.last_ids = v.log_ws = None      # the view's ~1 GB of buffers go back to the allocator
         for name in ("means", "quats", "scales_act", "opac_act", "normals", "kd", "ks", "g_flat"):
             for s in used:
@@ -296,9 +240,9 @@ def _poll_unchecked(st: _DeviceState, wait_views=None) -> None:
                     cap.key32 = True
             hs = v.host_status
             if hs is not None:                               # the view's OWN device word (nothing shared, nothing to clear)
-                if int(hs[0]) != 0 or int(hs[3]) != 0:
-                    over = True
-                    cap.key32 = cap.key32 or int(hs[3]) != 0
+                truncated, key32, _ = F.status_overflow(hs)
+                over = over or truncated
+                cap.key32 = cap.key32 or key32
                 F.release_counts4(hs)
                 v.host_status = None
             cap.learn(hc, v.N)
@@ -319,7 +263,6 @@ def _warn_unreported(step: "_Step") -> None:
 
 def _view_forward(step: _Step, cam: Camera, exposure: Tensor, tone: int, want_grad: bool) -> Tuple[Tensor, _View]:
     st, t = step.st, step.t
-    lib = L.lib()
     dev = st.dev
     mr, mm, mode = step.cfg
     W, H = int(cam.width), int(cam.height)
@@ -348,7 +291,7 @@ def _view_forward(step: _Step, cam: Camera, exposure: Tensor, tone: int, want_gr
             status = torch.zeros(4, dtype=torch.int64, device=dev)
     tight = os.environ.get("GEOSPLAT_TIGHT_TILES", "1") != "0"
     side.wait_event(step.ready)                            # parameters / pyramid / activations -- NOT the previous view's compositor
-    cam_t = camera_tensors(st, cam, side)
+    cam_t = st.cameras.get(cam, side)
     v = _View()
     v.cam, v.W, v.H, v.tone, v.exact, v.cap, v.done, v.index = cam_t, W, H, tone, exact, cap, (False if want_grad else None), len(step.views)
     v.N, v.status, v.over, v.i_seen, v.reported = N, status, False, 0, False
@@ -359,10 +302,9 @@ def _view_forward(step: _Step, cam: Camera, exposure: Tensor, tone: int, want_gr
         # the record stream of the compositor (gs_raster_prepare_vis: 0.1 ms, HBM gather) is built on the CALLER's stream, whose
         # compositor forward (0.29 ms per view) leaves it idle for more than half of the forward phase, while the front streams
         # (0.47 ms of front + binning per view) are its critical path (measured: the same 13.3 ms either way)
-        split = True
-        state, V, I = F.bin_stage(fr, i_cap, status, prepare=not split)
-        v_packed = torch.zeros(max(V, 1), lib.gs_raster_grad_stride(3), dtype=torch.float32, device=dev) if want_grad else None
-        log_ws = torch.empty(lib.gs_raster_log_ws_bytes(L.i64(I), W, H, 16), dtype=torch.uint8, device=dev)
+        state, V, I = F.bin_stage(fr, i_cap, status, prepare=False)
+        v_packed = torch.zeros(max(V, 1), L.lib().gs_raster_grad_stride(3), dtype=torch.float32, device=dev) if want_grad else None
+        log_ws = F.log_ws(I, W, H, dev)
         v.host_status = None
         if not exact:
             # the device's own word (word 0: a view truncated at its capacity, or a look-back of the front / emission that gave up;
@@ -382,35 +324,24 @@ def _view_forward(step: _Step, cam: Camera, exposure: Tensor, tone: int, want_gr
         if isinstance(x, Tensor):
             x.record_stream(main)
     main.wait_event(ev)
-    if split:
-        for x in (fr.vis, fr.counts, fr.packed_index):
-            if x is not None:
-                x.record_stream(main)
-        state, V, I = F.bin_stage(fr, i_cap, status, binned=(state["flatten_ids"], state["isect_offsets"]))
+    for x in (fr.vis, fr.counts, fr.packed_index):
+        if x is not None:
+            x.record_stream(main)
+    state, V, I = F.bin_stage(fr, i_cap, status, binned=(state["flatten_ids"], state["isect_offsets"]))
     if v_packed is not None:
         state["v_packed"] = v_packed
-    f32 = torch.float32
-    render = torch.empty(H, W, 3, dtype=f32, device=dev); alphas = torch.empty(H, W, dtype=f32, device=dev)
-    last_ids = torch.empty(H, W, dtype=torch.int32, device=dev); img = torch.empty(H, W, 4, dtype=f32, device=dev)
-    rws = state["raster_ws"]
-    L.check(lib.gs_raster_composite_tone_log(W, H, 16, V, None, L.i64(I), L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
-                                             L.ptr(render), L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(img), L.ptr(rws),
-                                             C.c_size_t(rws.numel()), L.ptr(log_ws), C.c_size_t(log_ws.numel()), L.stream()),
-            "gs_raster_composite_tone_log")
+    img, render, alphas, last_ids = F.composite_fwd(state, V, I, W, H, tone, exposure, log_ws)
     v.V, v.I, v.state, v.render, v.alphas, v.last_ids, v.log_ws, v.exposure = V, I, state, render, alphas, last_ids, log_ws, exposure
     return img, v
 
 
 def _view_backward(step: _Step, v: _View, v_img: Tensor) -> Tensor:
     """A6 + S4 backward of one view on the current stream; queues the view for a tail launch.  Returns d loss / d exposure."""
-    lib = L.lib()
-    s = v.state
-    if s is None:
+    if v.state is None:
         raise L.GeoSplatHipError("splat(): backward through a view a second time (its buffers were released after the first; "
                                  "render the view again instead of retain_graph)")
     v_img = v_img.contiguous().float()
     g_exp = torch.zeros(1, dtype=torch.float32, device=step.st.dev)
-    rws = s["raster_ws"]
     gather = step.has_gather                               # (False: only the exposure needs a gradient -- no tail, no gather node)
     if gather:
         if step.g is None:
@@ -426,13 +357,7 @@ def _view_backward(step: _Step, v: _View, v_img: Tensor) -> Tensor:
 
 
 def _view_backward_launch(step: _Step, v: _View, v_img: Tensor, g_exp: Tensor, gather: bool) -> Tensor:
-    lib = L.lib()
-    s = v.state
-    rws = s["raster_ws"]
-    L.check(lib.gs_raster_bwd_tone_log_acc(v.W, v.H, 16, v.V, None, L.i64(v.I), L.ptr(s["counts"]), L.ptr(s["isect_offsets"]),
-                                           L.ptr(v.render), L.ptr(v.alphas), L.ptr(v.last_ids), v.tone, L.ptr(v.exposure), L.ptr(v_img),
-                                           L.ptr(s["v_packed"]), L.ptr(g_exp), L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(v.log_ws),
-                                           C.c_size_t(v.log_ws.numel()), L.stream()), "gs_raster_bwd_tone_log_acc")
+    F.composite_bwd(v.state, v.V, v.I, v.W, v.H, v.tone, v.exposure, v.render, v.alphas, v.last_ids, v.log_ws, v_img, g_exp)
     v.done = True
     if not gather:
         v.state = v.render = v.alphas = v.last_ids = v.log_ws = None
