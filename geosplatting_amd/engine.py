@@ -26,8 +26,7 @@ from .cameras import Camera
 from .parallel import GradBucket, collectives_active
 from . import front as F
 from .shading import _MODE, _TONE, RenderableAttrs, _make_env, get_fg_lut
-from .splitsum import (TextureSplitSum, as_splitsum, as_splitsum_backward, as_splitsum_backward_sharded,
-                       as_splitsum_sharded, can_shard_prefilter)
+from .splitsum import TextureSplitSum, as_splitsum, as_splitsum_backward, as_splitsum_forward, can_shard_prefilter
 from .splats import SplatSet
 
 PARAM_NAMES = ("means", "scales", "quats", "opacities", "normals", "kd", "ks", "cubemap", "exposure")
@@ -222,15 +221,12 @@ class RenderStep:
         the one filtered once."""
         if not self.prefilter:
             if self._static_env is None:
-                with torch.no_grad():
-                    self._static_env = as_splitsum(self.p.cubemap)
+                self._static_env = as_splitsum_forward(self.p.cubemap)
             return self._static_env
-        cubemap = self.p.cubemap.detach()
         if sharded:
             import torch.distributed as dist
-            return as_splitsum_sharded(cubemap, dist.get_rank(), world, self._prefilter_group())
-        with torch.no_grad():
-            return as_splitsum(cubemap)
+            return as_splitsum_forward(self.p.cubemap, rank=dist.get_rank(), world=world, group=self._prefilter_group(), sharded=True)
+        return as_splitsum_forward(self.p.cubemap)
 
     def _sharding(self, all_reduce: bool):
         """(world, sharded): S5 sharded over the ranks (each applies 1/world of every level's tiles, all-reduce of the disjoint
@@ -436,8 +432,8 @@ class RenderStep:
                 start_head, _ = self.bucket.all_reduce_split("cubemap")
                 with torch.cuda.stream(head_stream):
                     start_head()                                # per-Gaussian segments: communication stream, default communicator
-            g_cube = as_splitsum_backward_sharded(ctx.g_base, ctx.g_levels, dist.get_rank(), ctx.world, grp,
-                                                  min_roughness=env.min_roughness, max_roughness=env.max_roughness)
+            g_cube = as_splitsum_backward(ctx.g_base, ctx.g_levels, min_roughness=env.min_roughness, max_roughness=env.max_roughness,
+                                          rank=dist.get_rank(), world=ctx.world, group=grp, sharded=True)
             b["cubemap"].copy_(g_cube)                          # identical on every rank: not reduced again
             if pstream is not None:
                 main.wait_stream(pstream)

@@ -139,6 +139,24 @@ def _build_direction(res: int, roughness: float, ct: float, bounds: Tensor, tabl
             "rows_per_tile": rows_per_tile}
 
 
+_wsum_cache: Dict[Tuple[int, float, float, int], Tensor] = {}
+
+
+def _weight_sums(res: int, roughness: float, cutoff: float, device: torch.device) -> Tensor:
+    """[6,R,R] sums of the pair weights per output texel: they do not depend on the cubemap, but on the pixel_area of the actual
+    sources (not mirror symmetric) -- the direct kernel on ones, cached like the bounds.  The tiled levels fold them into their
+    scales (specular_tiles), the direct backward divides by them."""
+    key = (res, float(roughness), float(cutoff), device.index or 0)
+    if key not in _wsum_cache:
+        ct, bounds = specular_bounds(res, roughness, cutoff, device)
+        ones = torch.ones(6, res, res, 3, dtype=torch.float32, device=device)
+        raw = torch.empty(6, res, res, 4, dtype=torch.float32, device=device)
+        L.check(L.lib().gs_specular_cubemap_fwd(res, L.ptr(ones), L.ptr(bounds), L.ptr(dir_table(res, device)), L.f32(roughness),
+                                                L.f32(ct), L.ptr(raw), L.stream()), "gs_specular_cubemap_fwd")
+        _wsum_cache[key] = raw[..., 3].contiguous()
+    return _wsum_cache[key]
+
+
 def specular_tiles(res: int, roughness: float, cutoff: float, device: torch.device) -> Optional[Dict]:
     """Tiled pair-weight tables of one pyramid level (csrc/gs_splitsum_tiles.hip), built once per (res, roughness, cutoff, device)
     -- they do not depend on the cubemap.  With exact mirror symmetry (checked on the device) the tables cover ONE octant of
@@ -176,12 +194,7 @@ def specular_tiles(res: int, roughness: float, cutoff: float, device: torch.devi
     if entry["fwd"]["pairs"] != entry["bwd"]["pairs"]:
         raise L.GeoSplatHipError(f"specular tiles R={res}: {entry['fwd']['pairs']} forward pairs but {entry['bwd']['pairs']} transposed "
                                  f"pairs (candidate margin {BWD_MARGIN} too small?)")
-    # sum of the pair weights per output texel (needs pixel_area of the actual sources: not mirror symmetric) -- the direct kernel on ones
-    ones = torch.ones(6, res, res, 3, dtype=torch.float32, device=device)
-    raw = torch.empty(6, res, res, 4, dtype=torch.float32, device=device)
-    L.check(lib.gs_specular_cubemap_fwd(res, L.ptr(ones), L.ptr(bounds), L.ptr(table), L.f32(roughness), L.f32(ct), L.ptr(raw), L.stream()),
-            "gs_specular_cubemap_fwd")
-    entry["wsum"] = raw[..., 3].contiguous()
+    entry["wsum"] = _weight_sums(res, roughness, cutoff, device)
     entry["inv_wsum"] = (1.0 / entry["wsum"]).contiguous()                # scale of the staged d loss / d level texels (backward)
     entry["area4"] = (table[..., 3] * 0.25).contiguous()                  # pixel_area / 4: scale of the staged sources (forward)
     _tiles_cache[key] = entry
@@ -223,7 +236,7 @@ def _tiles_apply(entry: Dict, direction: str, src: Tensor, dst: Tensor, tile_beg
                                             L.ptr(dst), tile_begin, te, C.c_size_t(d["lds_bytes"]), L.stream()), "gs_specular_tiles_apply")
 
 
-MERGED_APPLY = True               # False (tests): one launch per level, the launch sequence of rounds 3-5
+MERGED_APPLY = True               # False (tests): _tiles_apply_multi launches the levels one by one
 
 
 def _tiles_apply_multi(jobs, direction: str, world: int = 1) -> None:
@@ -390,38 +403,6 @@ def specular_cubemap(cubemap: Tensor, roughness: float, cutoff: float = 0.99, ca
     return _SpecularCubemap.apply(cubemap, float(roughness), ct, bounds)
 
 
-def _specular_level_backward(gl: Tensor, rough: float, cutoff: float) -> Tensor:
-    """d loss / d (mip level) from d loss / d (prefiltered level), on the current stream, without an autograd graph."""
-    res = gl.shape[1]
-    g = torch.empty(6, res, res, 3, dtype=torch.float32, device=gl.device)
-    e = specular_tiles(res, rough, cutoff, gl.device)
-    if e is not None:
-        _tiles_apply(e, "bwd", gl.contiguous(), g)
-        return g
-    ct, bounds = specular_bounds(res, rough, cutoff, gl.device)
-    wsum = _direct_wsum(res, rough, cutoff, gl.device)
-    v = (gl / wsum).contiguous()
-    L.check(L.lib().gs_specular_cubemap_bwd(res, L.ptr(bounds), L.ptr(dir_table(res, gl.device)), L.ptr(v), L.f32(rough), L.f32(ct),
-                                            L.ptr(g), 0, L.stream()), "gs_specular_cubemap_bwd")
-    return g
-
-
-_wsum_cache: Dict[Tuple[int, float, float, int], Tensor] = {}
-
-
-def _direct_wsum(res: int, roughness: float, cutoff: float, device: torch.device) -> Tensor:
-    """[6,R,R,1] sums of the pair weights per output texel (they do not depend on the cubemap): the direct kernel on ones."""
-    key = (res, float(roughness), float(cutoff), device.index or 0)
-    if key not in _wsum_cache:
-        ct, bounds = specular_bounds(res, roughness, cutoff, device)
-        ones = torch.ones(6, res, res, 3, dtype=torch.float32, device=device)
-        raw = torch.empty(6, res, res, 4, dtype=torch.float32, device=device)
-        L.check(L.lib().gs_specular_cubemap_fwd(res, L.ptr(ones), L.ptr(bounds), L.ptr(dir_table(res, device)), L.f32(roughness),
-                                                L.f32(ct), L.ptr(raw), L.stream()), "gs_specular_cubemap_fwd")
-        _wsum_cache[key] = raw[..., 3:].contiguous()
-    return _wsum_cache[key]
-
-
 # ----------------------------------------------------------------------------- atlas packing (reference layout)
 def merge_mipmaps(mipmaps: List[Tensor]) -> Tensor:
     """[6,R,R,3], [6,R/2,R/2,3], ... -> atlas [6,4,R,R] (rfstudio/graphics/_mesh/_texture.py:228-244)"""
@@ -486,39 +467,103 @@ def _mip_chain_backward(g_mips: List[Tensor], g_base: Tensor) -> Tensor:
     return g_mips[0]
 
 
+# ----------------------------------------------------------------------------- the whole pyramid: one forward, one backward
+# The reference prefilters the environment once per step on its one device (rfstudio/model/geosplat.py:780-785); with one
+# view per GPU the replicated prefilter would sit beside a ~2 ms view on every rank (Amdahl).  The tiled operator is independent
+# per tile of output texels in both directions, so rank r applies its share of every tiled level's tile list (shard_tiles) into
+# a zero-filled level and the ranks SUM (disjoint supports: x + 0, exact and identical everywhere):
+#   forward : one all-reduce over the flat pyramid (25 MB for a 512^2 map)
+#   backward: the caller's all-reduce of the 25 MB texel gradients (they are sums over the views of ALL ranks), then one
+#             all-reduce of the per-level cubemap-gradient pieces; the mip chain / diffuse backward and the levels that are not
+#             tiled (direct kernels) are replicated, so every rank ends with the same cubemap gradient and NO all-reduce of it
+#             is needed.
+# Unsharded (rank 0 of world 1, sharded=False) the same code writes every tiled level into an uninitialised buffer.
+def _level_roughness(n: int, min_roughness: float, max_roughness: float) -> List[float]:
+    return [(idx / (n - 2)) * (max_roughness - min_roughness) + min_roughness for idx in range(n - 1)] + [1.0]
+
+
+def can_shard_prefilter(cubemap_res: int, world: int, min_resolution: int = 16) -> bool:
+    from .parallel import collectives_active
+    return (world > 1 or collectives_active()) and tiles_eligible(cubemap_res) and cubemap_res >= 4 * min_resolution
+
+
+def _tiled_levels(direction: str, srcs: List[Tensor], roughs: List[float], cutoff: float, rank: int, world: int, group,
+                  sharded: bool, first: Optional[Tensor] = None) -> List[Optional[Tensor]]:
+    """The tiled levels of one direction (fwd: mip -> prefiltered level; bwd: d loss / d level -> d loss / d mip) in ONE apply over
+    this rank's share of every level's tiles, into one flat buffer: zero-filled and summed over `group` when `sharded`,
+    uninitialised otherwise.  `first` (unsharded only): written instead of the buffer for level 0.  None for the levels that are
+    not tiled: the caller runs the direct kernels for them."""
+    dev = srcs[0].device
+    tiled = [i for i, s in enumerate(srcs) if tiles_eligible(int(s.shape[1]))]
+    outs: List[Optional[Tensor]] = [None] * len(srcs)
+    if first is not None and 0 in tiled:
+        outs[0] = first
+    own = [i for i in tiled if outs[i] is None]
+    sizes = [srcs[i].numel() for i in own]
+    flat = (torch.zeros if sharded else torch.empty)(sum(sizes), dtype=torch.float32, device=dev)
+    for i, q in zip(own, torch.split(flat, sizes)):
+        outs[i] = q.view_as(srcs[i])
+    jobs = []
+    for i in tiled:
+        e = specular_tiles(int(srcs[i].shape[1]), roughs[i], cutoff, dev)
+        jobs.append((e, srcs[i], outs[i], *shard_tiles(e["n_tiles"], rank, world)))
+    _tiles_apply_multi(jobs, direction, world)
+    if sharded and tiled:
+        import torch.distributed as dist
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    return outs
+
+
+def as_splitsum_forward(cubemap: Tensor, *, cutoff: float = 0.99, min_resolution: int = 16, min_roughness: float = 0.08,
+                        max_roughness: float = 0.5, rank: int = 0, world: int = 1, group=None, sharded: bool = False) -> TextureSplitSum:
+    """`as_splitsum` without an autograd graph, on the CURRENT stream: the mip chain (one launch), the diffuse map, every tiled
+    level in one launch (sharded: this rank's tiles, then the all-reduce) and the levels that are not tiled through the direct
+    kernel, on every rank."""
+    L.require_cuda(cubemap)
+    with torch.no_grad():
+        mips = mip_chain(cubemap, min_resolution)
+        assert len(mips) > 2, "Min resolution is too large."
+        # (round 6, measured and removed: the diffuse map on a stream of its own beside the levels' launch -- a fifth stream shares
+        #  one of HIP's four hardware queues with a front stream: 649 against 710 views/s)
+        base = diffuse_cubemap(mips[-1])
+        roughs = _level_roughness(len(mips), min_roughness, max_roughness)
+        levels = _tiled_levels("fwd", mips, roughs, cutoff, rank, world, group, sharded)
+        levels = [specular_cubemap(m, r, cutoff) if l is None else l for m, r, l in zip(mips, roughs, levels)]
+    return TextureSplitSum(base, levels, min_roughness, max_roughness)
+
+
 def as_splitsum_backward(g_base: Tensor, g_levels: List[Tensor], *, cutoff: float = 0.99, min_roughness: float = 0.08,
-                         max_roughness: float = 0.5, out: Optional[Tensor] = None) -> Tensor:
+                         max_roughness: float = 0.5, out: Optional[Tensor] = None, rank: int = 0, world: int = 1, group=None,
+                         sharded: bool = False) -> Tensor:
     """Explicit backward of `as_splitsum` on the CURRENT stream (no autograd graph, so a caller can place it on any HIP
     stream -- the autograd engine would run it on the stream of the forward): texel gradients of the base map and of
-    the n levels -> gradient of the cubemap (written into `out` [6,R,R,3] when given).  The tiled levels run as ONE launch."""
-    n = len(g_levels)
-    roughs = _level_roughness(n, min_roughness, max_roughness)
-    g_mips: List[Optional[Tensor]] = [None] * n
-    jobs = []
+    the n levels -> gradient of the cubemap (written into `out` [6,R,R,3] when given).  The tiled levels run as ONE launch.
+    Sharded, the texel gradients must already be summed over the ranks, and every rank gets the same cubemap gradient."""
+    roughs = _level_roughness(len(g_levels), min_roughness, max_roughness)
+    first = None if sharded else out                   # (sharded: level 0 is a piece of the summed buffer)
+    g_mips = _tiled_levels("bwd", g_levels, roughs, cutoff, rank, world, group, sharded, first)
     for i, (gl, rough) in enumerate(zip(g_levels, roughs)):
-        res = gl.shape[1]
-        e = specular_tiles(res, rough, cutoff, gl.device)
-        if e is None:
-            g_mips[i] = _specular_level_backward(gl, rough, cutoff)
-            continue
-        g = out if (i == 0 and out is not None) else torch.empty(6, res, res, 3, dtype=torch.float32, device=gl.device)
-        jobs.append((e, gl, g, 0, None))
-        g_mips[i] = g
-    _tiles_apply_multi(jobs, "bwd")
+        if g_mips[i] is None:                          # direct kernel: the transposed gather of d loss / d level over the weight sums
+            res = gl.shape[1]
+            ct, bounds = specular_bounds(res, rough, cutoff, gl.device)
+            v = (gl / _weight_sums(res, rough, cutoff, gl.device).unsqueeze(-1)).contiguous()
+            g_mips[i] = first if (i == 0 and first is not None) else torch.empty_like(v)
+            L.check(L.lib().gs_specular_cubemap_bwd(res, L.ptr(bounds), L.ptr(dir_table(res, gl.device)), L.ptr(v), L.f32(rough),
+                                                    L.f32(ct), L.ptr(g_mips[i]), 0, L.stream()), "gs_specular_cubemap_bwd")
     if out is not None and g_mips[0] is not out:
         out.copy_(g_mips[0]); g_mips[0] = out
     return _mip_chain_backward(g_mips, g_base)
 
 
-class _SplitSumFused(torch.autograd.Function):
-    """as_splitsum as ONE autograd node: mip chain (one launch), diffuse map, every specular level (one launch); backward =
-    as_splitsum_backward.  Used when every level goes through the tiled tables (R a multiple of 16 down to min_resolution)."""
+class _SplitSum(torch.autograd.Function):
+    """as_splitsum as ONE autograd node: forward = as_splitsum_forward, backward = as_splitsum_backward."""
 
     @staticmethod
     def forward(ctx, cubemap: Tensor, cutoff: float, min_resolution: int, min_roughness: float, max_roughness: float):
-        base, levels = _as_splitsum_fused(cubemap, cutoff, min_resolution, min_roughness, max_roughness)
-        ctx.cfg = (cutoff, min_roughness, max_roughness, [tuple(l.shape) for l in levels], tuple(base.shape))
-        return (base, *levels)
+        env = as_splitsum_forward(cubemap, cutoff=cutoff, min_resolution=min_resolution, min_roughness=min_roughness,
+                                  max_roughness=max_roughness)
+        ctx.cfg = (cutoff, min_roughness, max_roughness, [tuple(l.shape) for l in env.levels], tuple(env.base.shape))
+        return (env.base, *env.levels)
 
     @staticmethod
     def backward(ctx, g_base, *g_levels):
@@ -530,132 +575,8 @@ class _SplitSumFused(torch.autograd.Function):
         return g, None, None, None, None
 
 
-def _fused_eligible(cubemap: Tensor, min_resolution: int) -> bool:
-    R = int(cubemap.shape[1])
-    if cubemap.dim() != 4 or cubemap.shape[3] != 3 or not MERGED_APPLY:
-        return False
-    n = 0
-    r = R
-    while r > min_resolution:
-        if not tiles_eligible(r) or r % 2:
-            return False
-        r //= 2
-        n += 1
-    return n >= 2 and n <= 5 and tiles_eligible(r)
-
-
-def _as_splitsum_fused(cubemap: Tensor, cutoff: float, min_resolution: int, min_roughness: float, max_roughness: float):
-    mips = mip_chain(cubemap, min_resolution)
-    n = len(mips)
-    # (round 6, measured and removed: the diffuse map on a stream of its own beside the levels' launch -- a fifth stream shares one of
-    #  HIP's four hardware queues with a front stream: 649 against 710 views/s)
-    with torch.no_grad():
-        base = diffuse_cubemap(mips[-1])
-    roughs = _level_roughness(n, min_roughness, max_roughness)
-    sizes = [m.numel() for m in mips]
-    flat = torch.empty(sum(sizes), dtype=torch.float32, device=cubemap.device)
-    levels = [t.view_as(m) for t, m in zip(torch.split(flat, sizes), mips)]
-    jobs = []
-    for m, out, rough in zip(mips, levels, roughs):
-        e = specular_tiles(int(m.shape[1]), rough, cutoff, cubemap.device)
-        jobs.append((e, m, out, 0, None))
-    _tiles_apply_multi(jobs, "fwd")
-    return base, levels
-
-
 def as_splitsum(cubemap: Tensor, *, cutoff: float = 0.99, min_resolution: int = 16, min_roughness: float = 0.08,
                 max_roughness: float = 0.5) -> TextureSplitSum:
     """TextureCubeMap.as_splitsum (rfstudio/graphics/_mesh/_texture.py:530-557); differentiable w.r.t. cubemap."""
-    L.require_cuda(cubemap)
-    if _fused_eligible(cubemap, min_resolution):
-        out = _SplitSumFused.apply(cubemap.float(), float(cutoff), int(min_resolution), float(min_roughness), float(max_roughness))
-        return TextureSplitSum(out[0], list(out[1:]), min_roughness, max_roughness)
-    mips = [cubemap.float()]
-    while mips[-1].shape[1] > min_resolution:
-        mips.append(_CubeMapMip.apply(mips[-1]))
-    assert len(mips) > 2, "Min resolution is too large."
-    base = diffuse_cubemap(mips[-1])
-    n = len(mips)
-    levels = []
-    for idx in range(n - 1):
-        roughness = (idx / (n - 2)) * (max_roughness - min_roughness) + min_roughness
-        levels.append(specular_cubemap(mips[idx], roughness, cutoff))
-    levels.append(specular_cubemap(mips[-1], 1.0, cutoff))
-    return TextureSplitSum(base, levels, min_roughness, max_roughness)
-
-
-# ----------------------------------------------------------------------------- sharded prefilter (multi-GPU)
-# The reference prefilters the environment once per step on its one device (rfstudio/model/geosplat.py:780-785); with one
-# view per GPU the replicated prefilter would sit beside a ~2 ms view on every rank (Amdahl).  The tiled operator is independent
-# per tile of output texels in both directions, so rank r applies its share of every tiled level's tile list (shard_tiles) into
-# a zero-filled level and the ranks SUM (disjoint supports: x + 0, exact and identical everywhere):
-#   forward : one all-reduce over the flat pyramid (25 MB for a 512^2 map)
-#   backward: all-reduce of the 25 MB texel gradients (they are sums over the views of ALL ranks), then one all-reduce of the
-#             per-level cubemap-gradient pieces; the mip chain / diffuse backward and the levels below 64^2 (direct kernels,
-#             tens of microseconds) are replicated, so every rank ends with the same cubemap gradient and NO all-reduce of it
-#             is needed.
-def _level_roughness(n: int, min_roughness: float, max_roughness: float) -> List[float]:
-    return [(idx / (n - 2)) * (max_roughness - min_roughness) + min_roughness for idx in range(n - 1)] + [1.0]
-
-
-def can_shard_prefilter(cubemap_res: int, world: int, min_resolution: int = 16) -> bool:
-    from .parallel import collectives_active
-    return (world > 1 or collectives_active()) and tiles_eligible(cubemap_res) and cubemap_res >= 4 * min_resolution
-
-
-def _flat_levels(res_list: List[int], device) -> Tuple[Tensor, List[Tensor]]:
-    sizes = [6 * r * r * 3 for r in res_list]
-    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=device)
-    return flat, [q.view(6, r, r, 3) for q, r in zip(torch.split(flat, sizes), res_list)]
-
-
-def as_splitsum_sharded(cubemap: Tensor, rank: int, world: int, group=None, *, cutoff: float = 0.99, min_resolution: int = 16,
-                        min_roughness: float = 0.08, max_roughness: float = 0.5) -> TextureSplitSum:
-    """`as_splitsum` (no autograd graph) with the tiled levels computed 1/world per rank and summed."""
-    import torch.distributed as dist
-    L.require_cuda(cubemap)
-    with torch.no_grad():
-        mips = mip_chain(cubemap, min_resolution)
-        assert len(mips) > 2, "Min resolution is too large."
-        base = diffuse_cubemap(mips[-1])
-        roughs = _level_roughness(len(mips), min_roughness, max_roughness)
-        tiled = [i for i, m in enumerate(mips) if tiles_eligible(m.shape[1])]
-        flat, parts = _flat_levels([mips[i].shape[1] for i in tiled], cubemap.device)
-        levels: List[Optional[Tensor]] = [None] * len(mips)
-        jobs = []
-        for out, i in zip(parts, tiled):
-            e = specular_tiles(mips[i].shape[1], roughs[i], cutoff, cubemap.device)
-            t0, t1 = shard_tiles(e["n_tiles"], rank, world)
-            jobs.append((e, mips[i], out, t0, t1))
-            levels[i] = out
-        _tiles_apply_multi(jobs, "fwd", world)
-        if tiled:
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-        for i, m in enumerate(mips):
-            if levels[i] is None:
-                levels[i] = specular_cubemap(m, roughs[i], cutoff)          # small levels: replicated
-    return TextureSplitSum(base, levels, min_roughness, max_roughness)
-
-
-def as_splitsum_backward_sharded(g_base: Tensor, g_levels: List[Tensor], rank: int, world: int, group=None, *, cutoff: float = 0.99,
-                                 min_roughness: float = 0.08, max_roughness: float = 0.5) -> Tensor:
-    """Cubemap gradient from texel gradients that are ALREADY summed over the ranks; identical result on every rank."""
-    import torch.distributed as dist
-    n = len(g_levels)
-    roughs = _level_roughness(n, min_roughness, max_roughness)
-    tiled = [i for i, gl in enumerate(g_levels) if tiles_eligible(gl.shape[1])]
-    flat, parts = _flat_levels([g_levels[i].shape[1] for i in tiled], g_base.device)
-    g_mips: List[Optional[Tensor]] = [None] * n
-    jobs = []
-    for out, i in zip(parts, tiled):
-        e = specular_tiles(g_levels[i].shape[1], roughs[i], cutoff, g_base.device)
-        t0, t1 = shard_tiles(e["n_tiles"], rank, world)
-        jobs.append((e, g_levels[i], out, t0, t1))
-        g_mips[i] = out
-    _tiles_apply_multi(jobs, "bwd", world)
-    if tiled:
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-    for i in range(n):
-        if g_mips[i] is None:
-            g_mips[i] = _specular_level_backward(g_levels[i], roughs[i], cutoff)
-    return _mip_chain_backward(g_mips, g_base)
+    out = _SplitSum.apply(cubemap.float(), float(cutoff), int(min_resolution), float(min_roughness), float(max_roughness))
+    return TextureSplitSum(out[0], list(out[1:]), min_roughness, max_roughness)
