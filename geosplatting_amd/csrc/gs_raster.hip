@@ -662,7 +662,9 @@ raster_fwd_window_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
                 listA = useA ? cur : listA;
                 listB = useA ? listB : cur;
                 slot[u] = win_wrap((useA ? qhead : baseB) + j);
-                if (CD > 3) cofs[u] = (useA ? parA : (parA ^ 1)) * D * 64 + j;
+                // (a lane without a candidate reads A's planes: B's may not have been written in this launch -- no B batch yet --
+                //  and LDS left over from an earlier kernel can hold a NaN / Inf that 0 * x would turn into a NaN pixel)
+                if (CD > 3) cofs[u] = ((useA || !has[u]) ? parA : (parA ^ 1)) * D * 64 + j;
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) { ca[u] = q.a[slot[u]]; cb[u] = q.b[slot[u]]; cc[u] = q.c[slot[u]]; }
@@ -696,7 +698,8 @@ raster_fwd_window_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
                     if (CD > 1) pix[1] = fmaf(cc[u].y, vis, pix[1]);
                     if (CD > 2) pix[2] = fmaf(cc[u].z, vis, pix[2]);
                 } else {
-                    // (no branch around the LDS reads: vis == 0 for a lane without an accepted candidate, the planes hold finite numbers)
+                    // (no branch around the LDS reads: vis == 0 for a lane without an accepted candidate, and the planes it reads were
+                    //  written by this launch -- colours or zeros, finite numbers)
                     const float* cg = colp + cofs[u];
 #pragma unroll
                     for (int k = 0; k < CD; ++k) if (k < D) pix[k] = fmaf(cg[k * 64], vis, pix[k]);
@@ -1149,16 +1152,17 @@ raster_bwd_lanes2_kernel(int W, int H, int tile_w, int n_tiles, int D, const int
 // (0.45 with the chunks decoupled through carried state and late pulls) against 0.385, 671-684 against 698-702 views/s.  LDS bank
 // conflicts were NOT the reason (20.0 M against 20.8 M conflict cycles, rocprofv3 --pmc).
 static constexpr int GS_LOG_PAIR_CAP = 790;                                     // + two spare slots (stores of lanes without a candidate land in [790])
-#ifndef GS_LOG_ASSIST_MAX                                         //   + 64 bytes: the pixels of an assisted walk trip
+#ifndef GS_LOG_ASSIST_MAX                                         //   + 4 bytes per assisted pixel: the pixels of an assisted walk trip
 #define GS_LOG_ASSIST_MAX 16                                      // walk trips with at most this many busy pixels are ASSISTED (0: never)
 #endif
+static_assert(GS_LOG_ASSIST_MAX >= 0 && GS_LOG_ASSIST_MAX <= 64, "an assisted trip serves at most the 64 pixels of one wave");
 struct LogLds {
     static constexpr int Q_BYTES = 64 * (16 + 16 + 8 + 4);
     static constexpr int OFF_MSK = Q_BYTES;
     static constexpr int OFF_BASE = OFF_MSK + 64 * 8;
     static constexpr int OFF_PAIR = OFF_BASE + 64 * 4;
     static constexpr int OFF_APIX = OFF_PAIR + (GS_LOG_PAIR_CAP + 2) * 8;
-    static constexpr int WAVE_BYTES = OFF_APIX + 16 * 4;
+    static constexpr int WAVE_BYTES = OFF_APIX + (GS_LOG_ASSIST_MAX > 16 ? GS_LOG_ASSIST_MAX : 16) * 4;
 };
 
 // DPP shift inside a 16-lane row: lane l receives src of lane l - N; lanes whose source lies outside the row receive `ident`
@@ -1339,7 +1343,7 @@ raster_bwd_log_kernel(int W, int H, int tile_w, int n_tiles, int D, const int32_
 #if GS_LOG_ASSIST_MAX > 0
                 // ---- ASSISTED trip.  Half of the walk's trips have at most 16 busy pixels (a third at most 8): the recurrence of
                 // a pixel is sequential, but everything in front of it -- sigma, exp, reciprocal, colour dot, the pair slot: 4/5 of
-                // a candidate's instructions -- is not.  G = 4 (8) lanes serve one busy pixel: helper h takes the pixel's h-th next
+                // a candidate's instructions -- is not.  G = 64 / na lanes (8 at most, a power of two) serve one busy pixel: helper h takes the pixel's h-th next
                 // candidate, the transmittance / accumulator recurrences become two exclusive scans over the G lanes (DPP inside the
                 // row), every helper stores its own pair, and the pixel's lane takes over the state behind the G candidates.
                 // Same candidates in the same order as the plain trips; the products are associated differently (a gradient).
@@ -1348,7 +1352,8 @@ raster_bwd_log_kernel(int W, int H, int tile_w, int n_tiles, int D, const int32_
                     const int na = __popcll(am);
                     // (lists of one or two candidates: a plain trip finishes them for less)
                     if (na <= GS_LOG_ASSIST_MAX && __ballot(__popcll(list) > 2) != 0ull) {
-                        const int gs = na <= 8 ? 3 : 2, G = 1 << gs;
+                        // (GS_LOG_ASSIST_MAX > 16 only: two lanes per pixel up to 32 busy pixels, one up to 64 -- every group must fit the wave)
+                        const int gs = na <= 8 ? 3 : (GS_LOG_ASSIST_MAX <= 16 || na <= 16) ? 2 : na <= 32 ? 1 : 0, G = 1 << gs;
                         const int rank = __popcll(am & lane_lt);
                         lanes_lds_sync();
                         if (list != 0ull) apix[rank] = lane;

@@ -135,6 +135,33 @@ def raster_bwd(W, H, tile_size, means2d, conics, opacities, colors, offsets, fla
     return v_means2d, v_conics, v_colors, v_opac
 
 
+def raster_bwd_budget(W, H, tile_size, means2d, conics, opacities, colors, offsets, flatten_ids, alphas, last_ids,
+                      v_render, v_alphas, background=None, stored_state=False):
+    """raster_bwd plus an error budget per gradient element (gso_raster_bwd_budget): returns
+    ((v_means2d, v_conics, v_colors, v_opacities), (b_means2d, b_conics, b_colors, b_opacities)), the budgets float64 in
+    units of 2^-24.  A correct fp32 implementation of the same backward on the same alphas / last_ids lands within
+    kappa * 2^-24 * budget of the values; stored_state=True widens the budget by the error of that stored state itself
+    (for a comparison with exact arithmetic, e.g. float64 autograd of forward and backward)."""
+    means2d, conics, opacities, colors = _f32(means2d), _f32(conics), _f32(opacities), _f32(colors)
+    V, D = colors.shape
+    assert D <= 64
+    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    flatten_ids = np.ascontiguousarray(flatten_ids, np.int32)
+    alphas = _f32(alphas); last_ids = np.ascontiguousarray(last_ids, np.int32)
+    v_render, v_alphas = _f32(v_render), _f32(v_alphas)
+    bg = None if background is None else _f32(background)
+    v_means2d = np.empty((V, 2), np.float32); v_conics = np.empty((V, 3), np.float32)
+    v_colors = np.empty((V, D), np.float32); v_opac = np.empty(V, np.float32)
+    b_means2d = np.empty((V, 2), np.float64); b_conics = np.empty((V, 3), np.float64)
+    b_colors = np.empty((V, D), np.float64); b_opac = np.empty(V, np.float64)
+    lib().gso_raster_bwd_budget(int(W), int(H), int(tile_size), int(D), _p(means2d), _p(conics), _p(opacities), _p(colors),
+                                _p(bg), C.c_int64(flatten_ids.shape[0]), _p(offsets), _p(flatten_ids), _p(alphas),
+                                _p(last_ids), _p(v_render), _p(v_alphas), int(V),
+                                _p(v_means2d), _p(v_conics), _p(v_colors), _p(v_opac),
+                                _p(b_means2d), _p(b_conics), _p(b_colors), _p(b_opac), int(bool(stored_state)))
+    return (v_means2d, v_conics, v_colors, v_opac), (b_means2d, b_conics, b_colors, b_opac)
+
+
 def project_bwd(means, quats, scales, opacities, viewmat, K, W, H, gaussian_ids, conics, compensations,
                 v_means2d, v_conics, v_opacities_packed, v_colors_packed, v_depths=None, eps2d=0.3):
     means, quats, scales, opacities = _f32(means), _f32(quats), _f32(scales), _f32(opacities)

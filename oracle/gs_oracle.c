@@ -511,6 +511,203 @@ GSO_API void gso_raster_bwd(int W, int H, int tile_size, int D,
 }
 
 /* ------------------------------------------------------------------------- */
+/* A6 with an error budget: the same walk and the same fp32 gradients as gso_raster_bwd, plus one budget per gradient
+ * element (double, in units of the fp32 unit roundoff 2^-24) that bounds how far a correct fp32 implementation of this
+ * stored-state backward may land from these values.  Per pair and component it adds
+ *   magnitude * w        the contribution re-evaluated on absolute values with every difference turned into a sum
+ *                        (a running-error bound: cancellation cannot hide error), times the walk factor
+ *                        w = 1 + sum_j 1/(1 - alpha_j) over the records the pixel has walked back from last_ids up to and
+ *                        including this one (first-order relative error of T rebuilt by division from T_final, and of the
+ *                        buffer recurrence);
+ *   magnitude * 2^24     if opac*vis lies within 2^-16 relative of 1/255 or of the 0.999 clamp: an implementation whose
+ *                        exponential differs by an ulp may take the other branch there, so the pair may be missing or
+ *                        its geometric gradient cut, i.e. wrong by its whole size (such a pair is budgeted even when this
+ *                        walk skips it);
+ *   behind such a pair   the pixel's later pairs carry the effect of that branch on T (relative alpha / (1 - alpha)) and
+ *                        on the buffer (its colour term), also at full size.
+ * A check then reads |got - want| <= kappa * 2^-24 * budget element-wise, with no exceptions.
+ * That bounds implementations that read the SAME stored state (alphas, last_ids).  stored_state != 0 adds the error of that
+ * state against exact arithmetic, for a comparison with a float64 forward-and-backward: the forward's fp32 product for T_final
+ * (w over the whole walk) and the rounding of alphas = 1 - T_final to fp32 (half an ulp of alpha: 0.5 / T_final relative).       */
+#define GSO_EPS_INV 16777216.0                           /* 2^24 */
+#define GSO_NEAR(x, t) (fabs((double)(x) - (double)(t)) <= (double)(t) * (1.0 / 65536.0))
+
+GSO_API void gso_raster_bwd_budget(int W, int H, int tile_size, int D,
+                                   const float* means2d, const float* conics, const float* opacities,
+                                   const float* colors, const float* background,
+                                   int64_t n_isects, const int32_t* offsets, const int32_t* flatten_ids,
+                                   const float* alphas, const int32_t* last_ids,
+                                   const float* v_render, const float* v_alphas, int V,
+                                   float* v_means2d, float* v_conics, float* v_colors, float* v_opacities,
+                                   double* b_means2d, double* b_conics, double* b_colors, double* b_opacities,
+                                   int stored_state)
+{
+    int tw = (W + tile_size - 1) / tile_size, th = (H + tile_size - 1) / tile_size;
+    int n_tiles = tw * th;
+    const int S = 6 + D;                                 /* per Gaussian: [xy(2), conic(3), opacity(1), color(D)] */
+    double* acc = (double*)calloc((size_t)V * (size_t)S + 1, sizeof(double));
+    double* bud = (double*)calloc((size_t)V * (size_t)S + 1, sizeof(double));
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int tile = 0; tile < n_tiles; ++tile) {
+        int ty = tile / tw, tx = tile % tw;
+        int64_t start = offsets[tile];
+        int64_t end = (tile == n_tiles - 1) ? n_isects : offsets[tile + 1];
+        if (end <= start) continue;
+        float buffer[64], vrc[64];
+        double babs[64];
+        for (int i = ty * tile_size; i < (ty + 1) * tile_size && i < H; ++i)
+            for (int j = tx * tile_size; j < (tx + 1) * tile_size && j < W; ++j) {
+                size_t pid = (size_t)i * W + j;
+                float px = (float)j + 0.5f, py = (float)i + 0.5f;
+                float T_final = 1.0f - alphas[pid];
+                float T = T_final;
+                float vra = v_alphas[pid];
+                double bg_abs = 0.0;
+                for (int k = 0; k < D; ++k) {
+                    buffer[k] = 0.0f; babs[k] = 0.0; vrc[k] = v_render[pid * D + k];
+                    if (background) bg_abs += fabs((double)background[k] * (double)vrc[k]);
+                }
+                double wsum = 0.0, amb_rel = 0.0, amb_abs = 0.0, wstate = 0.0;
+                int64_t bin_final = last_ids[pid];
+                if (bin_final >= end) bin_final = end - 1;
+                if (stored_state) {                      /* error of the stored state itself (see the header): a first pass */
+                    for (int64_t idx = bin_final; idx >= start; --idx) {
+                        int g = flatten_ids[idx];
+                        float dx = means2d[2 * g] - px, dy = means2d[2 * g + 1] - py;
+                        float sigma = gso_sigma(conics[3 * g], conics[3 * g + 1], conics[3 * g + 2], dx, dy);
+                        float alpha = fminf(0.999f, opacities[g] * gso_exp_neg(sigma));
+                        if (sigma < 0.0f || alpha < 1.0f / 255.0f) continue;
+                        wstate += 1.0 + 1.0 / (1.0 - (double)alpha);
+                    }
+                    wstate += 0.5 / (double)T_final;
+                }
+                for (int64_t idx = bin_final; idx >= start; --idx) {
+                    int g = flatten_ids[idx];
+                    float ca = conics[3 * g], cb = conics[3 * g + 1], cc = conics[3 * g + 2];
+                    float opac = opacities[g];
+                    float dx = means2d[2 * g] - px, dy = means2d[2 * g + 1] - py;
+                    float sigma = gso_sigma(ca, cb, cc, dx, dy);
+                    float vis = gso_exp_neg(sigma);
+                    float ov = opac * vis;
+                    float alpha = fminf(0.999f, ov);
+                    const int live = !(sigma < 0.0f || alpha < 1.0f / 255.0f);
+                    const int near_lo = sigma >= 0.0f && GSO_NEAR(ov, 1.0f / 255.0f);
+                    const int near_hi = sigma >= 0.0f && GSO_NEAR(ov, 0.999f);
+                    if (!live && !near_lo && !near_hi) continue;
+                    float ra = 1.0f / (1.0f - alpha);
+                    float Tp = T * ra;                   /* this pair's T if it is composited */
+                    const float* col = colors + (size_t)g * D;
+                    double* a = acc + (size_t)g * S;
+                    double* b = bud + (size_t)g * S;
+                    if (live) {                          /* exactly gso_raster_bwd's arithmetic */
+                        T = Tp;
+                        float fac = alpha * T;
+                        float v_alpha = 0.0f;
+                        for (int k = 0; k < D; ++k) {
+                            v_alpha += (col[k] * T - buffer[k] * ra) * vrc[k];
+                            double vc = (double)(fac * vrc[k]);
+#pragma omp atomic
+                            a[6 + k] += vc;
+                        }
+                        v_alpha += T_final * ra * vra;
+                        if (background) {
+                            float accum = 0.0f;
+                            for (int k = 0; k < D; ++k) accum += background[k] * vrc[k];
+                            v_alpha += -T_final * ra * accum;
+                        }
+                        if (opac * vis <= 0.999f) {
+                            float v_sigma = -opac * vis * v_alpha;
+                            double g_ca = (double)(0.5f * v_sigma * dx * dx);
+                            double g_cb = (double)(v_sigma * dx * dy);
+                            double g_cc = (double)(0.5f * v_sigma * dy * dy);
+                            double g_x = (double)(v_sigma * (ca * dx + cb * dy));
+                            double g_y = (double)(v_sigma * (cb * dx + cc * dy));
+                            double g_o = (double)(vis * v_alpha);
+#pragma omp atomic
+                            a[0] += g_x;
+#pragma omp atomic
+                            a[1] += g_y;
+#pragma omp atomic
+                            a[2] += g_ca;
+#pragma omp atomic
+                            a[3] += g_cb;
+#pragma omp atomic
+                            a[4] += g_cc;
+#pragma omp atomic
+                            a[5] += g_o;
+                        }
+                        wsum += (double)ra;
+                    }
+                    /* magnitudes in double: |v_alpha| <= VA, colour terms fac |vrc| */
+                    const double Td = Tp, rad = ra, facd = (double)alpha * Td;
+                    double VA = ((double)T_final * fabs((double)vra) + (double)T_final * bg_abs) * rad;
+                    for (int k = 0; k < D; ++k)
+                        VA += (fabs((double)col[k]) * Td + babs[k] * rad) * fabs((double)vrc[k]);
+                    const double w = live ? 1.0 + wsum + wstate : 0.0;
+                    const double full = (near_lo || near_hi) ? GSO_EPS_INV : 0.0;
+                    /* scale of this pair's own terms, and the absolute v_alpha / colour slack left by branches behind it */
+                    const double sc = w + full;
+                    const double dVA = (amb_rel * VA + rad * amb_abs) * GSO_EPS_INV;
+                    const double dfac = amb_rel * facd * GSO_EPS_INV;
+                    const double adx = fabs((double)dx), ady = fabs((double)dy);
+                    const double gv = fabs((double)ov);  /* |d v_sigma / d v_alpha| */
+                    const double va_tot = VA * sc + dVA;
+                    const double m_x = gv * va_tot * (fabs((double)ca) * adx + fabs((double)cb) * ady);
+                    const double m_y = gv * va_tot * (fabs((double)cb) * adx + fabs((double)cc) * ady);
+                    const double m_a = 0.5 * gv * va_tot * adx * adx;
+                    const double m_b = gv * va_tot * adx * ady;
+                    const double m_c = 0.5 * gv * va_tot * ady * ady;
+                    const double m_o = (double)vis * va_tot;
+#pragma omp atomic
+                    b[0] += m_x;
+#pragma omp atomic
+                    b[1] += m_y;
+#pragma omp atomic
+                    b[2] += m_a;
+#pragma omp atomic
+                    b[3] += m_b;
+#pragma omp atomic
+                    b[4] += m_c;
+#pragma omp atomic
+                    b[5] += m_o;
+                    for (int k = 0; k < D; ++k) {
+                        const double m_k = (facd * sc + dfac) * fabs((double)vrc[k]);
+#pragma omp atomic
+                        b[6 + k] += m_k;
+                    }
+                    if (near_lo) {                       /* the other branch here moves T and the buffer of every later pair */
+                        amb_rel += (double)alpha * rad;
+                        double cv = 0.0;
+                        for (int k = 0; k < D; ++k) cv += fabs((double)col[k] * (double)vrc[k]);
+                        amb_abs += facd * cv;
+                    }
+                    if (live) {
+                        float fac = alpha * T;
+                        for (int k = 0; k < D; ++k) {
+                            buffer[k] += col[k] * fac;
+                            babs[k] += fabs((double)col[k]) * (double)fac;
+                        }
+                    }
+                }
+            }
+    }
+    for (int g = 0; g < V; ++g) {
+        const double* a = acc + (size_t)g * S;
+        const double* b = bud + (size_t)g * S;
+        v_means2d[2 * g] = (float)a[0]; v_means2d[2 * g + 1] = (float)a[1];
+        v_conics[3 * g] = (float)a[2]; v_conics[3 * g + 1] = (float)a[3]; v_conics[3 * g + 2] = (float)a[4];
+        v_opacities[g] = (float)a[5];
+        for (int k = 0; k < D; ++k) v_colors[(size_t)g * D + k] = (float)a[6 + k];
+        b_means2d[2 * g] = b[0]; b_means2d[2 * g + 1] = b[1];
+        b_conics[3 * g] = b[2]; b_conics[3 * g + 1] = b[3]; b_conics[3 * g + 2] = b[4];
+        b_opacities[g] = b[5];
+        for (int k = 0; k < D; ++k) b_colors[(size_t)g * D + k] = b[6 + k];
+    }
+    free(acc);
+    free(bud);
+}
+
+/* ------------------------------------------------------------------------- */
 /* A7: projection backward (gsplat fully_fused_projection_packed_bwd) + the
  * gather backward of A1'.  Inputs are per-visible grads; outputs are DENSE
  * [N,*] (sparse_grad=False at rfstudio/model/gsplat.py:349), zero for culled

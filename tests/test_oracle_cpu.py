@@ -20,6 +20,7 @@ import geosplatting_amd.synthetic as syn
 from oracle import mesh_ref
 from geosplatting_amd import cameras as cam_mod
 from geosplatting_amd import splitsum as ss
+from tests import util
 from tests.util import activated, rel_err, sphere_case
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -377,6 +378,54 @@ def test_oracle_backward_vs_float64_autograd():
     # flat disks (3rd scale e^-10): quats / scales are ill-conditioned -> fp32 noise floor ~1e-4
     assert rel_err(gr["v_quats"], tq.grad.numpy()) < 5e-4
     assert rel_err(gr["v_scales"], ts.grad.numpy()) < 5e-4
+
+
+# the ill-conditioned regimes at CPU size: opacity 1 at the 0.999 clamp in front of a deep stack, walks of hundreds of low-alpha records
+# back from T_final ~ 1e-4, ~1 px speckle, a ragged image with a background
+_BUDGET_CPU_SCENES = dict(deep_stack=lambda: util.deep_stack_scene(W=48, H=48, n=2500),
+                          veil=lambda: util.veil_scene(W=48, H=48, n=1200, n_veil=8),
+                          speckle=lambda: util.speckle_scene(),
+                          ragged=lambda: util.ragged_scene(W=61, H=45, n_heavy=1500, n_light=40))
+
+
+@pytest.mark.parametrize("kind", ["dense", "alpha", "sparse"])
+@pytest.mark.parametrize("scene", list(_BUDGET_CPU_SCENES))
+def test_raster_bwd_budget_vs_float64_autograd(scene, kind):
+    """The error budget of oracle.raster_bwd_budget is honest: the oracle's fp32 compositor gradients lie within
+    (kappa / 2) * 2^-24 * budget of float64 autograd through oracle/torch_ref.py's restatement, element by element -- with the
+    stored-state term, since the float64 side has no fp32 alphas (without it the deep walks are off by up to ~2000 eps * budget:
+    1 - alphas rounded to fp32 at T_final = 1e-4 is 5000 ulp of T_final).  Pixels whose fp32 / float64 forwards take different
+    decisions (oracle `ambiguous`, or T_final off by more than 1e-3) get zero cotangents."""
+    sc = _BUDGET_CPU_SCENES[scene]()
+    W, H, D, bg = sc["W"], sc["H"], 3, sc["background"]
+    m = oracle.rasterization(sc["means"], sc["quats"], sc["scales"], sc["opacities"], util.scene_colors(sc, D), sc["viewmat"], sc["K"],
+                             W, H, background=bg)
+    st = util.raster_pair_stats(W, H, m["means2d"], m["conics"], m["opacities"], m["isect_offsets"], m["flatten_ids"], m["last_ids"])
+    if scene == "veil":
+        assert st["clamped_live"] > 0 and st["max_distinct_last"] >= 8, st
+    if scene in ("deep_stack", "veil", "ragged"):
+        assert float((1.0 - m["alphas"]).min()) < 1.1e-4 and st["max_list"] > 1000, st      # walks back from T_final ~ 1e-4
+    dt = torch.float64
+    leaf = lambda a: torch.tensor(np.asarray(a, np.float64), requires_grad=True)
+    m2d, con, op, col = leaf(m["means2d"]), leaf(m["conics"]), leaf(m["opacities"]), leaf(m["colors"])
+    render, alpha = tr.rasterize(m2d, con, op, col, W, H, 16, torch.tensor(m["isect_offsets"]), torch.tensor(m["flatten_ids"]))
+    if bg is not None:
+        render = render + (1 - alpha)[..., None] * torch.tensor(bg, dtype=dt)
+    t32 = 1.0 - m["alphas"].astype(np.float64)
+    unstable = m["ambiguous"] | (np.abs((1.0 - alpha.detach().numpy()) - t32) > 1e-3 * t32)
+    assert unstable.mean() < 0.02
+    vr, va = util.budget_cotangents(kind, H, W, D, seed=5)
+    vr[unstable] = 0.0; va[unstable] = 0.0
+    ((render * torch.tensor(vr, dtype=dt)).sum() + (alpha * torch.tensor(va, dtype=dt)).sum()).backward()
+    got, bud = oracle.raster_bwd_budget(W, H, 16, m["means2d"], m["conics"], m["opacities"], m["colors"], m["isect_offsets"],
+                                        m["flatten_ids"], m["alphas"], m["last_ids"], vr, va, background=bg, stored_state=True)
+    plain = oracle.raster_bwd(W, H, 16, m["means2d"], m["conics"], m["opacities"], m["colors"], m["isect_offsets"].reshape(-1),
+                              m["flatten_ids"], m["alphas"], m["last_ids"], vr, va, background=bg)
+    print(f"\n  {scene} / {kind}")
+    for name, g, p, want, b in zip(("v_means2d", "v_conics", "v_colors", "v_opacities"), got, plain, (m2d, con, col, op), bud):
+        assert np.array_equal(g, p), name                   # the budget walk computes exactly gso_raster_bwd's gradients
+        assert float(np.abs(want.grad.numpy()).max()) > 0 or kind == "alpha" and name == "v_colors"
+        util.assert_within_budget(name, g, want.grad.numpy(), b, util.BUDGET_KAPPA / 2)
 
 
 @pytest.mark.parametrize("mode", ["pbr", "diffuse", "specular"])
