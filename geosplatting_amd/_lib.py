@@ -47,9 +47,9 @@ SYMBOLS = [
     "gs_cubemap_mip_bwd", "gs_diffuse_cubemap_fwd", "gs_diffuse_cubemap_bwd", "gs_specular_bounds", "gs_specular_bounds_ws_bytes", "gs_specular_bounds_fast", "gs_cube_dir_table",
     "gs_specular_cubemap_fwd", "gs_specular_cubemap_bwd", "gs_specular_tiles_count", "gs_specular_tiles_fill",
     "gs_specular_tiles_check", "gs_specular_tiles_apply", "gs_specular_tiles_apply_multi", "gs_mgadapter_fwd", "gs_mgadapter_bwd", "gs_vertex_normals_fwd",
-    "gs_vertex_normals_bwd", "gs_photo_loss_ws_bytes", "gs_photo_loss", "gs_hashgrid_fwd", "gs_hashgrid_bwd_ws_bytes", "gs_hashgrid_bwd", "gs_hashgrid_bwd_fixed_ws_bytes", "gs_hashgrid_bwd_fixed", "gs_mlp_wgrad_ws_bytes", "gs_mlp_wgrad",
+    "gs_vertex_normals_bwd", "gs_photo_loss_ws_bytes", "gs_photo_loss", "gs_smooth_loss_ws_bytes", "gs_smooth_loss", "gs_hashgrid_fwd", "gs_hashgrid_bwd_ws_bytes", "gs_hashgrid_bwd", "gs_hashgrid_bwd_fixed_ws_bytes", "gs_hashgrid_bwd_fixed", "gs_mlp_wgrad_ws_bytes", "gs_mlp_wgrad",
     "gs_flexicubes_ws_bytes", "gs_flexicubes_count", "gs_flexicubes_fwd", "gs_flexicubes_bwd", "gs_flexicubes_entropy_fwd",
-    "gs_flexicubes_entropy_bwd", "gs_front_ws_bytes", "gs_front_fwd", "gs_isect_bin_front_ws_bytes", "gs_isect_bin_front", "gs_tail_bwd", "gs_tail_bwd_multi", "gs_tail_bwd_multi_parts", "gs_tail_priv_ws_bytes", "gs_tail_priv_reduce", "gs_activation_chain",
+    "gs_flexicubes_entropy_bwd", "gs_front_ws_bytes", "gs_front_fwd", "gs_isect_bin_front_ws_bytes", "gs_isect_bin_front", "gs_tail_bwd", "gs_tail_bwd_multi", "gs_tail_bwd_multi_parts", "gs_tail_priv_ws_bytes", "gs_tail_priv_reduce", "gs_smooth_gather", "gs_smooth_fold", "gs_activation_chain",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
         l.gs_flexicubes_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         l.gs_photo_loss_ws_bytes.restype = C.c_size_t
         l.gs_photo_loss_ws_bytes.argtypes = [C.c_int, C.c_int]
+        l.gs_smooth_loss_ws_bytes.restype = C.c_size_t
+        l.gs_smooth_loss_ws_bytes.argtypes = [C.c_int, C.c_int]
         l.gs_specular_bounds_ws_bytes.restype = C.c_size_t
         l.gs_specular_bounds_ws_bytes.argtypes = [C.c_int]
         l.gs_front_ws_bytes.restype = C.c_size_t

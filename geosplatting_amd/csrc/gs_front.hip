@@ -914,3 +914,64 @@ extern "C" int gs_activation_chain(int64_t N, const float* g_scales_act, const f
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The attribute renders of the smoothing regularisers (rfstudio/model/geosplat.py:881-922) on the view's own binning: the colours of
+// the D = 9 compositor pair in packed-slot order, and its gradient records folded back (include/geosplat_hip.h).  Contraction is off
+// in this file: n * 0.5 + 0.5 rounds twice, as torch's two elementwise launches do.
+__global__ void __launch_bounds__(256)
+smooth_gather_kernel(GsCount vc, const float4* __restrict__ vis, const float* __restrict__ kd, const float* __restrict__ ks,
+                     const float* __restrict__ normals, float* __restrict__ cols)
+{
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= gs_count(vc)) return;
+    const size_t g = (size_t)__float_as_int(vis[4 * s + 3].y);
+    float* c = cols + 9 * s;
+    c[0] = kd[3 * g]; c[1] = kd[3 * g + 1]; c[2] = kd[3 * g + 2];
+    c[3] = 0.0f; c[4] = ks[2 * g]; c[5] = ks[2 * g + 1];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[6 + k] = normals[3 * g + k] * 0.5f + 0.5f;
+}
+
+__global__ void __launch_bounds__(256)
+smooth_fold_kernel(GsCount vc, const float4* __restrict__ vis, const float* __restrict__ v9, int stride9, float* __restrict__ vp,
+                   int stride, float* __restrict__ v_kd, float* __restrict__ v_ks, float* __restrict__ v_normals)
+{
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= gs_count(vc)) return;
+    const size_t g = (size_t)__float_as_int(vis[4 * s + 3].y);
+    const float* a = v9 + (size_t)stride9 * s;
+    float* b = vp + (size_t)stride * s;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] += a[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v_kd[3 * g + k] += a[6 + k];
+    v_ks[2 * g] += a[10]; v_ks[2 * g + 1] += a[11];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v_normals[3 * g + k] += 0.5f * a[12 + k];
+}
+
+extern "C" int gs_smooth_gather(int V_cap, const int64_t* counts_dev, const float* vis_records, const float* kd, const float* ks,
+                                const float* normals, float* cols, void* stream)
+{
+    GS_CHECK_ARG(V_cap >= 0, "bad V_cap");
+    if (V_cap == 0) return GS_OK;
+    GS_CHECK_ARG(vis_records && kd && ks && normals && cols, "null argument");
+    hipLaunchKernelGGL(smooth_gather_kernel, dim3(gs_cdiv(V_cap, 256)), dim3(256), 0, (hipStream_t)stream,
+                       GsCount{ (long long)V_cap, (const long long*)counts_dev }, (const float4*)vis_records, kd, ks, normals, cols);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+extern "C" int gs_smooth_fold(int V_cap, const int64_t* counts_dev, const float* vis_records, const float* v_packed9, int stride9,
+                              float* v_packed, int stride, float* v_kd, float* v_ks, float* v_normals, void* stream)
+{
+    GS_CHECK_ARG(V_cap >= 0 && stride9 >= 6 + 9 && stride >= 6, "bad V_cap or record strides");
+    if (V_cap == 0) return GS_OK;
+    GS_CHECK_ARG(vis_records && v_packed9 && v_packed && v_kd && v_ks && v_normals, "null argument");
+    hipLaunchKernelGGL(smooth_fold_kernel, dim3(gs_cdiv(V_cap, 256)), dim3(256), 0, (hipStream_t)stream,
+                       GsCount{ (long long)V_cap, (const long long*)counts_dev }, (const float4*)vis_records, v_packed9, stride9, v_packed,
+                       stride, v_kd, v_ks, v_normals);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}

@@ -64,6 +64,18 @@ def _auto_tail_schedule(n_views: int):
 
 
 @dataclass
+class Smoothing:
+    """The smoothing regularisers of a fused step (rfstudio/model/geosplat.py:881-922; stage1.train_step_fused builds it from the
+    model).  Per attribute render -- kd, (0, ks), normals * 0.5 + 0.5, all composited over `background` [3] -- a term kind
+    (loss.SMOOTH_NONE / SMOOTH_EDGE / SMOOTH_TV) and its weight, already divided by the global batch size; `gt`: per LOCAL view the
+    ground truth blended over that background [H,W,3] (None when no term is edge-aware)."""
+    kinds: Tuple[int, int, int]
+    weights: Tuple[float, float, float]
+    background: Tensor
+    gt: Optional[Sequence[Tensor]] = None
+
+
+@dataclass
 class _Geometry:
     """What RenderStep._geometry hands to the records and views phases of a step."""
     scales_act: Tensor; opac_act: Tensor                  # the once-per-step exp / sigmoid activations
@@ -85,6 +97,7 @@ class _Views:
     main: Optional[torch.cuda.Stream]                     # the caller's stream (capture_views: set at every replay)
     pstream: Optional[torch.cuda.Stream]                  # the per-Gaussian gradients become final on this stream (None: on main)
     tail_job: Optional[dict]                              # the last tail launch, left to _chunked_tail
+    smooth_grads: Optional[Tuple[Tensor, Tensor, Tensor]] = None   # kd / ks / normal gradients of the smoothing terms, not yet in `b`
     captured: bool = False                                # recorded into a graph: its tensors live in the graph's private pool
 
 
@@ -123,6 +136,8 @@ class RenderStep:
         n_fly = int(os.environ.get("GEOSPLAT_STEPS_IN_FLIGHT", "3"))
         self._max_in_flight = max(1, n_fly)
         self._in_flight = collections.deque() if n_fly > 0 else None     # end-of-step events of the steps the GPU has not finished (None: unbounded)
+        self.last_smoothing_loss = None    # device scalar: the smoothing terms of the last step's local views (__call__(smoothing=...))
+        self.last_attribute_renders = None # with keep_images: that step's attribute renders [H,W,9] per view (tests)
 
     def _prefilter_group(self):
         """A second communicator for the prefilter exchange (25 MB all-reduce + two rounds of small all-gathers), so that it
@@ -238,7 +253,7 @@ class RenderStep:
         return world, sharded
 
     def _views(self, cameras, upstream, all_reduce, keep_images, geo: _Geometry, env: Optional[TextureSplitSum] = None,
-               recs: Optional[Dict[int, F.Front]] = None) -> _Views:
+               recs: Optional[Dict[int, F.Front]] = None, smoothing: Optional[Smoothing] = None) -> _Views:
         """Second phase of a step: the zero fill, the pyramid (`env`: already filtered, capture_views) and every view up to its last
         tail launch.  Same arithmetic as the autograd path, driven directly through the C-ABI: every tail launch ADDS into the flat
         gradient bucket, the exp / sigmoid activations of GSplatter.render_rgba (rfstudio/model/gsplat.py:336-339) are applied once
@@ -249,7 +264,12 @@ class RenderStep:
         record stream: ~22 short kernels, none of which fills the chip), the fronts of consecutive views alternating between them
         (one: 638 views/s, two: 690, three: 655); the caller's stream runs the VALU-bound compositor forward / backward -- the step's
         critical path; a tail stream runs the gradient kernels of the views in batches.  In capacity mode nothing makes the host wait,
-        so the fronts run as far ahead of the compositor as their inputs allow."""
+        so the fronts run as far ahead of the compositor as their inputs allow.
+
+        `smoothing`: after each view's shaded compositor backward, its attribute renders and their regularisers on the main stream
+        (F.smooth_view: the view's own binning, a D = 9 compositor pair, gs_smooth_loss, the fold of its gradient records into the
+        view's v_packed -- ahead of the tail launch that reads it -- and into per-Gaussian kd / ks / normal scratch, which reaches the
+        bucket behind the last tail launch, whose first launch overwrites those rows)."""
         lib = L.lib()
         p = self.p
         dev = p.means.device
@@ -271,8 +291,18 @@ class RenderStep:
         while tex_res[-1] > 16:
             tex_res.append(tex_res[-1] // 2)
         tex_sizes = [6 * tex_res[-1] * tex_res[-1] * 3] + [6 * r * r * 3 for r in tex_res]        # base map, then the levels
-        sc = self.bucket.zero_with_scratch([3 * N, N, sum(tex_sizes)])
+        # (smoothing: kd / ks / normal gradient scratch, the loss scalar and the zero alpha cotangent of the attribute renders)
+        sm_sizes = [3 * N, 2 * N, 3 * N, 1, max([c.width * c.height for c in cameras] + [1])] if smoothing is not None else []
+        sc = self.bucket.zero_with_scratch([3 * N, N, sum(tex_sizes)] + sm_sizes)
         b = self.bucket.unpack()
+        smooth_grads = None
+        self.last_smoothing_loss = self.last_attribute_renders = None
+        if smoothing is not None:
+            smooth_grads = (sc[3].view(N, 3), sc[4].view(N, 2), sc[5].view(N, 3))
+            smooth_loss, zero_alphas = sc[6].view(()), sc[7]
+            bg9 = smoothing.background.detach().to(dev, f32).reshape(3).repeat(3).contiguous()
+            self.last_smoothing_loss = smooth_loss           # sum of the smoothing terms of this step's local views (device scalar)
+            self.last_attribute_renders = [] if keep_images else None   # [H,W,9] per view: kd, (0, ks), normals * 0.5 + 0.5 (tests)
         g_scales_act = sc[0].view(N, 3); g_opac_act = sc[1]
         exposure = p.exposure.detach().reshape(1).contiguous()
         if env is None:
@@ -331,6 +361,8 @@ class RenderStep:
                     F.release_counts4(fr.host_counts)
                 # the packed gradient records of this view, zeroed HERE (front stream, under the compositor of the previous view)
                 state["v_packed"] = torch.zeros(max(V, 1), lib.gs_raster_grad_stride(3), dtype=f32, device=dev)
+                if smoothing is not None:                    # (the D = 9 pair of the smoothing renders: a second set of records)
+                    state["v_packed9"] = torch.zeros(max(V, 1), lib.gs_raster_grad_stride(9), dtype=f32, device=dev)
                 ev = torch.cuda.Event(); ev.record(side)
             for t in state.values():
                 if isinstance(t, torch.Tensor):
@@ -360,6 +392,11 @@ class RenderStep:
             if kev is not None:
                 k3 = torch.cuda.Event(enable_timing=True); k3.record(main)
                 kev.append(("raster_bwd_kernel", k2, k3))
+            if smoothing is not None:                        # (behind the shaded backward: its tile order lives in the same workspace)
+                attr = F.smooth_view(s, V, I, W, H, kd, ks, normals, bg9, None if smoothing.gt is None else smoothing.gt[i],
+                                     smoothing.kinds, smoothing.weights, smooth_loss, zero_alphas, *smooth_grads)
+                if keep_images:
+                    self.last_attribute_renders.append(attr)
             # keep the front streams two views ahead: A(i+2), then B1(i+1) -- AFTER this view's main-stream chain has been enqueued
             # (their ~35 launches cost the host 0.2-0.3 ms; issued first, the compositor stream idled that long per view)
             if i + 2 < n_views:
@@ -382,6 +419,14 @@ class RenderStep:
             if keep_images:
                 images.append(img)
         main.wait_stream(tail)
+        if smooth_grads is not None and tail_job is None:
+            # the smoothing scratch joins the bucket behind the last tail launch (the first one STORES the kd / ks / normal rows) and
+            # ahead of their all-reduce, which starts on pstream (_finish)
+            for name, g in zip(("kd", "ks", "normals"), smooth_grads):
+                b[name].add_(g)
+            if pstream is not None:
+                pstream.wait_stream(main)
+            smooth_grads = None
         if i_cap is not None:                                # the overflow word follows the step to the host, asynchronously
             if torch.cuda.is_current_stream_capturing():      # a replayed graph refreshes ONE pinned buffer; replay.check() reads it
                 if self._status_host is None:
@@ -407,12 +452,12 @@ class RenderStep:
                 for t in (scales_act, opac_act):
                     t.record_stream(pstream)
         return _Views(b, images if keep_images else None, g_base, g_levels, g_flat, env, sharded, world, all_reduce, main, pstream,
-                      tail_job)
+                      tail_job, smooth_grads)
 
-    def _step(self, cameras, upstream, all_reduce, keep_images):
+    def _step(self, cameras, upstream, all_reduce, keep_images, smoothing: Optional[Smoothing] = None):
         """One whole step: geometry (the first view binned under the prefilter), views, _finish."""
         geo = self._geometry(cameras, bin_first=self.prefilter)
-        return self._finish(self._views(cameras, upstream, all_reduce, keep_images, geo))
+        return self._finish(self._views(cameras, upstream, all_reduce, keep_images, geo, smoothing=smoothing))
 
     def _finish(self, ctx: _Views):
         """What follows the views of a step: gradient all-reduce (its per-Gaussian part under the prefilter backward) and the
@@ -488,6 +533,9 @@ class RenderStep:
                 L.check(lib.gs_activation_chain(L.i64(n1 - n0), L.ptr(sl(g_scales_act)), L.ptr(sl(scales_act)), L.ptr(sl(g_opac_act)),
                                                 L.ptr(sl(opac_act)), L.ptr(b["scales"][n0:n1]), L.ptr(b["opacities"][n0:n1]), L.stream()),
                         "gs_activation_chain")
+                if ctx.smooth_grads is not None:              # the smoothing scratch of these rows, behind this chunk's shading half
+                    for name, g in zip(("kd", "ks", "normals"), ctx.smooth_grads):
+                        b[name][n0:n1].add_(g[n0:n1])
                 ev_c = torch.cuda.Event(); ev_c.record(pstream)
             self.bucket.all_reduce_rows(names, n0, n1, after=ev_c)
         if not ctx.captured:                                  # (a captured segment's tensors live in the graph's private pool)
@@ -545,7 +593,8 @@ class RenderStep:
         check.stale = False
         return out, graphs, check
 
-    def capture(self, cameras: List[Camera], upstream: Callable[[int, Tensor], Tensor], keep_images: bool = False):
+    def capture(self, cameras: List[Camera], upstream: Callable[[int, Tensor], Tensor], keep_images: bool = False,
+                smoothing: Optional[Smoothing] = None):
         """One fused step over a FIXED camera list recorded into a HIP graph (torch.cuda.CUDAGraph): possible because in
         capacity mode a step has fixed launch shapes and no host synchronisation.  Returns `replay() -> (grads, images)`:
         the gradients land in this engine's bucket, exactly as after __call__(..., all_reduce=False); the caller reduces
@@ -555,6 +604,8 @@ class RenderStep:
         replay.check() synchronises and returns False if a view exceeded the capacity OR left the depth range of the 24-bit binning
         keys baked into the graph: the graph is then stale (it would keep replaying with clamped keys, i.e. a wrong depth order) --
         call poll_capacity() and capture() AGAIN before the next replay; a replay after a False check() raises."""
+        if smoothing is not None:
+            raise NotImplementedError("the smoothing regularisers run on the eager fused step (__call__), not in a captured graph")
         if not (self.fused and self.mode == "pbr"):
             raise RuntimeError("capture() needs the fused path")
         if self._i_cap is None:
@@ -575,7 +626,7 @@ class RenderStep:
         return replay
 
     def capture_views(self, cameras: List[Camera], upstream: Callable[[int, Tensor], Tensor], all_reduce: bool = True,
-                      keep_images: bool = False):
+                      keep_images: bool = False, smoothing: Optional[Smoothing] = None):
         """The VIEWS of a step -- everything between the pyramid and the texel gradients: shading, projection, binning, compositor,
         tone map, upstream and the whole per-view backward -- recorded into one HIP graph, with the prefilter and every collective
         OUTSIDE of it.  This is the shape BASELINE config 4 needs (one view per GPU): a single view is ~45 launches, 2.3-4.5 ms from
@@ -584,6 +635,8 @@ class RenderStep:
         = prefilter forward (eager, sharded over the ranks when all_reduce and world > 1) -> copy into the graph's pyramid buffers ->
         graph replay -> prefilter backward + all-reduces (eager); same results as __call__.  `upstream` as in capture();
         step.check() as replay.check()."""
+        if smoothing is not None:
+            raise NotImplementedError("the smoothing regularisers run on the eager fused step (__call__), not in a captured graph")
         if not (self.fused and self.mode == "pbr" and self.prefilter):
             raise RuntimeError("capture_views() needs the fused path with the prefilter in the step")
         if self._i_cap is None:
@@ -736,14 +789,17 @@ class RenderStep:
         return ok
 
     def __call__(self, cameras: List[Camera], upstream: Callable[[int, Tensor], Tensor], all_reduce: bool = True,
-                 keep_images: bool = False):
+                 keep_images: bool = False, smoothing: Optional[Smoothing] = None):
         """Forward + backward for `cameras`; `upstream(i, image)` returns d(loss)/d(image) for local view i.
-        Returns (grads dict of views into the flat bucket, images or None)."""
+        Returns (grads dict of views into the flat bucket, images or None).  `smoothing` (fused PBR path only): the smoothing
+        regularisers of the local views join the step -- their gradients are in the bucket, their sum in `last_smoothing_loss`."""
+        if smoothing is not None and not (self.fused and self.mode == "pbr"):
+            raise NotImplementedError("the smoothing regularisers run on the fused PBR step only")
         if self.fused and self.mode == "pbr":
             self._throttle()                                 # first: the step that just left the window has finished, its word is readable
             self.poll_capacity(_internal=True)               # non-blocking: counts / overflow words of the finished steps (an overflow
                                                              # seen here is kept for the caller's next poll_capacity())
-            out = self._step(cameras, upstream, all_reduce, keep_images)
+            out = self._step(cameras, upstream, all_reduce, keep_images, smoothing)
             if self._in_flight is not None:
                 ev = torch.cuda.Event(); ev.record()
                 self._in_flight.append(ev)

@@ -297,6 +297,45 @@ def composite_bwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Te
                                                C.c_size_t(log.numel()), L.stream()), "gs_raster_bwd_tone_log_acc")
 
 
+def smooth_view(state, V: int, I: int, W: int, H: int, kd: Tensor, ks: Tensor, normals: Tensor, bg9: Tensor, gt: Optional[Tensor],
+                kinds, weights, loss: Tensor, zero_alphas: Tensor, g_kd: Tensor, g_ks: Tensor, g_normals: Tensor) -> Tensor:
+    """The smoothing regularisers of one view on its own binning, on the current stream, AFTER the view's shaded compositor backward
+    (rfstudio/model/geosplat.py:881-922: un-shaded renders of kd, (0, ks) and normals * 0.5 + 0.5 over the background): the colours
+    in packed-slot order (gs_smooth_gather), ONE D = 9 compositor pair on the view's prepared workspace (D > 3: the colours come from
+    `cols`, not from the record stream, which holds the shaded ones), the loss (gs_smooth_loss: ADDS to `loss`), and the fold of the
+    D = 9 gradient records (state["v_packed9"], zeroed by the caller) into the view's v_packed and into g_kd / g_ks / g_normals.
+    `zero_alphas`: at least H * W zeros (the renders have no alpha cotangent).  Returns the attribute renders [H,W,9]."""
+    lib = L.lib()
+    dev = kd.device
+    st = L.stream()
+    counts, vis, offsets, rws = state["counts"], state["vis_records"], state["isect_offsets"], state["raster_ws"]
+    cols = torch.empty(max(V, 1), 9, dtype=torch.float32, device=dev)
+    L.check(lib.gs_smooth_gather(V, L.ptr(counts), L.ptr(vis), L.ptr(kd), L.ptr(ks), L.ptr(normals), L.ptr(cols), st), "gs_smooth_gather")
+    render = torch.empty(H, W, 9, dtype=torch.float32, device=dev)
+    alphas = torch.empty(H, W, dtype=torch.float32, device=dev)
+    last_ids = torch.empty(H, W, dtype=torch.int32, device=dev)
+    if counts is None:
+        L.check(lib.gs_raster_composite(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(offsets), L.ptr(render), L.ptr(alphas),
+                                        L.ptr(last_ids), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_composite")
+    else:
+        L.check(lib.gs_raster_composite_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(counts), L.ptr(offsets), L.ptr(render),
+                                            L.ptr(alphas), L.ptr(last_ids), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_composite_cap")
+    from .loss import smooth_loss_and_grad
+    _, v_img = smooth_loss_and_grad(render, gt, kinds, weights, out=loss)
+    v9 = state["v_packed9"]
+    if counts is None:
+        L.check(lib.gs_raster_bwd_acc(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(offsets), L.ptr(alphas), L.ptr(last_ids),
+                                      L.ptr(v_img), L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_bwd_acc")
+    else:
+        L.check(lib.gs_raster_bwd_acc_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(counts), L.ptr(offsets), L.ptr(alphas),
+                                          L.ptr(last_ids), L.ptr(v_img), L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), C.c_size_t(rws.numel()),
+                                          st), "gs_raster_bwd_acc_cap")
+    vp = state["v_packed"]
+    L.check(lib.gs_smooth_fold(V, L.ptr(counts), L.ptr(vis), L.ptr(v9), int(v9.shape[1]), L.ptr(vp), int(vp.shape[1]), L.ptr(g_kd),
+                               L.ptr(g_ks), L.ptr(g_normals), st), "gs_smooth_fold")
+    return render
+
+
 def tail_schedule(default):
     """Views per tail launch of a backward pass, the last entry repeating: GEOSPLAT_TAIL_BATCH ("3,4,1"), or `default` ("auto")."""
     tb = os.environ.get("GEOSPLAT_TAIL_BATCH", "auto")

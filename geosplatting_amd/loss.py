@@ -104,3 +104,34 @@ class TrainerUpstream:
 
     def mean_loss(self) -> Tensor:
         return self.out[:, 0].sum() * self.scale
+
+
+SMOOTH_NONE, SMOOTH_EDGE, SMOOTH_TV = 0, 1, 2          # GS_SMOOTH_* of include/geosplat_hip.h
+
+
+def smooth_loss_and_grad(img: Tensor, gt_rgb: Optional[Tensor], kinds, weights, out: Optional[Tensor] = None,
+                         v_img: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The smoothing regularisers of one view (csrc/gs_smooth.hip; stage1._edge_aware / stage1._tv): img [H,W,9] = the kd, (0, ks)
+    and normal * 0.5 + 0.5 renders over the background, gt_rgb [H,W,3] the blended ground truth (None without an edge-aware term),
+    kinds / weights: three each (SMOOTH_NONE / SMOOTH_EDGE / SMOOTH_TV and the weight of that render).  ADDS the weighted sum to
+    `out` (a device scalar, zeros if None) and writes d(sum)/d(img) into `v_img`; returns (out, v_img)."""
+    _lib.require_cuda(img, gt_rgb)
+    H, W = img.shape[0], img.shape[1]
+    if img.shape != (H, W, 9) or (gt_rgb is not None and gt_rgb.shape != (H, W, 3)):
+        raise _lib.GeoSplatHipError("smooth_loss expects img[H,W,9] and gt_rgb[H,W,3]")
+    if len(kinds) != 3 or len(weights) != 3:
+        raise _lib.GeoSplatHipError("smooth_loss expects three term kinds and three weights")
+    img = img.detach().contiguous().float()
+    gt = None if gt_rgb is None else gt_rgb.detach().contiguous().float()
+    if out is None:
+        out = torch.zeros((), device=img.device)
+    if v_img is None:
+        v_img = torch.empty_like(img)
+    l = _lib.lib()
+    nbytes = l.gs_smooth_loss_ws_bytes(W, H)
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=img.device)
+    k = (C.c_int * 3)(*[int(x) for x in kinds])
+    w = (C.c_float * 3)(*[float(x) for x in weights])
+    _lib.check(l.gs_smooth_loss(W, H, _lib.ptr(img), _lib.ptr(gt), k, w, _lib.ptr(out), _lib.ptr(v_img), _lib.ptr(ws),
+                                C.c_size_t(nbytes), _lib.stream()), "gs_smooth_loss")
+    return out, v_img

@@ -10,9 +10,10 @@ mean over the views, plus the regulariser.
 Data parallel (one process per GPU): every rank holds the same parameters, extracts the same mesh, renders ITS views
 (`views[rank::world_size]`), and the gradients of all parameters travel as ONE flat fp32 all-reduce (RCCL over xGMI).
 With the loss normalised by the global view count and the regulariser by the world size, the reduced gradient is the
-single-process gradient.  `smooth_type` 'jitter' (the reference's default) runs on the fused engine too; the 'grad' / 'tv'
-branches and `normal_grad_weight` of render_report (:881-922: extra un-shaded renders of kd / ks / normals, kornia's
-`spatial_gradient` restated below -- kornia is absent, so that one function is unpinned) run on the autograd step.  The stage hand-off files are: `export_model`
+single-process gradient.  Every `smooth_type` runs on the fused engine too: 'jitter' (the reference's default) in the field, the
+'grad' / 'tv' branches and `normal_grad_weight` of render_report (:881-922: un-shaded renders of kd / ks / normals, kornia's
+`spatial_gradient` restated below -- kornia is absent, so that one function is unpinned) as `engine.Smoothing` (one D = 9 compositor
+pair per view on the view's own binning, csrc/gs_smooth.hip).  The stage hand-off files are: `export_model`
 (:839-854, the dict stage 2 loads), `state_dict` with the reference's names and `<step:010d>.ckpt` checkpoints
 (rfstudio/engine/train.py:172-190).
 """
@@ -357,6 +358,29 @@ class GeoSplatSchedule:
             model.cubemap.clamp_min_(self.cubemap_floor)
 
 
+def smoothing_terms(model: Stage1Model, gt_rgba: Optional[Sequence[Tensor]], batch_size: int):
+    """`engine.Smoothing` of `Stage1Model.smoothing_regularization` for the views whose ground truth is `gt_rgba` (None when no term is
+    active): per render (kd, (0, ks), normals * 0.5 + 0.5) edge-aware under 'grad' and for the normals, TV under 'tv', a weight of 0
+    skips the term; weights / batch_size (the views of the whole step); the ground truth blended over the background as there."""
+    from .engine import Smoothing
+    from .loss import SMOOTH_EDGE, SMOOTH_NONE, SMOOTH_TV
+    kind = {"grad": SMOOTH_EDGE, "tv": SMOOTH_TV}.get(model.smooth_type, SMOOTH_NONE)
+    kinds = [kind if model.kd_grad_weight > 0 else SMOOTH_NONE, kind if model.ks_grad_weight > 0 else SMOOTH_NONE,
+             SMOOTH_EDGE if model.normal_grad_weight > 0 else SMOOTH_NONE]
+    weights = [model.kd_grad_weight, model.ks_grad_weight, model.normal_grad_weight]
+    weights = [w / batch_size if k != SMOOTH_NONE else 0.0 for k, w in zip(kinds, weights)]
+    if all(k == SMOOTH_NONE for k in kinds):
+        return None
+    bg = model.background_color
+    gts = None
+    if SMOOTH_EDGE in kinds:
+        if gt_rgba is None:
+            raise ValueError("smooth_type='grad' / normal_grad_weight need the ground-truth images (gt_outputs.blend(background))")
+        with torch.no_grad():
+            gts = [(g[..., :3] * g[..., 3:] + bg * (1 - g[..., 3:])).contiguous() for g in gt_rgba]     # RGBAImages.blend
+    return Smoothing(tuple(kinds), tuple(weights), bg.detach(), gts)
+
+
 def train_step_fused(model: Stage1Model, cameras: Sequence[Camera], gt_rgba: Sequence[Tensor], *, gt_is_srgb: bool = True,
                      use_mask_loss: bool = True, rank: int = 0, world_size: int = 1, seed: int = 0,
                      train_bg: Optional[Sequence[Tensor]] = None) -> Dict[str, Tensor]:
@@ -366,13 +390,13 @@ def train_step_fused(model: Stage1Model, cameras: Sequence[Camera], gt_rgba: Seq
     runs the same field / MGAdapter / FlexiCubes backward: no second collective.  Replicas must start identical
     (`broadcast_parameters`) and stay so: the backward kernels behind the cut use fp32 atomics, so callers re-broadcast
     every few hundred steps (`_main`: every 200); the Gaussian count is checked across ranks before every
-    collective (a topology that differs on one rank would otherwise reduce buffers of different sizes)."""
+    collective (a topology that differs on one rank would otherwise reduce buffers of different sizes).  The smoothing
+    regularisers (smooth_type 'grad' / 'tv', normal_grad_weight) run inside the engine's step (`smoothing_terms`); their value, a
+    per-rank term as in `train_step`, is `model._last_smoothing` and part of the returned regularisation."""
     from .engine import PathParams, RenderStep
     from .loss import TrainerUpstream
     n_total = len(cameras)
     mine = list(range(rank, n_total, world_size))
-    if model.smooth_type != "jitter" or model.normal_grad_weight > 0:
-        raise NotImplementedError("the 'grad' / 'tv' / normal smoothing renders run on the autograd step (train_step)")
     params = model.parameters()
     for p in params:
         p.grad = None
@@ -392,11 +416,12 @@ def train_step_fused(model: Stage1Model, cameras: Sequence[Camera], gt_rgba: Seq
     up = TrainerUpstream([gt_rgba[i] for i in mine], n_total, gt_is_srgb=gt_is_srgb, use_mask_loss=use_mask_loss,
                          train_bg=None if train_bg is None else [train_bg[i] for i in mine],
                          generator=model.bg_generator(rank), device=splats.means.device)   # `mine` may be empty (world > views)
+    smoothing = smoothing_terms(model, [gt_rgba[i] for i in mine], n_total) if mine else None
     # capacity protocol (engine.RenderStep.poll_capacity): the step runs without (V, I) read-backs; a view that outgrew the
     # intersection capacity (the extracted surface changes every iteration) is reported afterwards and the step repeated with
     # the raised capacity -- collectively, since the per-Gaussian gradients were already reduced over the ranks
     for attempt in range(4):
-        g, _ = step([cameras[i] for i in mine], up, all_reduce=world_size > 1)
+        g, _ = step([cameras[i] for i in mine], up, all_reduce=world_size > 1, smoothing=smoothing)
         ok = step.poll_capacity(wait=True)
         if world_size > 1:
             flag = torch.tensor([0.0 if ok else 1.0], device=splats.means.device)
@@ -409,6 +434,8 @@ def train_step_fused(model: Stage1Model, cameras: Sequence[Camera], gt_rgba: Seq
                              generator=model.bg_generator(rank), device=splats.means.device)
     else:
         raise RuntimeError("intersection capacity still exceeded after 4 attempts")
+    # per-view terms of THIS rank's views (already / n_total): not replicated across ranks, as in train_step
+    model._last_smoothing = step.last_smoothing_loss.clone() if smoothing is not None else reg.new_zeros(())
     heads = cut + [exposure]
     gh = [g["means"], g["scales"], g["quats"], g["opacities"], g["normals"], g["kd"], g["ks"], g["exposure"].reshape(1)]
     keep = [(h, gg) for h, gg in zip(heads, gh) if h.requires_grad]
@@ -417,7 +444,7 @@ def train_step_fused(model: Stage1Model, cameras: Sequence[Camera], gt_rgba: Seq
     for p in params:
         if p.grad is None:
             p.grad = torch.zeros_like(p)
-    return {"loss_local_views": up.mean_loss() * (n_total / max(1, len(mine))), "regularization": reg.detach(),
+    return {"loss_local_views": up.mean_loss() * (n_total / max(1, len(mine))), "regularization": reg.detach() + model._last_smoothing,
             "#gaussians": torch.tensor(splats.means.shape[0]), "exposure": exposure.detach().mean()}
 
 
@@ -507,7 +534,13 @@ def _main() -> None:
     dev = torch.device("cuda", local)
     if world > 1:
         dist.init_process_group("nccl", rank=rank, world_size=world)
-    iters = next((int(a) for a in sys.argv[1:] if a.isdigit()), 20)      # [iters] [--autograd]
+    argv = sys.argv[1:]                                      # [iters] [--autograd] [--smooth grad|tv] [--normal-weight W]
+    values = {i + 1 for i, a in enumerate(argv) if a in ("--smooth", "--normal-weight")}
+    iters = next((int(a) for i, a in enumerate(argv) if a.isdigit() and i not in values), 20)
+    smooth = argv[argv.index("--smooth") + 1] if "--smooth" in argv else None
+    normal_w = float(argv[argv.index("--normal-weight") + 1]) if "--normal-weight" in argv else (0.5 if smooth else 0.0)
+    if smooth not in (None, "grad", "tv"):
+        raise SystemExit("--smooth takes 'grad' or 'tv'")
     R, HW, n_views = 64, 256, max(8, world)
     cams = syn.blender_cameras(n_views, HW, HW)
     grid = FlexiCubes.from_resolution(R, device=dev, random_sdf=False, scale=1.05)
@@ -524,6 +557,9 @@ def _main() -> None:
     model = Stage1Model(R, light_resolution=128, device=dev, log2_hashmap_size=16,
                         sdf_init=grid.vertices.norm(dim=-1, keepdim=True) - 0.5)
     model.sdf_weight = 0.1
+    if smooth is not None:                                   # the smoothing regularisers on (GeoSplatSchedule's end weights)
+        model.smooth_type, model.kd_grad_weight, model.ks_grad_weight = smooth, 0.03, 0.001
+    model.normal_grad_weight = normal_w
     opt = torch.optim.Adam(model.parameters(), lr=5e-3)
     resync = 200
     if world > 1:
@@ -543,7 +579,9 @@ def _main() -> None:
                   f"#gaussians {int(m['#gaussians'])}", flush=True)
     torch.cuda.synchronize()
     if rank == 0 and t0 is not None and iters > 2:
-        print(f"{(time.time() - t0) / (iters - 2) * 1e3:.1f} ms per iteration ({n_views} views of {HW}x{HW}, grid {R}^3, {world} rank(s))")
+        what = f", smooth_type {model.smooth_type}, normal weight {model.normal_grad_weight:g}" if (smooth or normal_w > 0) else ""
+        print(f"{(time.time() - t0) / (iters - 2) * 1e3:.1f} ms per iteration ({n_views} views of {HW}x{HW}, grid {R}^3, {world} rank(s), "
+              f"{'autograd' if '--autograd' in sys.argv else 'fused'} step{what})")
     if world > 1:
         dist.destroy_process_group()
 

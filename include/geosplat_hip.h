@@ -59,6 +59,11 @@ extern "C" {
 #define GS_TONE_NAIVE    1
 #define GS_TONE_ACES     2
 
+/* term kinds of gs_smooth_loss */
+#define GS_SMOOTH_NONE   0
+#define GS_SMOOTH_EDGE   1
+#define GS_SMOOTH_TV     2
+
 const char* gs_last_error(void);
 int         gs_version(void);
 
@@ -473,6 +478,19 @@ int gs_photo_loss(int W, int H, const float* rgb, const float* alpha, const floa
                   const float* train_bg, const float* metric_bg, float ssim_lambda, float mask_weight,
                   float grad_scale, float* out, float* v_rgb, float* v_alpha, void* ws, size_t ws_bytes, void* stream);
 
+/* The smoothing regularisers of the stage-1 trainer (rfstudio/model/geosplat.py:881-922; geosplatting_amd/stage1.py _edge_aware /
+ * _tv) on the un-shaded attribute renders of one view, value AND gradient in one call:
+ *   img[H,W,9]: three renders over the background, channel order kd(3), (0, ks)(3), normal * 0.5 + 0.5 (3);
+ *   gt_rgb[H,W,3]: the ground truth blended over the background (NULL when no term is GS_SMOOTH_EDGE);
+ *   kinds[3], weights[3] (host): per render GS_SMOOTH_NONE, GS_SMOOTH_EDGE = (|S(r)| exp(-|S(gt)|)).sum(dir).mean() with S the
+ *     normalised Sobel pair (kernel / 8, replicate padding, cross-correlation), or GS_SMOOTH_TV = the two mean squared forward
+ *     differences, times its weight.
+ *   *out (device) += the weighted sum (fixed-order reduction in double: deterministic);  v_img[H,W,9] = d out / d img (written;
+ *   0 in the channels of a render without a term).  W, H >= 2; ws: gs_smooth_loss_ws_bytes(W, H) bytes. */
+size_t gs_smooth_loss_ws_bytes(int W, int H);
+int gs_smooth_loss(int W, int H, const float* img, const float* gt_rgb, const int* kinds, const float* weights, float* out,
+                   float* v_img, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ F1: hash-grid encoding --------- */
 /* HashEncoding, `backend='torch'` semantics (rfstudio/model/components/encoding.py:187-229): every level hashed,
  * x in [-1,1]^3 -> x/2+1/2, scalings[l] = floor(min_res * growth^l) (host array of L floats, computed by the caller
@@ -621,6 +639,18 @@ int gs_tail_priv_reduce(const GsEnv* env /*host*/, int mode, const void* priv_ws
 /* Chain rule of the per-step activations of GSplatter.render_rgba (rfstudio/model/gsplat.py:336-339: `scales.exp()`,
  * `sigmoid(opacities)`) applied once to gradients accumulated over the views of a step:
  *   v_scales[N,3] = g_scales_act * scales_act,   v_opacities[N] = (g_opac_act * opac_act) * (1 - opac_act). */
+/* The attribute renders of the smoothing regularisers on a view the engine has binned (gs_front_fwd's packed slots), D = 9:
+ *   gs_smooth_gather: cols[slot, 9] = (kd, 0, ks0, ks1, normal * 0.5 + 0.5) of the Gaussian of every visible slot (its index is in
+ *     the slot's vis_records entry) -- the colours gs_raster_composite*(D = 9) reads;
+ *   gs_smooth_fold: the compositor's D = 9 gradient records v_packed9 [V, stride9] of the same view: their geometry floats [0..5]
+ *     are ADDED to the shaded view's v_packed [V, stride] (same slots), their colour floats to the per-Gaussian v_kd [N,3], v_ks [N,2]
+ *     (channel 0 of (0, ks) dropped) and v_normals [N,3] (times 0.5).  Plain read-modify-write: the folds of a step run on one stream.
+ * counts_dev == NULL: V_cap is the count; else {V, I} on the device (capacity protocol). */
+int gs_smooth_gather(int V_cap, const int64_t* counts_dev, const float* vis_records, const float* kd, const float* ks,
+                     const float* normals, float* cols, void* stream);
+int gs_smooth_fold(int V_cap, const int64_t* counts_dev, const float* vis_records, const float* v_packed9, int stride9, float* v_packed,
+                   int stride, float* v_kd, float* v_ks, float* v_normals, void* stream);
+
 int gs_activation_chain(int64_t N, const float* g_scales_act, const float* scales_act, const float* g_opac_act, const float* opac_act,
                         float* v_scales, float* v_opacities, void* stream);
 
