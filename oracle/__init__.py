@@ -163,7 +163,9 @@ def raster_bwd_budget(W, H, tile_size, means2d, conics, opacities, colors, offse
 
 
 def project_bwd(means, quats, scales, opacities, viewmat, K, W, H, gaussian_ids, conics, compensations,
-                v_means2d, v_conics, v_opacities_packed, v_colors_packed, v_depths=None, eps2d=0.3):
+                v_means2d, v_conics, v_opacities_packed, v_colors_packed, v_depths=None, eps2d=0.3, classic=False):
+    """A7 + the gather backward.  classic=True: gsplat's rasterize_mode='classic' (gs_project_bwd_ex with GS_PROJ_CLASSIC):
+    v_opacities = v_opacities_packed and the compensation contributes nothing to the covariance."""
     means, quats, scales, opacities = _f32(means), _f32(quats), _f32(scales), _f32(opacities)
     viewmat, K = _f32(viewmat).reshape(4, 4), _f32(K).reshape(3, 3)
     gids = np.ascontiguousarray(gaussian_ids, np.int32)
@@ -174,11 +176,40 @@ def project_bwd(means, quats, scales, opacities, viewmat, K, W, H, gaussian_ids,
     N, V, D = means.shape[0], gids.shape[0], v_col.shape[1]
     g_means = np.empty((N, 3), np.float32); g_quats = np.empty((N, 4), np.float32)
     g_scales = np.empty((N, 3), np.float32); g_opac = np.empty(N, np.float32); g_colors = np.empty((N, D), np.float32)
-    lib().gso_project_bwd(int(N), int(V), int(D), _p(means), _p(quats), _p(scales), _p(opacities), _p(viewmat), _p(K),
-                          int(W), int(H), _fl(eps2d), _p(gids), _p(conics), _p(comps), _p(v_means2d), _p(vd),
-                          _p(v_conics), _p(v_op), _p(v_col),
-                          _p(g_means), _p(g_quats), _p(g_scales), _p(g_opac), _p(g_colors))
+    lib().gso_project_bwd_ex(int(N), int(V), int(D), _p(means), _p(quats), _p(scales), _p(opacities), _p(viewmat), _p(K),
+                             int(W), int(H), _fl(eps2d), _p(gids), _p(conics), _p(comps), _p(v_means2d), _p(vd),
+                             _p(v_conics), _p(v_op), _p(v_col), int(bool(classic)),
+                             _p(g_means), _p(g_quats), _p(g_scales), _p(g_opac), _p(g_colors))
     return g_means, g_quats, g_scales, g_opac, g_colors
+
+
+def project_bwd_budget(means, quats, scales, opacities, viewmat, K, W, H, gaussian_ids, conics, compensations,
+                       v_means2d, v_conics, v_opacities_packed, v_depths=None, eps2d=0.3, classic=False, stored_state=False):
+    """project_bwd's gradients (bit for bit) plus an error budget per element (gso_project_bwd_budget): returns
+    ((v_means [N,3], v_quats [N,4], v_scales [N,3], v_opacities [N]), (b_means, b_quats, b_scales, b_opacities)), the budgets
+    float64 in units of 2^-24: a running-error bound of the whole backward, the recomputed forward intermediates included.  A
+    correct fp32 implementation that reads the same stored conics / compensations lands within kappa * 2^-24 * budget of the
+    values; culled Gaussians have gradient 0 and budget 0.  stored_state=True widens the budget by the error of the stored fp32
+    conics and compensations themselves (for a comparison with exact arithmetic, e.g. float64 autograd of forward and backward)."""
+    means, quats, scales, opacities = _f32(means), _f32(quats), _f32(scales), _f32(opacities)
+    viewmat, K = _f32(viewmat).reshape(4, 4), _f32(K).reshape(3, 3)
+    gids = np.ascontiguousarray(gaussian_ids, np.int32)
+    conics, comps = _f32(conics), _f32(compensations)
+    v_means2d, v_conics, v_op = _f32(v_means2d), _f32(v_conics), _f32(v_opacities_packed)
+    vd = None if v_depths is None else _f32(v_depths)
+    N, V = means.shape[0], gids.shape[0]
+    assert conics.shape == (V, 3) and comps.shape == (V,) and v_means2d.shape == (V, 2) and v_conics.shape == (V, 3) and v_op.shape == (V,)
+    assert vd is None or vd.shape == (V,)
+    g_means = np.empty((N, 3), np.float32); g_quats = np.empty((N, 4), np.float32)
+    g_scales = np.empty((N, 3), np.float32); g_opac = np.empty(N, np.float32)
+    b_means = np.empty((N, 3), np.float64); b_quats = np.empty((N, 4), np.float64)
+    b_scales = np.empty((N, 3), np.float64); b_opac = np.empty(N, np.float64)
+    lib().gso_project_bwd_budget(int(N), int(V), _p(means), _p(quats), _p(scales), _p(opacities), _p(viewmat), _p(K),
+                                 int(W), int(H), _fl(eps2d), _p(gids), _p(conics), _p(comps), _p(v_means2d), _p(vd),
+                                 _p(v_conics), _p(v_op), int(bool(classic)),
+                                 _p(g_means), _p(g_quats), _p(g_scales), _p(g_opac),
+                                 _p(b_means), _p(b_quats), _p(b_scales), _p(b_opac), int(bool(stored_state)))
+    return (g_means, g_quats, g_scales, g_opac), (b_means, b_quats, b_scales, b_opac)
 
 
 def rasterization(means, quats, scales, opacities, colors, viewmat, K, W, H, tile_size=16,

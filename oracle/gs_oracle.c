@@ -712,33 +712,252 @@ GSO_API void gso_raster_bwd_budget(int W, int H, int tile_size, int D,
  * gather backward of A1'.  Inputs are per-visible grads; outputs are DENSE
  * [N,*] (sparse_grad=False at rfstudio/model/gsplat.py:349), zero for culled
  * Gaussians.  v_opacities_packed / v_colors_packed are grads w.r.t. the
- * packed (opacity*compensation) and packed colors.                           */
-GSO_API void gso_project_bwd(int N, int V, int D,
-                             const float* means, const float* quats, const float* scales, const float* opacities,
-                             const float* viewmat, const float* K, int W, int H, float eps2d,
-                             const int32_t* gaussian_ids, const float* conics, const float* compensations,
-                             const float* v_means2d, const float* v_depths /*nullable*/, const float* v_conics,
-                             const float* v_opacities_packed, const float* v_colors_packed,
-                             float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors)
+ * packed (opacity*compensation) and packed colors.
+ *
+ * classic != 0: gsplat's rasterize_mode='classic' (gs_project_bwd_ex with GS_PROJ_CLASSIC): the packed opacity was
+ * opacities[n] itself, so v_opacities = v_opacity_packed and the compensation contributes nothing to the covariance --
+ * the statements below with comp = 1 and opacity = 0.                          */
+
+/* Running-error arithmetic of the budget (gso_project_bwd_budget): a value (double) and a bound `e` of the absolute error
+ * an fp32 evaluation of it may carry, in units of the fp32 unit roundoff 2^-24.  Every operation propagates the errors of
+ * its operands to first order (plus the second-order product term) and adds one rounding of its own, sized by the
+ * ABSOLUTE values of the operands: a sum or difference a +- b is charged |a| + |b|, not |a +- b|, so cancellation cannot
+ * hide error, and an implementation that sums in another order, contracts a product into the sum or uses a
+ * one-ulp reciprocal stays within a small multiple of the bound.  Exact inputs carry e = 0; products with an exact zero stay
+ * exactly zero with e = 0 (a Gaussian whose cotangents are all zero gets budget 0).                                        */
+typedef struct { double v, e; } gso_ev;
+#define GSO_EPS (1.0 / 16777216.0)                      /* 2^-24 */
+static inline double ev_me(double m, double e) { return m == 0.0 || e == 0.0 ? 0.0 : m * e; }      /* magnitude * error, 0 * inf = 0 */
+static inline gso_ev ev_in(double v) { gso_ev r = { v, 0.0 }; return r; }
+static inline gso_ev ev_err(double v, double e) { gso_ev r = { v, e }; return r; }
+static inline gso_ev ev_scale(gso_ev a, double c) { gso_ev r = { a.v * c, ev_me(fabs(c), a.e) }; return r; }   /* exact factor (+-1, 2, 0.5) */
+static inline gso_ev ev_mul(gso_ev a, gso_ev b)
 {
-    gso_cam cam; cam_from(viewmat, K, W, H, &cam);
-    memset(v_means, 0, sizeof(float) * 3 * (size_t)N);
-    memset(v_quats, 0, sizeof(float) * 4 * (size_t)N);
-    memset(v_scales, 0, sizeof(float) * 3 * (size_t)N);
-    memset(v_opacities, 0, sizeof(float) * (size_t)N);
-    memset(v_colors, 0, sizeof(float) * (size_t)D * (size_t)N);
-#pragma omp parallel for schedule(static)
-    for (int v = 0; v < V; ++v) {
-        int n = gaussian_ids[v];
-        const float* mean = means + 3 * (size_t)n;
-        const float* quat = quats + 4 * (size_t)n;
-        const float* scale = scales + 3 * (size_t)n;
-        /* A1' backward: opac_packed = opac[n] * comp ; colors_packed = colors[n] */
-        float comp = compensations[v];
-        float v_op = v_opacities_packed[v];
-        v_opacities[n] = v_op * comp;
-        float v_comp = v_op * opacities[n];
-        for (int k = 0; k < D; ++k) v_colors[(size_t)n * D + k] = v_colors_packed[(size_t)v * D + k];
+    gso_ev r; r.v = a.v * b.v;
+    if ((a.v == 0.0 && a.e == 0.0) || (b.v == 0.0 && b.e == 0.0)) { r.e = 0.0; return r; }      /* an exact zero (0 * inf stays out) */
+    r.e = ev_me(fabs(a.v), b.e) + ev_me(fabs(b.v), a.e) + ev_me(a.e, b.e) * GSO_EPS + fabs(r.v);
+    return r;
+}
+static inline gso_ev ev_add(gso_ev a, gso_ev b)
+{
+    gso_ev r; r.v = a.v + b.v;
+    r.e = a.e + b.e + ((a.v == 0.0 && a.e == 0.0) || (b.v == 0.0 && b.e == 0.0) ? 0.0 : fabs(a.v) + fabs(b.v));
+    return r;
+}
+static inline gso_ev ev_sub(gso_ev a, gso_ev b) { return ev_add(a, ev_scale(b, -1.0)); }
+static inline gso_ev ev_div(gso_ev a, gso_ev b)
+{
+    gso_ev r; r.v = a.v / b.v;
+    if (a.v == 0.0 && a.e == 0.0) { r.e = 0.0; return r; }
+    const double den = fabs(b.v) - b.e * GSO_EPS;       /* the smallest the divisor may be */
+    r.e = den > 0.0 ? (a.e + ev_me(fabs(r.v), b.e)) / den + fabs(r.v) : INFINITY;
+    return r;
+}
+static inline gso_ev ev_sqrt(gso_ev a)                  /* a.v >= 0; not first order: the argument may be as uncertain as it is large */
+{
+    gso_ev r; r.v = sqrt(a.v);
+    const double E = a.e * GSO_EPS, lo = a.v > E ? a.v - E : 0.0;
+    const double up = sqrt(a.v + E) - r.v, dn = r.v - sqrt(lo);
+    r.e = (up > dn ? up : dn) / GSO_EPS + r.v;
+    return r;
+}
+static inline gso_ev ev_dot2(gso_ev a0, gso_ev b0, gso_ev a1, gso_ev b1) { return ev_add(ev_mul(a0, b0), ev_mul(a1, b1)); }
+static inline gso_ev ev_dot3(gso_ev a0, gso_ev b0, gso_ev a1, gso_ev b1, gso_ev a2, gso_ev b2)
+{
+    return ev_add(ev_dot2(a0, b0, a1, b1), ev_mul(a2, b2));
+}
+static inline gso_ev ev_clamp(gso_ev x, gso_ev lo, gso_ev hi) { return x.v > hi.v ? hi : (x.v < lo.v ? lo : x); }
+
+/* The budget of one Gaussian: the statements of project_bwd_gauss (and of project_one for the recomputed forward
+ * intermediates mean_c, Rq, M, covar, covar_c, the clamp limits, tx, ty and J) once more in the running-error arithmetic.
+ * The stored conic (ia, ib, ic) and compensation are exact inputs unless stored_state != 0: then they carry the error the
+ * fp32 forward gave them against exact arithmetic (the cancellation in det = c00 c11 - c01 c10 and in det_orig, and
+ * sqrt(det_orig / det) near 0 and near 1), measured against a double evaluation of the same forward, and v_sqr_comp carries
+ * what gsplat's regularised 0.5 / (comp + 1e-6) at the stored compensation differs from the derivative of the square root at
+ * the exact one.  The budget is finite for every Gaussian whose exact compensation is not 0. */
+static void project_bwd_budget_gauss(const gso_cam* cam, int W, int H, float eps2d_f, const float* mean, const float* quat,
+                                     const float* scale, float opacity, float ia_f, float ib_f, float ic_f, float comp_f,
+                                     float vm2x_f, float vm2y_f, float v_ca, float v_cb, float v_cc, float v_op_f, float v_depth_f,
+                                     int stored_state, int classic, double* b_mean, double* b_quat, double* b_scale, double* b_op)
+{
+    gso_ev R[9], t[3];
+    for (int i = 0; i < 9; ++i) R[i] = ev_in(cam->R[i]);
+    for (int i = 0; i < 3; ++i) t[i] = ev_in(cam->t[i]);
+    const gso_ev fx = ev_in(cam->fx), fy = ev_in(cam->fy), cx = ev_in(cam->cx), cy = ev_in(cam->cy);
+    const gso_ev Wf = ev_in((double)W), Hf = ev_in((double)H), eps2d = ev_in(eps2d_f);
+    /* ---- forward intermediates */
+    gso_ev mc[3];
+    for (int i = 0; i < 3; ++i)
+        mc[i] = ev_add(ev_dot3(R[i * 3], ev_in(mean[0]), R[i * 3 + 1], ev_in(mean[1]), R[i * 3 + 2], ev_in(mean[2])), t[i]);
+    gso_ev q[4], qn[4], Rq[9], M[9], cov[9], T1[9], Cc[9], s[3];
+    for (int k = 0; k < 4; ++k) q[k] = ev_in(quat[k]);
+    for (int k = 0; k < 3; ++k) s[k] = ev_in(scale[k]);
+    const gso_ev n2 = ev_add(ev_add(ev_add(ev_mul(q[1], q[1]), ev_mul(q[2], q[2])), ev_mul(q[3], q[3])), ev_mul(q[0], q[0]));
+    const gso_ev inv = ev_div(ev_in(1.0), ev_sqrt(n2));
+    for (int k = 0; k < 4; ++k) qn[k] = ev_mul(q[k], inv);
+    {
+        const gso_ev w = qn[0], x = qn[1], y = qn[2], z = qn[3], one = ev_in(1.0);
+        const gso_ev x2 = ev_mul(x, x), y2 = ev_mul(y, y), z2 = ev_mul(z, z), xy = ev_mul(x, y), xz = ev_mul(x, z), yz = ev_mul(y, z);
+        const gso_ev wx = ev_mul(w, x), wy = ev_mul(w, y), wz = ev_mul(w, z);
+        Rq[0] = ev_sub(one, ev_scale(ev_add(y2, z2), 2.0)); Rq[1] = ev_scale(ev_sub(xy, wz), 2.0); Rq[2] = ev_scale(ev_add(xz, wy), 2.0);
+        Rq[3] = ev_scale(ev_add(xy, wz), 2.0); Rq[4] = ev_sub(one, ev_scale(ev_add(x2, z2), 2.0)); Rq[5] = ev_scale(ev_sub(yz, wx), 2.0);
+        Rq[6] = ev_scale(ev_sub(xz, wy), 2.0); Rq[7] = ev_scale(ev_add(yz, wx), 2.0); Rq[8] = ev_sub(one, ev_scale(ev_add(x2, y2), 2.0));
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) M[i * 3 + j] = ev_mul(Rq[i * 3 + j], s[j]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) cov[i * 3 + j] = ev_dot3(M[i * 3], M[j * 3], M[i * 3 + 1], M[j * 3 + 1], M[i * 3 + 2], M[j * 3 + 2]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) T1[i * 3 + j] = ev_dot3(R[i * 3], cov[j], R[i * 3 + 1], cov[3 + j], R[i * 3 + 2], cov[6 + j]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Cc[i * 3 + j] = ev_dot3(T1[i * 3], R[j * 3], T1[i * 3 + 1], R[j * 3 + 1], T1[i * 3 + 2], R[j * 3 + 2]);
+    const gso_ev x = mc[0], y = mc[1], z = mc[2];
+    const gso_ev c03 = ev_err(0.3, 0.3);                 /* the constant 0.3f is not 0.3 */
+    const gso_ev tan_fovx = ev_div(ev_scale(Wf, 0.5), fx), tan_fovy = ev_div(ev_scale(Hf, 0.5), fy);
+    const gso_ev lim_x_pos = ev_add(ev_div(ev_sub(Wf, cx), fx), ev_mul(c03, tan_fovx));
+    const gso_ev lim_x_neg = ev_add(ev_div(cx, fx), ev_mul(c03, tan_fovx));
+    const gso_ev lim_y_pos = ev_add(ev_div(ev_sub(Hf, cy), fy), ev_mul(c03, tan_fovy));
+    const gso_ev lim_y_neg = ev_add(ev_div(cy, fy), ev_mul(c03, tan_fovy));
+    const gso_ev rz = ev_div(ev_in(1.0), z), rz2 = ev_mul(rz, rz), rz3 = ev_mul(rz2, rz);
+    const gso_ev xrz = ev_mul(x, rz), yrz = ev_mul(y, rz);
+    const gso_ev tx = ev_mul(z, ev_clamp(xrz, ev_scale(lim_x_neg, -1.0), lim_x_pos));
+    const gso_ev ty = ev_mul(z, ev_clamp(yrz, ev_scale(lim_y_neg, -1.0), lim_y_pos));
+    const gso_ev zero = ev_in(0.0);
+    gso_ev J[6] = { ev_mul(fx, rz), zero, ev_mul(ev_mul(ev_scale(fx, -1.0), tx), rz2),
+                    zero, ev_mul(fy, rz), ev_mul(ev_mul(ev_scale(fy, -1.0), ty), rz2) };
+
+    /* ---- the stored state: exact inputs, or with the forward's own error */
+    gso_ev ia = ev_in(ia_f), ib = ev_in(ib_f), ic = ev_in(ic_f), comp = ev_in(comp_f);
+    double comp_x = comp_f;                              /* the compensation in exact arithmetic (stored_state only) */
+    if (stored_state) {
+        /* The .v fields above are the forward evaluated in double on the same fp32 inputs, i.e. exact next to fp32: the stored
+         * values are charged what they actually differ from it by (plus 2^-20 relative for the double evaluation's own
+         * cancellation).  A running-error bound of the fp32 forward would be useless exactly where it matters: for a needle
+         * whose det_orig = c00 c11 - c01 c10 cancels, it lets comp reach 0 and 1 / (comp + 1e-6) has no bound. */
+        const double a00 = J[0].v * Cc[0].v + J[2].v * Cc[6].v, a01 = J[0].v * Cc[1].v + J[2].v * Cc[7].v, a02 = J[0].v * Cc[2].v + J[2].v * Cc[8].v;
+        const double a10 = J[4].v * Cc[3].v + J[5].v * Cc[6].v, a11 = J[4].v * Cc[4].v + J[5].v * Cc[7].v, a12 = J[4].v * Cc[5].v + J[5].v * Cc[8].v;
+        double c00 = a00 * J[0].v + a02 * J[2].v, c01 = a01 * J[4].v + a02 * J[5].v;
+        double c10 = a10 * J[0].v + a12 * J[2].v, c11 = a11 * J[4].v + a12 * J[5].v;
+        const double det_orig = c00 * c11 - c01 * c10;
+        c00 += eps2d.v; c11 += eps2d.v;
+        const double det = c00 * c11 - c01 * c10;
+        const double slack = 1.0 / 1048576.0;
+        ia.e = (fabs(ia_f - c11 / det) + slack * fabs(ia_f)) / GSO_EPS;
+        ib.e = (fabs(ib_f + c01 / det) + slack * fabs(ib_f)) / GSO_EPS;
+        ic.e = (fabs(ic_f - c00 / det) + slack * fabs(ic_f)) / GSO_EPS;
+        if (!classic) {                                  /* (classic: the constant 1) */
+            comp_x = sqrt(det_orig / det > 0.0 ? det_orig / det : 0.0);
+            comp.e = (fabs(comp_f - comp_x) + slack * fabs(comp_f)) / GSO_EPS;
+        }
+    }
+
+    /* ---- backward */
+    const gso_ev v_op = ev_in(v_op_f);
+    const gso_ev g_op = ev_mul(v_op, comp);
+    const gso_ev v_comp = ev_mul(v_op, ev_in(opacity));
+    const gso_ev ga = ev_in(v_ca), gb = ev_in(0.5 * (double)v_cb), gc = ev_in(v_cc);
+    const gso_ev p00 = ev_dot2(ia, ga, ib, gb), p01 = ev_dot2(ia, gb, ib, gc);
+    const gso_ev p10 = ev_dot2(ib, ga, ic, gb), p11 = ev_dot2(ib, gb, ic, gc);
+    gso_ev G[4] = { ev_scale(ev_dot2(p00, ia, p01, ib), -1.0), ev_scale(ev_dot2(p00, ib, p01, ic), -1.0),
+                    ev_scale(ev_dot2(p10, ia, p11, ib), -1.0), ev_scale(ev_dot2(p10, ib, p11, ic), -1.0) };
+    {
+        const gso_ev det_conic = ev_sub(ev_mul(ia, ic), ev_mul(ib, ib));
+        gso_ev v_sqr_comp;
+        if (stored_state && !classic) {
+            /* against exact arithmetic the factor 0.5 / (comp + 1e-6) is wrong by what it differs from the derivative of the
+             * square root at the exact compensation, 0.5 / comp_x (no regulariser there): taken as it is, not to first order */
+            const double rc = 0.5 / ((double)comp_f + 1e-6), rc_x = 0.5 / comp_x;
+            v_sqr_comp = ev_mul(v_comp, ev_err(rc, fabs(rc - rc_x) / GSO_EPS + 3.0 * rc));
+        } else
+            v_sqr_comp = ev_div(ev_scale(v_comp, 0.5), ev_add(comp, ev_err(1e-6, 1e-6)));
+        const gso_ev om = ev_sub(ev_in(1.0), ev_mul(comp, comp));
+        const gso_ev ed = ev_mul(eps2d, det_conic);
+        G[0] = ev_add(G[0], ev_mul(v_sqr_comp, ev_sub(ev_mul(om, ia), ed)));
+        G[1] = ev_add(G[1], ev_mul(v_sqr_comp, ev_mul(om, ib)));
+        G[2] = ev_add(G[2], ev_mul(v_sqr_comp, ev_mul(om, ib)));
+        G[3] = ev_add(G[3], ev_mul(v_sqr_comp, ev_sub(ev_mul(om, ic), ed)));
+    }
+    gso_ev GJ[6], v_Cc[9], JC[6], JCt[6], v_J[6];
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 3; ++j) GJ[i * 3 + j] = ev_dot2(G[i * 2], J[j], G[i * 2 + 1], J[3 + j]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) v_Cc[i * 3 + j] = ev_dot2(J[i], GJ[j], J[3 + i], GJ[3 + j]);
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 3; ++j) {
+            JC[i * 3 + j]  = ev_dot3(J[i * 3], Cc[j], J[i * 3 + 1], Cc[3 + j], J[i * 3 + 2], Cc[6 + j]);
+            JCt[i * 3 + j] = ev_dot3(J[i * 3], Cc[j * 3], J[i * 3 + 1], Cc[j * 3 + 1], J[i * 3 + 2], Cc[j * 3 + 2]);
+        }
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 3; ++j)
+            v_J[i * 3 + j] = ev_add(ev_dot2(G[i * 2], JCt[j], G[i * 2 + 1], JCt[3 + j]), ev_dot2(G[i], JC[j], G[2 + i], JC[3 + j]));
+    const gso_ev vm2x = ev_in(vm2x_f), vm2y = ev_in(vm2y_f);
+    const gso_ev nfx = ev_scale(fx, -1.0), nfy = ev_scale(fy, -1.0);
+    gso_ev v_mc[3];
+    v_mc[0] = ev_mul(ev_mul(fx, rz), vm2x);
+    v_mc[1] = ev_mul(ev_mul(fy, rz), vm2y);
+    v_mc[2] = ev_mul(ev_scale(ev_add(ev_mul(ev_mul(fx, x), vm2x), ev_mul(ev_mul(fy, y), vm2y)), -1.0), rz2);
+    if (xrz.v <= lim_x_pos.v && xrz.v >= -lim_x_neg.v) v_mc[0] = ev_add(v_mc[0], ev_mul(ev_mul(nfx, rz2), v_J[2]));
+    else                                               v_mc[2] = ev_add(v_mc[2], ev_mul(ev_mul(ev_mul(nfx, rz3), v_J[2]), tx));
+    if (yrz.v <= lim_y_pos.v && yrz.v >= -lim_y_neg.v) v_mc[1] = ev_add(v_mc[1], ev_mul(ev_mul(nfy, rz2), v_J[5]));
+    else                                               v_mc[2] = ev_add(v_mc[2], ev_mul(ev_mul(ev_mul(nfy, rz3), v_J[5]), ty));
+    {
+        const gso_ev a0 = ev_mul(ev_mul(nfx, rz2), v_J[0]), a1 = ev_mul(ev_mul(fy, rz2), v_J[4]);
+        const gso_ev a2 = ev_mul(ev_mul(ev_mul(ev_scale(fx, 2.0), tx), rz3), v_J[2]);
+        const gso_ev a3 = ev_mul(ev_mul(ev_mul(ev_scale(fy, 2.0), ty), rz3), v_J[5]);
+        v_mc[2] = ev_add(v_mc[2], ev_add(ev_add(ev_sub(a0, a1), a2), a3));
+    }
+    v_mc[2] = ev_add(v_mc[2], ev_in(v_depth_f));
+    for (int i = 0; i < 3; ++i)
+        b_mean[i] = ev_dot3(R[i], v_mc[0], R[3 + i], v_mc[1], R[6 + i], v_mc[2]).e;
+    gso_ev Tm[9], v_cov[9], Sy[9], v_M[9], v_Rq[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Tm[i * 3 + j] = ev_dot3(R[i], v_Cc[j], R[3 + i], v_Cc[3 + j], R[6 + i], v_Cc[6 + j]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) v_cov[i * 3 + j] = ev_dot3(Tm[i * 3], R[j], Tm[i * 3 + 1], R[3 + j], Tm[i * 3 + 2], R[6 + j]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Sy[i * 3 + j] = ev_add(v_cov[i * 3 + j], v_cov[j * 3 + i]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            v_M[i * 3 + j] = ev_dot3(Sy[i * 3], M[j], Sy[i * 3 + 1], M[3 + j], Sy[i * 3 + 2], M[6 + j]);
+            v_Rq[i * 3 + j] = ev_mul(v_M[i * 3 + j], s[j]);
+        }
+    for (int j = 0; j < 3; ++j)
+        b_scale[j] = ev_dot3(Rq[j], v_M[j], Rq[3 + j], v_M[3 + j], Rq[6 + j], v_M[6 + j]).e;
+    {
+        const gso_ev w = qn[0], xq = qn[1], yq = qn[2], zq = qn[3];
+#define VR(i, j) v_Rq[(i) * 3 + (j)]
+#define EA ev_add
+#define ES ev_sub
+#define EM ev_mul
+        gso_ev vqn[4];
+        vqn[0] = ev_scale(EA(EA(EM(xq, ES(VR(2, 1), VR(1, 2))), EM(yq, ES(VR(0, 2), VR(2, 0)))), EM(zq, ES(VR(1, 0), VR(0, 1)))), 2.0);
+        vqn[1] = ev_scale(EA(EA(EA(EM(ev_scale(xq, -2.0), EA(VR(1, 1), VR(2, 2))), EM(yq, EA(VR(1, 0), VR(0, 1)))),
+                                EM(zq, EA(VR(2, 0), VR(0, 2)))), EM(w, ES(VR(2, 1), VR(1, 2)))), 2.0);
+        vqn[2] = ev_scale(EA(EA(ES(EM(xq, EA(VR(1, 0), VR(0, 1))), EM(ev_scale(yq, 2.0), EA(VR(0, 0), VR(2, 2)))),
+                                EM(zq, EA(VR(2, 1), VR(1, 2)))), EM(w, ES(VR(0, 2), VR(2, 0)))), 2.0);
+        vqn[3] = ev_scale(EA(ES(EA(EM(xq, EA(VR(2, 0), VR(0, 2))), EM(yq, EA(VR(2, 1), VR(1, 2)))),
+                                EM(ev_scale(zq, 2.0), EA(VR(0, 0), VR(1, 1)))), EM(w, ES(VR(1, 0), VR(0, 1)))), 2.0);
+#undef VR
+#undef EA
+#undef ES
+#undef EM
+        const gso_ev dotp = ev_add(ev_add(ev_add(ev_mul(vqn[0], qn[0]), ev_mul(vqn[1], qn[1])), ev_mul(vqn[2], qn[2])), ev_mul(vqn[3], qn[3]));
+        for (int k = 0; k < 4; ++k) b_quat[k] = ev_mul(ev_sub(vqn[k], ev_mul(dotp, qn[k])), inv).e;
+    }
+    *b_op = g_op.e;
+}
+
+/* The fp32 gradients of ONE visible Gaussian (the statements gso_project_bwd has always run). */
+static void project_bwd_gauss(const gso_cam* pcam, int W, int H, float eps2d, const float* mean, const float* quat,
+                              const float* scale, float opacity, float ia, float ib, float ic, float comp,
+                              float vm2x, float vm2y, float v_ca, float v_cb, float v_cc, float v_op, const float* v_depth /*nullable*/,
+                              float* g_mean, float* g_quat, float* g_scale, float* g_op)
+{
+    const gso_cam cam = *pcam;
+    {
+        /* A1' backward: opac_packed = opac[n] * comp */
+        *g_op = v_op * comp;
+        float v_comp = v_op * opacity;
 
         /* recompute forward intermediates */
         gso_proj p;
@@ -746,8 +965,7 @@ GSO_API void gso_project_bwd(int N, int V, int D,
         const float* Cc = p.covar_c;
 
         /* conic = inverse(covar2d_blur): v_covar2d = -conic * v_conic_mat * conic */
-        float ia = conics[3 * v], ib = conics[3 * v + 1], ic = conics[3 * v + 2];
-        float ga = v_conics[3 * v], gb = 0.5f * v_conics[3 * v + 1], gc = v_conics[3 * v + 2];
+        float ga = v_ca, gb = 0.5f * v_cb, gc = v_cc;
         /* P = Minv * G */
         float p00 = ia * ga + ib * gb, p01 = ia * gb + ib * gc;
         float p10 = ib * ga + ic * gb, p11 = ib * gb + ic * gc;
@@ -799,7 +1017,6 @@ GSO_API void gso_project_bwd(int N, int V, int D,
             for (int j = 0; j < 3; ++j)
                 v_J[i * 3 + j] = (G[i * 2 + 0] * JCt[0 * 3 + j] + G[i * 2 + 1] * JCt[1 * 3 + j])
                                + (G[0 * 2 + i] * JC[0 * 3 + j] + G[1 * 2 + i] * JC[1 * 3 + j]);
-        float vm2x = v_means2d[2 * v], vm2y = v_means2d[2 * v + 1];
         float v_mc[3];
         v_mc[0] = cam.fx * rz * vm2x;
         v_mc[1] = cam.fy * rz * vm2y;
@@ -810,12 +1027,12 @@ GSO_API void gso_project_bwd(int N, int V, int D,
         else                                             v_mc[2] += -cam.fy * rz3 * v_J[5] * ty;
         v_mc[2] += -cam.fx * rz2 * v_J[0] - cam.fy * rz2 * v_J[4]
                  + 2.0f * cam.fx * tx * rz3 * v_J[2] + 2.0f * cam.fy * ty * rz3 * v_J[5];
-        if (v_depths) v_mc[2] += v_depths[v];
+        if (v_depth) v_mc[2] += *v_depth;
 
         /* world<-camera: mean_c = R p + t ; covar_c = R covar R^T */
         const float* R = cam.R;
         for (int i = 0; i < 3; ++i)
-            v_means[3 * (size_t)n + i] = (R[0 * 3 + i] * v_mc[0] + R[1 * 3 + i] * v_mc[1]) + R[2 * 3 + i] * v_mc[2];
+            g_mean[i] = (R[0 * 3 + i] * v_mc[0] + R[1 * 3 + i] * v_mc[1]) + R[2 * 3 + i] * v_mc[2];
         float Tm[9], v_cov[9];
         /* v_covar = R^T v_Cc R */
         for (int i = 0; i < 3; ++i)
@@ -833,7 +1050,7 @@ GSO_API void gso_project_bwd(int N, int V, int D,
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) v_Rq[i * 3 + j] = v_M[i * 3 + j] * scale[j];
         for (int j = 0; j < 3; ++j)
-            v_scales[3 * (size_t)n + j] = (Rq[0 * 3 + j] * v_M[0 * 3 + j] + Rq[1 * 3 + j] * v_M[1 * 3 + j]) + Rq[2 * 3 + j] * v_M[2 * 3 + j];
+            g_scale[j] = (Rq[0 * 3 + j] * v_M[0 * 3 + j] + Rq[1 * 3 + j] * v_M[1 * 3 + j]) + Rq[2 * 3 + j] * v_M[2 * 3 + j];
 
         /* rotmat <- normalized quaternion <- raw quaternion */
         float qw = quat[0], qx = quat[1], qy = quat[2], qz = quat[3];
@@ -848,8 +1065,101 @@ GSO_API void gso_project_bwd(int N, int V, int D,
 #undef VR
         float qn[4] = { w, xq, yq, zq };
         float dotp = ((vqn[0] * qn[0] + vqn[1] * qn[1]) + vqn[2] * qn[2]) + vqn[3] * qn[3];
-        for (int k = 0; k < 4; ++k) v_quats[4 * (size_t)n + k] = (vqn[k] - dotp * qn[k]) * inv;
+        for (int k = 0; k < 4; ++k) g_quat[k] = (vqn[k] - dotp * qn[k]) * inv;
     }
+}
+
+/* gso_project_bwd (b_* == NULL) and gso_project_bwd_budget share this loop, so the gradients are the same bits. */
+static void project_bwd_all(int N, int V, int D,
+                            const float* means, const float* quats, const float* scales, const float* opacities,
+                            const float* viewmat, const float* K, int W, int H, float eps2d,
+                            const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                            const float* v_means2d, const float* v_depths /*nullable*/, const float* v_conics,
+                            const float* v_opacities_packed, const float* v_colors_packed /*nullable: D == 0*/, int classic,
+                            float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                            double* b_means, double* b_quats, double* b_scales, double* b_opacities, int stored_state)
+{
+    gso_cam cam; cam_from(viewmat, K, W, H, &cam);
+    memset(v_means, 0, sizeof(float) * 3 * (size_t)N);
+    memset(v_quats, 0, sizeof(float) * 4 * (size_t)N);
+    memset(v_scales, 0, sizeof(float) * 3 * (size_t)N);
+    memset(v_opacities, 0, sizeof(float) * (size_t)N);
+    if (v_colors) memset(v_colors, 0, sizeof(float) * (size_t)D * (size_t)N);
+    if (b_means) {
+        memset(b_means, 0, sizeof(double) * 3 * (size_t)N);
+        memset(b_quats, 0, sizeof(double) * 4 * (size_t)N);
+        memset(b_scales, 0, sizeof(double) * 3 * (size_t)N);
+        memset(b_opacities, 0, sizeof(double) * (size_t)N);
+    }
+#pragma omp parallel for schedule(static)
+    for (int v = 0; v < V; ++v) {
+        int n = gaussian_ids[v];
+        const float* mean = means + 3 * (size_t)n;
+        const float* quat = quats + 4 * (size_t)n;
+        const float* scale = scales + 3 * (size_t)n;
+        /* A1' backward: colors_packed = colors[n] */
+        if (v_colors)
+            for (int k = 0; k < D; ++k) v_colors[(size_t)n * D + k] = v_colors_packed[(size_t)v * D + k];
+        const float comp = classic ? 1.0f : compensations[v];
+        const float opac = classic ? 0.0f : opacities[n];
+        project_bwd_gauss(&cam, W, H, eps2d, mean, quat, scale, opac, conics[3 * v], conics[3 * v + 1], conics[3 * v + 2], comp,
+                          v_means2d[2 * v], v_means2d[2 * v + 1], v_conics[3 * v], v_conics[3 * v + 1], v_conics[3 * v + 2],
+                          v_opacities_packed[v], v_depths ? v_depths + v : NULL,
+                          v_means + 3 * (size_t)n, v_quats + 4 * (size_t)n, v_scales + 3 * (size_t)n, v_opacities + n);
+        if (b_means)
+            project_bwd_budget_gauss(&cam, W, H, eps2d, mean, quat, scale, opac, conics[3 * v], conics[3 * v + 1], conics[3 * v + 2], comp,
+                                     v_means2d[2 * v], v_means2d[2 * v + 1], v_conics[3 * v], v_conics[3 * v + 1], v_conics[3 * v + 2],
+                                     v_opacities_packed[v], v_depths ? v_depths[v] : 0.0f, stored_state, classic,
+                                     b_means + 3 * (size_t)n, b_quats + 4 * (size_t)n, b_scales + 3 * (size_t)n, b_opacities + n);
+    }
+}
+
+GSO_API void gso_project_bwd(int N, int V, int D,
+                             const float* means, const float* quats, const float* scales, const float* opacities,
+                             const float* viewmat, const float* K, int W, int H, float eps2d,
+                             const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                             const float* v_means2d, const float* v_depths /*nullable*/, const float* v_conics,
+                             const float* v_opacities_packed, const float* v_colors_packed,
+                             float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors)
+{
+    project_bwd_all(N, V, D, means, quats, scales, opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations,
+                    v_means2d, v_depths, v_conics, v_opacities_packed, v_colors_packed, 0,
+                    v_means, v_quats, v_scales, v_opacities, v_colors, NULL, NULL, NULL, NULL, 0);
+}
+
+/* gso_project_bwd with gs_project_bwd_ex's `classic` option (see the head of this section). */
+GSO_API void gso_project_bwd_ex(int N, int V, int D,
+                                const float* means, const float* quats, const float* scales, const float* opacities,
+                                const float* viewmat, const float* K, int W, int H, float eps2d,
+                                const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                                const float* v_means2d, const float* v_depths /*nullable*/, const float* v_conics,
+                                const float* v_opacities_packed, const float* v_colors_packed, int classic,
+                                float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors)
+{
+    project_bwd_all(N, V, D, means, quats, scales, opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations,
+                    v_means2d, v_depths, v_conics, v_opacities_packed, v_colors_packed, classic,
+                    v_means, v_quats, v_scales, v_opacities, v_colors, NULL, NULL, NULL, NULL, 0);
+}
+
+/* A7 with an error budget: the gradients of gso_project_bwd(_ex), bit for bit, plus one budget per element of
+ * v_means [N,3], v_quats [N,4], v_scales [N,3], v_opacities [N] (double, in units of 2^-24): the running-error bound of
+ * project_bwd_budget_gauss.  A culled Gaussian has budget 0 (and gradient 0), and so has every element that only zero
+ * cotangents reach.  A check reads |got - want| <= kappa * 2^-24 * budget element-wise, with no exceptions; it bounds
+ * implementations that read the SAME stored conics / compensations.  stored_state != 0 adds the error of that stored state
+ * against exact arithmetic, for a comparison with a float64 forward-and-backward (classic: of the conics only, the
+ * compensation being the constant 1).                                                                                      */
+GSO_API void gso_project_bwd_budget(int N, int V,
+                                    const float* means, const float* quats, const float* scales, const float* opacities,
+                                    const float* viewmat, const float* K, int W, int H, float eps2d,
+                                    const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                                    const float* v_means2d, const float* v_depths /*nullable*/, const float* v_conics,
+                                    const float* v_opacities_packed, int classic,
+                                    float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                                    double* b_means, double* b_quats, double* b_scales, double* b_opacities, int stored_state)
+{
+    project_bwd_all(N, V, 0, means, quats, scales, opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations,
+                    v_means2d, v_depths, v_conics, v_opacities_packed, NULL, classic,
+                    v_means, v_quats, v_scales, v_opacities, NULL, b_means, b_quats, b_scales, b_opacities, stored_state);
 }
 
 /* ------------------------------------------------------------------------- */

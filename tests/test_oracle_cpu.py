@@ -428,6 +428,60 @@ def test_raster_bwd_budget_vs_float64_autograd(scene, kind):
         util.assert_within_budget(name, g, want.grad.numpy(), b, util.BUDGET_KAPPA / 2)
 
 
+def _proj_float64_grads(sc, vw, gid, vm2, vc, vo, vd, classic):
+    """float64 autograd through oracle/torch_ref.project of sum(cotangent * packed output) over the visible Gaussians `gid`"""
+    dt = torch.float64
+    leaf = lambda a: torch.tensor(np.asarray(a, np.float64), requires_grad=True)
+    tm, tq, ts, to = leaf(sc["means"]), leaf(sc["quats"]), leaf(sc["scales"]), leaf(sc["opacities"])
+    T = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=dt)
+    m2d, dep, con, comp = tr.project(tm, tq, ts, T(vw["viewmat"]), T(vw["K"]), float(vw["W"]), float(vw["H"]),
+                                     eps2d=float(np.float32(0.3)))
+    g = torch.tensor(gid).long()
+    op_packed = to[g] if classic else to[g] * comp[g]
+    loss = (m2d[g] * T(vm2)).sum() + (con[g] * T(vc)).sum() + (op_packed * T(vo)).sum()
+    if vd is not None:
+        loss = loss + (dep[g] * T(vd)).sum()
+    loss.backward()
+    return tm.grad.numpy(), tq.grad.numpy(), ts.grad.numpy(), to.grad.numpy()
+
+
+@pytest.mark.parametrize("kind", list(util.PROJ_COTANGENTS) + ["classic"])
+@pytest.mark.parametrize("scene", list(util.PROJ_BUDGET_SCENES))
+def test_project_bwd_budget_vs_float64_autograd(scene, kind):
+    """The error budget of oracle.project_bwd_budget is honest: the oracle's fp32 projection gradients lie within
+    (kappa / 2) * 2^-24 * budget of float64 autograd through oracle/torch_ref.project, element by element, for EVERY Gaussian of
+    every view of the scene (the scenes' decision margins make fp32 and float64 take the same clamp route) -- with the stored-state
+    term, since the float64 side has no fp32 conics / compensations.  The gradients are gso_project_bwd's bit for bit, culled
+    Gaussians and all-zero cotangent rows give exact zeros with budget 0.  ('classic': dense cotangents, rasterize_mode='classic'.)
+    Worst ratios |fp32 - float64| / (2^-24 budget) seen (util.PROJ_BUDGET_KAPPA / 2 = 2): v_means 0.88, v_quats 0.08, v_scales 0.98,
+    v_opacities 1.00 (v_opacities = v_op * comp: all of its error is the stored compensation's, which the budget charges as measured)."""
+    sc = util.PROJ_BUDGET_SCENES[scene]()
+    classic = kind == "classic"
+    print(f"\n  {scene} / {kind}")
+    for vi, vw in enumerate(sc["views"]):
+        m = util.proj_scene_forward(sc, vi)
+        gid, V = m["gaussian_ids"], len(m["gaussian_ids"])
+        assert V > 1000
+        vm2, vc, vo, vd = util.proj_budget_cotangents("dense" if classic else kind, V, seed=11 + vi)
+        got, bud = oracle.project_bwd_budget(sc["means"], sc["quats"], sc["scales"], sc["opacities"], vw["viewmat"], vw["K"], vw["W"],
+                                             vw["H"], gid, m["conics"], m["compensations"], vm2, vc, vo, v_depths=vd, classic=classic,
+                                             stored_state=True)
+        plain = oracle.project_bwd(sc["means"], sc["quats"], sc["scales"], sc["opacities"], vw["viewmat"], vw["K"], vw["W"], vw["H"],
+                                   gid, m["conics"], m["compensations"], vm2, vc, vo, np.zeros((V, 3), np.float32), v_depths=vd,
+                                   classic=classic)
+        want = _proj_float64_grads(sc, vw, gid, vm2, vc, vo, vd, classic)
+        culled = np.ones(len(sc["regime"]), bool); culled[gid] = False
+        dead = culled.copy(); dead[gid[3::7]] = True                # culled, or every cotangent zero
+        for name, g, p, w, b in zip(("v_means", "v_quats", "v_scales", "v_opacities"), got, plain, want, bud):
+            assert g.view(np.int32).tobytes() == p.view(np.int32).tobytes(), name       # exactly gso_project_bwd's gradients
+            assert not g[dead].any() and not b[dead].any() and not w[dead].any(), name
+            if classic and name == "v_opacities":
+                assert np.array_equal(g[gid], vo)
+            assert np.isfinite(b).all(), name                      # no element of any Gaussian without a bound
+            assert float(np.abs(w).max()) > 0 or (kind == "geometry" and name == "v_opacities")
+            util.assert_within_budget(f"view {vi} {name}", g, w, b, util.PROJ_BUDGET_KAPPA / 2)
+
+
 @pytest.mark.parametrize("mode", ["pbr", "diffuse", "specular"])
 def test_oracle_shading_vs_float64_autograd(mode):
     sc, cam = sphere_case(1, 32)

@@ -87,14 +87,22 @@ def compare_grads(got, want, tol=2e-5):
 # ----------------------------------------------------------------------------- compositor backward against the oracle's error budget
 EPS32 = 2.0 ** -24
 BUDGET_KAPPA = 16.0          # one constant for every kernel and scene: 4.8 x the worst ratio seen (tests/test_gpu_raster_budget.py)
+# The projection backward (tests/test_gpu_project_budget.py) has a constant of its own, set from two measurements: (a) the fp32 oracle
+# against float64 autograd on the CPU (tests/test_oracle_cpu.py, bar kappa / 2): worst ratio 1.00; (b) the kernels on an MI355X: worst
+# ratio 0.54.  Kappa is the smallest power of two that is at least 4 x (b).  The budget there is a rigorous running-error bound, so a
+# correct implementation stays near or below 1 whatever the compiler does; the compositor's budget is not of that kind (its worst
+# ratio is 3.31), and sharing its 16 would leave 30 x headroom here.
+PROJ_BUDGET_KAPPA = 4.0
 
 
 def assert_within_budget(name, got, want, budget, kappa=BUDGET_KAPPA):
-    """|got - want| <= kappa * 2^-24 * budget for EVERY element (budget from oracle.raster_bwd_budget, in units of 2^-24); an element
-    whose budget is 0 was touched by no pair and must be exactly `want`.  Prints the worst ratio |got - want| / (2^-24 budget) and
+    """|got - want| <= kappa * 2^-24 * budget for EVERY element (budget from oracle.raster_bwd_budget / oracle.project_bwd_budget, in
+    units of 2^-24); an element whose budget is 0 was touched by no pair (is culled, or has only zero cotangents) and must be exactly
+    `want`; a budget that is not finite checks nothing and is refused.  Prints the worst ratio |got - want| / (2^-24 budget) and
     returns it."""
     got = np.asarray(got, dtype=np.float64); want = np.asarray(want, dtype=np.float64); budget = np.asarray(budget, dtype=np.float64)
     assert got.shape == want.shape == budget.shape, (name, got.shape, want.shape, budget.shape)
+    assert np.isfinite(budget).all() and np.isfinite(got).all() and np.isfinite(want).all(), name
     err = np.abs(got - want)
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(budget > 0, err / (EPS32 * budget), np.where(err > 0, np.inf, 0.0))
@@ -240,3 +248,266 @@ def raster_pair_stats(W, H, means2d, conics, opacities, offsets, flatten_ids, la
                         busy = int((per_pix > 0).sum())
                         st["min_busy_pixels"] = busy if st["min_busy_pixels"] is None else min(st["min_busy_pixels"], busy)
     return st
+
+
+# ----------------------------------------------------------------------------- projection backward against the oracle's error budget
+PROJ_NEAR = 0.01                         # near plane of every projection-budget scene
+PROJ_REGIMES = ("plain", "near", "clamp_x", "clamp_y", "clamp_xy", "tiny", "aniso", "iso", "qnorm", "flat")
+
+
+def proj_camera(yaw, pitch, roll, pos, W, H, fx, fy, cx, cy):
+    """a rotated and translated pinhole camera (OpenCV axes): dict(viewmat [4,4] f32 world->camera, K [3,3] f32, W, H)"""
+    cy_, sy = math.cos(yaw), math.sin(yaw); cp, sp = math.cos(pitch), math.sin(pitch); cr, sr = math.cos(roll), math.sin(roll)
+    Ry = np.array([[cy_, 0, sy], [0, 1, 0], [-sy, 0, cy_]]); Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
+    Rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
+    R = (Ry @ Rx @ Rz).T                                               # world -> camera
+    vm = np.eye(4); vm[:3, :3] = R; vm[:3, 3] = -R @ np.asarray(pos, np.float64)
+    return dict(viewmat=vm.astype(np.float32), K=np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32), W=W, H=H)
+
+
+def proj_limits(view):
+    """(lim_x_pos, lim_x_neg, lim_y_pos, lim_y_neg) of the tan-fov clamp of a view, float64"""
+    K, W, H = view["K"].astype(np.float64), view["W"], view["H"]
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    return (W - cx) / fx + 0.15 * W / fx, cx / fx + 0.15 * W / fx, (H - cy) / fy + 0.15 * H / fy, cy / fy + 0.15 * H / fy
+
+
+def proj_cam_coords(scene, view):
+    """camera-space means [N,3] of a scene in a view (float64 arithmetic on the fp32 inputs)"""
+    vm = view["viewmat"].astype(np.float64)
+    return scene["means"].astype(np.float64) @ vm[:3, :3].T + vm[:3, 3]
+
+
+def proj_margins_ok(scene, view, rel=1e-3):
+    """per Gaussian: every decision of the projection has a margin -- z is `rel` away from the near plane and, in front of it,
+    x/z and y/z are `rel` away from both clamp limits -- so that fp32 and float64, or a division and a hardware reciprocal, decide
+    alike"""
+    mc = proj_cam_coords(scene, view)
+    z = mc[:, 2]
+    ok = np.abs(z / PROJ_NEAR - 1.0) >= rel
+    front = z > PROJ_NEAR
+    zs = np.where(front, z, 1.0)
+    lxp, lxn, lyp, lyn = proj_limits(view)
+    for r, (lp, ln) in ((mc[:, 0] / zs, (lxp, lxn)), (mc[:, 1] / zs, (lyp, lyn))):
+        ok &= ~front | ((np.abs(r - lp) >= rel * lp) & (np.abs(r + ln) >= rel * ln))
+    return ok
+
+
+def _rand_quats(r, n):
+    q = r.randn(n, 4)
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def _proj_regime(r, name, n, view, smin):
+    """n Gaussians of one regime in the CAMERA space of `view`: (mean_c [n,3], quats [n,4], scales [n,3]); projected sizes are
+    chosen in pixels (sigma_px) and turned into scales by z / focal"""
+    K, W, H = view["K"].astype(np.float64), view["W"], view["H"]
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    f = math.sqrt(fx * fy)
+    lxp, lxn, lyp, lyn = proj_limits(view)
+    z = r.uniform(2.0, 6.0, n)
+    xr = (r.uniform(0.05 * W, 0.95 * W, n) - cx) / fx            # x / z, on screen
+    yr = (r.uniform(0.05 * H, 0.95 * H, n) - cy) / fy
+    quats = _rand_quats(r, n)
+    sig = r.uniform(max(smin, 1.2), 8.0, n)                       # pixels
+    ratio = r.uniform(0.6, 1.6, (n, 3))                           # mild anisotropy
+    if name == "plain":
+        sig = r.uniform(smin, 8.0, n)
+    elif name == "near":
+        z = PROJ_NEAR * np.exp(r.uniform(math.log(1.02), math.log(9.5), n))
+        sig = r.uniform(1.5, 6.0, n)
+    elif name in ("clamp_x", "clamp_y", "clamp_xy"):
+        k = r.uniform(1.02, 1.35, (n, 2)); side = r.rand(n, 2) < 0.5
+        ox = np.where(side[:, 0], lxp * k[:, 0], -lxn * k[:, 0]); oy = np.where(side[:, 1], lyp * k[:, 1], -lyn * k[:, 1])
+        dx = np.where(side[:, 0], fx * ox + cx - W, -(fx * ox + cx)); dy = np.where(side[:, 1], fy * oy + cy - H, -(fy * oy + cy))
+        if name == "clamp_x":
+            xr, d = ox, dx
+        elif name == "clamp_y":
+            yr, d = oy, dy
+        else:
+            xr, yr, d = ox, oy, np.maximum(dx, dy)
+        sig = d / 1.5 + 12.0                                       # large radii: the centre is off screen, the Gaussian is not
+        ratio = r.uniform(0.8, 1.25, (n, 3))
+    elif name == "tiny":
+        sig = np.exp(r.uniform(math.log(0.004), math.log(0.085), n))  # comp ~ sig^2 / 0.3: 5e-5 ... 0.04
+        ratio = r.uniform(0.8, 1.25, (n, 3))
+    elif name == "aniso":
+        sig = r.uniform(5.0, 40.0, n)
+        ratio = np.stack([np.ones(n), 10.0 ** r.uniform(-4.0, 0.0, n), 10.0 ** r.uniform(-4.0, 0.0, n)], 1)
+        ratio = np.take_along_axis(ratio, np.argsort(r.rand(n, 3), axis=1), 1)
+    elif name == "iso":
+        ratio = np.ones((n, 3))
+    elif name == "qnorm":
+        quats = quats * np.exp(r.uniform(math.log(1e-3), math.log(1e3), n))[:, None]
+        quats[0] *= 1e-3 / np.linalg.norm(quats[0]); quats[1] *= 1e3 / np.linalg.norm(quats[1])
+    elif name == "flat":
+        ratio[:, 2] = 1.0
+    else:
+        raise KeyError(name)
+    scales = (sig * z / f)[:, None] * ratio
+    if name == "flat":
+        scales[:, 2] = math.exp(-10.0)
+    return np.stack([xr * z, yr * z, z], 1), quats, scales
+
+
+def _proj_culled(r, n, view, radius_clip):
+    """n Gaussians no view of the forward keeps: behind the camera, between the camera and the near plane, off screen, and (with a
+    radius clip) too small"""
+    W, H = view["W"], view["H"]
+    K = view["K"].astype(np.float64)
+    lxp, lxn, lyp, lyn = proj_limits(view)
+    mc, quats, scales = _proj_regime(r, "plain", n, view, 1.2)
+    kind = np.arange(n) % (4 if radius_clip > 0 else 3)
+    mc[kind == 0] *= -1.0                                                           # behind the camera
+    m = kind == 1                                                                   # in front of it, before the near plane
+    zn = PROJ_NEAR * r.uniform(0.1, 0.99, m.sum())
+    mc[m] *= (zn / mc[m, 2])[:, None]; scales[m] *= (zn / (mc[m, 2] + 4.0))[:, None]
+    m = kind == 2                                                                   # beyond the clamp limit, small: off screen
+    mc[m, 0] = lxp * r.uniform(1.05, 1.3, m.sum()) * mc[m, 2]
+    scales[m] = (r.uniform(1.2, 2.0, m.sum()) * mc[m, 2] / math.sqrt(K[0, 0] * K[1, 1]))[:, None] * np.ones(3)
+    m = kind == 3                                                                   # radius 2 (the blur alone): below a radius clip of 3
+    scales[m] = (r.uniform(0.01, 0.1, m.sum()) * mc[m, 2] / math.sqrt(K[0, 0] * K[1, 1]))[:, None] * np.ones(3)
+    return mc, quats, scales, kind
+
+
+def proj_budget_scene(name, views, n_per=260, n_culled=400, radius_clip=0.0, seed=0):
+    """A projection-budget scene: n_per Gaussians of every regime of PROJ_REGIMES placed in the camera space of views[0] and mapped
+    back through that camera, culled Gaussians interleaved (one random order).  With several views, Gaussians that sit within the
+    decision margin of ANY view are replaced at construction (the builder draws again), so no Gaussian of the scene is ever excluded
+    from a check.  dict(means, quats, scales, opacities, views, radius_clip, regime [N] (index into PROJ_REGIMES, -1 = built to be
+    culled), seed); the regimes and margins are asserted by proj_scene_forward."""
+    r = np.random.RandomState(1000 + seed)
+    v0 = views[0]
+    vm = v0["viewmat"].astype(np.float64)
+    smin = 0.4 if radius_clip == 0.0 else 1.2
+    parts = [(i, n_per) for i in range(len(PROJ_REGIMES))] + [(-1, n_culled)]
+    means, quats, scales, regime = [], [], [], []
+    for reg, n in parts:
+        have = 0
+        for attempt in range(20):
+            if reg >= 0:
+                mc, q, s = _proj_regime(r, PROJ_REGIMES[reg], n, v0, smin)
+            else:
+                mc, q, s, _ = _proj_culled(r, n, v0, radius_clip)
+            m = ((mc - vm[:3, 3]) @ vm[:3, :3]).astype(np.float32)
+            trial = dict(means=m)
+            ok = np.ones(n, bool)
+            for vw in views:
+                ok &= proj_margins_ok(trial, vw, rel=2e-3)
+            take = np.nonzero(ok)[0][:n - have]
+            means.append(m[take]); quats.append(q[take]); scales.append(s[take]); regime.append(np.full(len(take), reg))
+            have += len(take)
+            if have == n:
+                break
+        assert have == n, (name, reg, have)
+    means, quats, scales, regime = (np.concatenate(a) for a in (means, quats, scales, regime))
+    order = r.permutation(len(regime))
+    sc = dict(name=name, means=means[order].astype(np.float32), quats=quats[order].astype(np.float32),
+              scales=scales[order].astype(np.float32), regime=regime[order], views=views, radius_clip=float(radius_clip), seed=seed)
+    sc["opacities"] = r.uniform(0.05, 1.0, len(order)).astype(np.float32)
+    return sc
+
+
+def proj_scene_forward(sc, view_index=0, check_regimes=True):
+    """oracle.project_fwd of a projection-budget scene in one of its views, with the decision margins asserted for EVERY Gaussian
+    and (view 0, which the scene was placed in) every regime of the scene asserted on the forward's outputs, so that a later change
+    cannot silently stop covering it.  Returns the oracle's dict."""
+    import oracle
+    vw = sc["views"][view_index]
+    W, H, clip = vw["W"], vw["H"], sc["radius_clip"]
+    assert W % 16 and H % 16 and W != H
+    K = vw["K"]
+    assert K[0, 0] != K[1, 1] and abs(K[0, 2] - W / 2) > 1 and abs(K[1, 2] - H / 2) > 1
+    assert proj_margins_ok(sc, vw).all()
+    m = oracle.project_fwd(sc["means"], sc["quats"], sc["scales"], vw["viewmat"], K, W, H, near=PROJ_NEAR, radius_clip=clip)
+    gid = m["gaussian_ids"]
+    vis = np.zeros(len(sc["regime"]), bool); vis[gid] = True
+    if clip > 0:                                                   # every radius at least 1 away from the clip
+        m0 = oracle.project_fwd(sc["means"], sc["quats"], sc["scales"], vw["viewmat"], K, W, H, near=PROJ_NEAR, radius_clip=0.0)
+        assert (np.abs(m0["radii"] - clip) >= 1).all()
+        assert len(m0["gaussian_ids"]) > len(gid)                  # ... and the clip culls some
+    reg = sc["regime"]
+    assert not vis[reg < 0].any() or view_index > 0                # built to be culled
+    culled_between = (~vis[:-1] & vis[1:]).sum()
+    assert culled_between > 50 or view_index > 0                   # culled rows interleaved with visible ones
+    mc = proj_cam_coords(sc, vw)
+    xr, yr, z = mc[:, 0] / mc[:, 2], mc[:, 1] / mc[:, 2], mc[:, 2]
+    lxp, lxn, lyp, lyn = proj_limits(vw)
+    in_x = (xr <= lxp) & (xr >= -lxn); in_y = (yr <= lyp) & (yr >= -lyn)
+    comp = np.full(len(reg), np.nan); comp[gid] = m["compensations"]
+    if view_index > 0:
+        # another camera on a scene placed for view 0: what it must still drive, counted on ITS visible Gaussians -- each clamp route,
+        # the near plane, comp -> 0 -- so that a later change of a camera cannot silently empty these
+        routes = [(in_x & in_y), (~in_x & in_y), (in_x & ~in_y), (~in_x & ~in_y)]
+        counts = [int((r & vis).sum()) for r in routes] + [int((vis & (z < 10 * PROJ_NEAR)).sum()), int((comp < 0.05).sum())]
+        assert min(counts) >= 30, (sc["name"], view_index, counts)
+    if not (check_regimes and view_index == 0):
+        return m
+    con = np.full((len(reg), 3), np.nan); con[gid] = m["conics"]
+    sel = lambda nm: reg == PROJ_REGIMES.index(nm)
+    tiny_culled = clip > 0                                          # (radius 2: the tiny regime is what a radius clip removes)
+    for nm in PROJ_REGIMES:
+        assert vis[sel(nm)].all() or (nm == "tiny" and tiny_culled), (sc["name"], nm, int((~vis[sel(nm)]).sum()))
+    s = sel("plain"); assert (in_x & in_y)[s].all() and (comp[s] > 0.2).all() and (comp[s] < 0.999).all()
+    s = sel("near"); assert ((z[s] > PROJ_NEAR) & (z[s] < 10 * PROJ_NEAR)).all()
+    s = sel("clamp_x"); assert (~in_x & in_y)[s].all() and (xr[s] > lxp).sum() > 20 and (xr[s] < -lxn).sum() > 20
+    s = sel("clamp_y"); assert (in_x & ~in_y)[s].all() and (yr[s] > lyp).sum() > 20 and (yr[s] < -lyn).sum() > 20
+    s = sel("clamp_xy"); assert (~in_x & ~in_y)[s].all()
+    for a in (xr[s] > lxp, xr[s] < -lxn):
+        for b in (yr[s] > lyp, yr[s] < -lyn):
+            assert (a & b).sum() > 10
+    if not tiny_culled:
+        s = sel("tiny"); assert (comp[s] < 0.05).all() and (comp[s] < 1e-3).sum() > 10 and (comp[s] > 0).all()
+    s = sel("aniso")
+    sr = sc["scales"][s].min(1) / sc["scales"][s].max(1)
+    assert sr.min() < 2e-4 and (con[s, 1] ** 2 > 0.99 * con[s, 0] * con[s, 2]).sum() > 5
+    s = sel("iso"); assert (sc["scales"][s] == sc["scales"][s][:, :1]).all()
+    s = sel("qnorm"); qn = np.linalg.norm(sc["quats"][s].astype(np.float64), axis=1)
+    assert qn.min() < 1.1e-3 and qn.max() > 0.9e3
+    s = sel("flat"); assert (sc["scales"][s, 2] == np.float32(math.exp(-10.0))).all()
+    return m
+
+
+def _proj_views_single(which):
+    if which == "yaw":        # 200 x 120, yawed by 0.4 rad
+        return [proj_camera(0.4, 0.0, 0.0, (0.5, -0.2, -1.0), 200, 120, 150.0, 170.0, 90.0, 70.0)]
+    return [proj_camera(-0.7, 0.35, 0.2, (-1.5, 0.8, 0.3), 187, 333, 260.0, 230.0, 101.0, 150.0)]
+
+
+def _proj_views_multi():
+    """eight different cameras around one scene: small changes of pose (so that the regimes of view 0 survive in part) and of
+    intrinsics and image size"""
+    r = np.random.RandomState(77)
+    views = [proj_camera(0.4, 0.0, 0.0, (0.5, -0.2, -1.0), 200, 120, 150.0, 170.0, 90.0, 70.0)]
+    for i in range(7):
+        W, H = (200 + 7 * i, 120 + 5 * i)
+        views.append(proj_camera(0.4 + r.uniform(-0.25, 0.25), r.uniform(-0.2, 0.2), r.uniform(-0.3, 0.3),
+                                 (0.5 + r.uniform(-0.02, 0.02), -0.2 + r.uniform(-0.02, 0.02), -1.0 + r.uniform(-0.03, 0.03)), W, H,
+                                 150.0 + 6 * i, 170.0 - 3 * i, 90.0 + 3 * i, 70.0 + 1.5 * i))
+    return views
+
+
+PROJ_BUDGET_SCENES = dict(
+    yaw=lambda: proj_budget_scene("yaw", _proj_views_single("yaw"), seed=0),
+    tilt_clip=lambda: proj_budget_scene("tilt_clip", _proj_views_single("tilt"), radius_clip=3.0, seed=1),
+    orbit8=lambda: proj_budget_scene("orbit8", _proj_views_multi(), n_per=200, n_culled=300, seed=2))
+
+PROJ_COTANGENTS = ("dense", "geometry", "opacity", "depth")
+
+
+def proj_budget_cotangents(kind, V, seed):
+    """packed cotangents of the projection budget tests: (v_means2d [V,2], v_conics [V,3], v_opacities [V], v_depths [V] or None);
+    'dense' random signed, 'geometry' (v_opacities = 0), 'opacity' (only the compensation path is live), 'depth' (dense, with
+    v_depths); in every kind each seventh row is all zeros (a Gaussian that reached no pixel: its gradients must be exactly 0)"""
+    r = np.random.RandomState(seed)
+    vm = r.uniform(-1, 1, (V, 2)).astype(np.float32); vc = r.uniform(-1, 1, (V, 3)).astype(np.float32)
+    vo = r.uniform(-1, 1, V).astype(np.float32); vd = r.uniform(-1, 1, V).astype(np.float32)
+    if kind == "geometry":
+        vo[:] = 0.0
+    elif kind == "opacity":
+        vm[:] = 0.0; vc[:] = 0.0
+    else:
+        assert kind in ("dense", "depth"), kind
+    for a in (vm, vc, vo, vd):
+        a[3::7] = 0.0
+    return vm, vc, vo, (vd if kind == "depth" else None)
