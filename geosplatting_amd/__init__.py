@@ -14,12 +14,17 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              GeoSplatter.get_geometry rfstudio/model/geosplat.py:751-769 (rank 4)
   stage1.Stage1Model / stage1.train_step  == GeoSplatter (stage 1) + GeoSplatTrainer.step, rfstudio/model/geosplat.py:676-927,
                                              rfstudio/trainer/geosplat_trainer.py:150-186 (BASELINE config 5)
+  gsplat3d.GaussianSet / GSplatModel / GSplatTrainer / mutate_adam
+                                          == Splats + GSplatter + GSplatTrainer + ModuleOptimizers.mutate_params: vanilla-3DGS training with
+                                             adaptive density control (rfstudio/graphics/_splats.py:82-184, rfstudio/model/gsplat.py,
+                                             rfstudio/trainer/gsplat_trainer.py, rfstudio/optim/optimizer.py:121-191)
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
 from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, view_matrix  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401
+from .gsplat3d import GaussianSet, GSplatModel, GSplatTrainer, mutate_adam  # noqa: F401
 from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401

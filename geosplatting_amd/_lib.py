@@ -35,6 +35,10 @@ class GsTileLevel(C.Structure):
                 ("desc", C.c_void_p), ("weights", C.c_void_p), ("dst", C.c_void_p), ("lds_bytes", C.c_size_t)]
 
 
+class GsDensifyTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("floats_per_row", C.c_int), ("kind", C.c_int)]
+
+
 class GsEnvGrad(C.Structure):
     _fields_ = [("base", C.c_void_p), ("levels", C.c_void_p * GS_MAX_LEVELS)]
 
@@ -50,6 +54,7 @@ SYMBOLS = [
     "gs_vertex_normals_bwd", "gs_photo_loss_ws_bytes", "gs_photo_loss", "gs_smooth_loss_ws_bytes", "gs_smooth_loss", "gs_hashgrid_fwd", "gs_hashgrid_bwd_ws_bytes", "gs_hashgrid_bwd", "gs_hashgrid_bwd_fixed_ws_bytes", "gs_hashgrid_bwd_fixed", "gs_mlp_wgrad_ws_bytes", "gs_mlp_wgrad",
     "gs_flexicubes_ws_bytes", "gs_flexicubes_count", "gs_flexicubes_fwd", "gs_flexicubes_bwd", "gs_flexicubes_entropy_fwd",
     "gs_flexicubes_entropy_bwd", "gs_front_ws_bytes", "gs_front_fwd", "gs_isect_bin_front_ws_bytes", "gs_isect_bin_front", "gs_tail_bwd", "gs_tail_bwd_multi", "gs_tail_bwd_multi_parts", "gs_tail_priv_ws_bytes", "gs_tail_priv_reduce", "gs_smooth_gather", "gs_smooth_fold", "gs_activation_chain",
+    "gs_densify_stats", "gs_densify_ws_bytes", "gs_densify_plan", "gs_densify_fill",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -101,6 +106,8 @@ def lib() -> C.CDLL:
         l.gs_raster_log_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
         l.gs_raster_ws_bytes.restype = C.c_size_t
         l.gs_raster_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+        l.gs_densify_ws_bytes.restype = C.c_size_t
+        l.gs_densify_ws_bytes.argtypes = [C.c_int64, C.c_int]
         _lib = l
     return _lib
 

@@ -654,6 +654,66 @@ int gs_smooth_fold(int V_cap, const int64_t* counts_dev, const float* vis_record
 int gs_activation_chain(int64_t N, const float* g_scales_act, const float* scales_act, const float* g_opac_act, const float* opac_act,
                         float* v_scales, float* v_opacities, void* stream);
 
+/* ------------------------------------------------------------------ adaptive density control of the 3DGS trainer ---------- */
+/* Splats.densify_and_cull / Splats.cull (rfstudio/graphics/_splats.py:121-175), GSplatter.update_grad_norm
+ * (rfstudio/model/gsplat.py:360-374) and the Adam-moment half of ModuleOptimizers.mutate_params (rfstudio/optim/optimizer.py:155-185).
+ * The count -> read totals -> fill protocol of the FlexiCubes entry points:
+ *
+ * gs_densify_stats: for every visible row v, xys_grad_norm[id] += |v_means2d[v]| and vis_counts[id] += 1 with id = gaussian_ids[v].
+ *   Ids are unique within a call (packed, one camera): plain read-modify-write.  Ids outside [0, N) are skipped.
+ *
+ * gs_densify_plan (count): scales[N,3] (log), opacities[N] (logit).  Per Gaussian
+ *     scale_max = max_j exp(scales_j),  avg = half_extent * (xys_grad_norm / vis_counts)     (half_extent = 0.5 * max(W, H), host)
+ *     high = avg > grad_thresh,  split = high && scale_max > size_thresh,  dup = high && scale_max <= size_thresh
+ *     cull = sigmoid(opacity) < alpha_thresh || (scale_thresh >= 0 && scale_max > scale_thresh)     (scale_thresh < 0: None)
+ *     selected = !(cull || split)
+ *   mode GS_DENSIFY_MODE_CULL is Splats.cull: only `cull` is evaluated (xys_grad_norm / vis_counts may be NULL, num_splits unused).
+ *   Leaves the classes and their exclusive ranks over the index order in `ws` and writes
+ *   totals[4] (device int64) = {n_selected, n_split, n_dup, N_out = n_selected + num_splits * n_split + n_dup}.
+ *   A duplicated Gaussian that is not culled appears twice (kept and copied); a culled one still yields its children or its copy.
+ *
+ * gs_densify_fill: after the caller has read `totals` and allocated.  `ws` must still hold what the plan left; the fill WRITES its row
+ *   map (output row -> source row) into the part of `ws` the plan reserved for it.  Output rows, as
+ *   Splats.cat([self[selected], self[splits].split(S).view(-1), self[dups]]): selected rows in index order, then child s of the
+ *   split row of rank r at n_selected + s * n_split + r (S-major), then the duplicates in index order.
+ *   indices[N_out]: the source index of a selected row, -1 for every new row (what mutate_params consumes).
+ *   Every tensor of `table` (host array) is gathered in one launch: dst[N_out, floats_per_row] from src[N, floats_per_row],
+ *     GS_DENSIFY_COPY    every row copied bit for bit (quats, colours, SH, opacities)
+ *     GS_DENSIFY_MEANS   child rows: R(q / |q|) (exp(scales) o z) + mean with z = randn[S, n_split, 3] (its flat row is the
+ *                        child's output row minus n_selected); other rows copied
+ *     GS_DENSIFY_SCALES  child rows: log(exp(scales) * (1 / 1.6)); other rows copied
+ *     GS_DENSIFY_MOMENT  selected rows copied, every new row 0 (Adam exp_avg / exp_avg_sq)
+ *   quats / scales are the SOURCE tensors [N,4] / [N,3]; they and randn may be NULL when no MEANS tensor has children.
+ *   The totals are the caller's: rows beyond them are not written and source rows are clamped to [0, N), so totals that do not
+ *   belong to the plan in `ws` give wrong rows but touch no memory outside the buffers they size.
+ *   Limits: N <= 2^27, num_splits <= 8, N_out * floats_per_row < 2^31, at most GS_DENSIFY_MAX_TENSORS tensors. */
+#define GS_DENSIFY_COPY         0
+#define GS_DENSIFY_MEANS        1
+#define GS_DENSIFY_SCALES       2
+#define GS_DENSIFY_MOMENT       3
+#define GS_DENSIFY_MODE_DENSIFY 0
+#define GS_DENSIFY_MODE_CULL    1
+#define GS_DENSIFY_MAX_TENSORS  32
+#define GS_DENSIFY_MAX_SPLITS   8
+#define GS_DENSIFY_MAX_N        (((int64_t)1) << 27)
+
+typedef struct GsDensifyTensor {
+    const float* src;
+    float*       dst;
+    int          floats_per_row;
+    int          kind;
+} GsDensifyTensor;
+
+int gs_densify_stats(int V, const int64_t* gaussian_ids, const float* v_means2d, int64_t N, float* xys_grad_norm, float* vis_counts,
+                     void* stream);
+size_t gs_densify_ws_bytes(int64_t N, int num_splits);
+int gs_densify_plan(int64_t N, const float* scales, const float* opacities, const float* xys_grad_norm, const float* vis_counts,
+                    float half_extent, float grad_thresh, float size_thresh, float alpha_thresh, float scale_thresh, int num_splits,
+                    int mode, void* ws, size_t ws_bytes, int64_t* totals, void* stream);
+int gs_densify_fill(int64_t N, int num_splits, void* ws, size_t ws_bytes, int64_t n_selected, int64_t n_split, int64_t n_dup,
+                    const GsDensifyTensor* table /*host*/, int n_tensors, const float* quats, const float* scales, const float* randn,
+                    int64_t* indices, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
