@@ -225,6 +225,17 @@ extern "C" size_t gs_shade_bwd_ws_bytes(const GsEnv* env, int mode)
     return shade_bwd_priv_floats(e, mode, lo, &bo) * sizeof(float) * GS_XCD_COPIES;
 }
 
+extern "C" int gs_shade_bwd_plan_blocks(const GsEnv* env, int mode, int N, int* block_threads)
+{
+    EnvDev e;
+    if (env_to_dev(env, e) != 0 || mode < 0 || mode > 2 || N < 0) return 0;
+    EnvGradDev eg;
+    ShadeBwdPlan plan;
+    if (shade_bwd_plan(e, mode, N, nullptr, 0, eg, plan) != GS_OK) return 0;
+    if (block_threads) *block_threads = plan.block;
+    return plan.blocks;
+}
+
 extern "C" int gs_shade_bwd(int N, const float* means, const float* normals, const float* kd, const float* ks,
                             const float* cam_pos, float min_roughness, float max_metallic, int mode,
                             const GsEnv* env, const float* v_colors, float* v_means, float* v_normals,

@@ -336,6 +336,9 @@ int gs_shade_fwd(int N, const float* means, const float* normals, const float* k
 /* Bytes of the optional workspace of gs_shade_bwd: 8 XCD-private copies of the texel-gradient levels that do
  * not fit LDS (XCD-local atomics stay in L2; device-scope ones are 32-byte write-throughs to the fabric). */
 size_t gs_shade_bwd_ws_bytes(const GsEnv* env /*host*/, int mode);
+/* launch shape gs_shade_bwd takes for N Gaussians: returns the number of blocks (0 on a bad env), *block_threads the block size;
+ * blocks * block_threads < N means persistent blocks that stride over the Gaussians (tests size a grid-stride case by it) */
+int gs_shade_bwd_plan_blocks(const GsEnv* env /*host*/, int mode, int N, int* block_threads);
 
 /* Recomputes the forward and chains v_colors[N,3].  v_means/v_normals/v_kd/v_ks are fully written (or added
  * to when accumulate != 0); texel gradients are always ACCUMULATED into env_grad.  ws may be NULL (plain

@@ -29,7 +29,7 @@ _lib = None
 
 def build(force: bool = False) -> str:
     """Compile the oracle with gcc (oracle/Makefile)."""
-    srcs = [os.path.join(_HERE, f) for f in ("gs_oracle.c", "gs_oracle_shade.c", "gs_oracle_splitsum.c")]
+    srcs = [os.path.join(_HERE, f) for f in ("gs_oracle.c", "gs_oracle_shade.c", "gs_oracle_splitsum.c", "gs_oracle_ev.h")]
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs
     )
@@ -302,6 +302,62 @@ def shade_bwd(means, normals, kd, ks, cam_pos, lut, base, levels: List[np.ndarra
                         _p(v_colors), _p(v_means), _p(v_normals), _p(v_kd), _p(v_ks), _p(v_base),
                         _ptr_array(v_levels))
     return dict(v_means=v_means, v_normals=v_normals, v_kd=v_kd, v_ks=v_ks, v_base=v_base, v_levels=v_levels)
+
+
+SHADE_MARGINS = ("len", "d", "lut_x", "lut_y", "rough", "lam", "l0_face", "l0_tx", "l0_ty", "l1_face", "l1_tx", "l1_ty",
+                 "base_face", "base_tx", "base_ty")
+
+
+def shade_bwd_budget(means, normals, kd, ks, cam_pos, lut, base, levels: List[np.ndarray], v_colors, min_roughness=0.1,
+                     max_metallic=1.0, mode="pbr", env_min_roughness=0.08, env_max_roughness=0.5, return_margins=False, pool=False):
+    """shade_bwd's gradients (bit for bit) plus an error budget per element (gso_shade_bwd_budget): returns (grads, budgets), two
+    dicts with the keys of shade_bwd, the budgets float64 in units of 2^-24: a running-error bound through the recomputed forward
+    and the whole chain rule; a texel element that collects n contributions adds (n - 1) * sum |contribution| for a summation in
+    any order.  A correct fp32 implementation that makes the same selections lands within kappa * 2^-24 * budget of the values;
+    rows whose colour cotangent is all zero and texels no footprint touches have gradient 0 and budget 0.  return_margins=True
+    appends margins [N, len(SHADE_MARGINS), 2]: per Gaussian and selecting quantity (distance to the nearest decision boundary,
+    forward error bound of the quantity); unused slots hold (inf, 0).  pool=True: the texel budgets hold the sum of the contributions'
+    own bounds only, and the budgets dict gains "abs" and "n" ([v_levels..., v_base] order: sum |contribution| and the number of
+    contributions per texel element) -- shade_pool_texels turns several such calls into the budget of their common sum."""
+    means, normals, kd, ks, cam_pos = _f32(means), _f32(normals), _f32(kd), _f32(ks), _f32(cam_pos)
+    lut, base, v_colors = _f32(lut), _f32(base), _f32(v_colors)
+    levels = [_f32(l) for l in levels]
+    res = np.array([l.shape[1] for l in levels], np.int32)
+    N = means.shape[0]
+    assert normals.shape == (N, 3) and kd.shape == (N, 3) and ks.shape == (N, 2) and v_colors.shape == (N, 3) and len(levels) <= 16
+    assert lib().gso_shade_margin_count() == len(SHADE_MARGINS)
+    g = dict(v_means=np.empty((N, 3), np.float32), v_normals=np.empty((N, 3), np.float32), v_kd=np.empty((N, 3), np.float32),
+             v_ks=np.empty((N, 2), np.float32), v_base=np.zeros_like(base), v_levels=[np.zeros_like(l) for l in levels])
+    b = dict(v_means=np.empty((N, 3), np.float64), v_normals=np.empty((N, 3), np.float64), v_kd=np.empty((N, 3), np.float64),
+             v_ks=np.empty((N, 2), np.float64), v_base=np.zeros(base.shape, np.float64),
+             v_levels=[np.zeros(l.shape, np.float64) for l in levels])
+    margins = np.empty((N, len(SHADE_MARGINS), 2), np.float64) if return_margins else None
+    pa = pn = None
+    if pool:
+        b["abs"] = [np.zeros(l.shape, np.float64) for l in levels] + [np.zeros(base.shape, np.float64)]
+        b["n"] = [np.zeros(l.shape, np.int32) for l in levels] + [np.zeros(base.shape, np.int32)]
+        pa, pn = _ptr_array(b["abs"]), _ptr_array(b["n"])
+    lib().gso_shade_bwd_budget(int(N), _p(means), _p(normals), _p(kd), _p(ks), _p(cam_pos), _fl(min_roughness),
+                               _fl(max_metallic), MODE[mode], _p(lut), int(lut.shape[-2]), _p(base), int(base.shape[1]),
+                               _ptr_array(levels), _p(res), len(levels), _fl(env_min_roughness), _fl(env_max_roughness),
+                               _p(v_colors), _p(g["v_means"]), _p(g["v_normals"]), _p(g["v_kd"]), _p(g["v_ks"]), _p(g["v_base"]),
+                               _ptr_array(g["v_levels"]), _p(b["v_means"]), _p(b["v_normals"]), _p(b["v_kd"]), _p(b["v_ks"]),
+                               _p(b["v_base"]), _ptr_array(b["v_levels"]), _p(margins), pa, pn)
+    return (g, b, margins) if return_margins else (g, b)
+
+
+def shade_pool_texels(parts):
+    """(want, budget) per texel array ([v_levels..., v_base] order) of the SUM of several shade_bwd_budget(pool=True) results
+    [(grads, budgets), ...] accumulated into one buffer in any order: the values in float64, the budget = the sum of the
+    contributions' own bounds + (n_total - 1) * sum |contribution|"""
+    L = len(parts[0][0]["v_levels"])
+    want, bud = [], []
+    for i in range(L + 1):
+        tex = lambda x: x["v_levels"][i] if i < L else x["v_base"]
+        w = sum(tex(g).astype(np.float64) for g, _ in parts)
+        own = sum(tex(b) for _, b in parts); a = sum(b["abs"][i] for _, b in parts); n = sum(b["n"][i].astype(np.int64) for _, b in parts)
+        want.append(w); bud.append(own + np.maximum(n - 1, 0) * a)
+    return want, bud
 
 
 def tex2d_linear_clamp(lut, uv):

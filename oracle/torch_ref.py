@@ -168,7 +168,11 @@ def cube_linear(tex: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
     tot = sum(torch.where(m, torch.zeros_like(v), v) for v, m in zip(vals, miss))
     vals = [torch.where(m, tot / 3.0, v) for v, m in zip(vals, miss)]
     top = vals[0] + fx * (vals[1] - vals[0]); bot = vals[2] + fx * (vals[3] - vals[2])
-    return top + fy * (bot - top)
+    out = top + fy * (bot - top)
+    # a direction without a major axis (zero, or not finite) has no footprint: colour 0 and no gradients, as cube_footprint's `valid`
+    ac = d.detach().abs().max(-1).values
+    valid = ((ac > 0) & torch.isfinite(ac))[:, None]
+    return torch.where(valid, out, torch.zeros_like(out))
 
 
 def mip_from_roughness(r, min_r=0.08, max_r=0.5, L=6):

@@ -667,3 +667,62 @@ def test_flexicubes_tables_cover_all_cases():
         assert sorted(e for p in dmc[c] for e in p) == crossing          # every crossing edge in exactly one patch
         assert all(3 <= len(p) <= 7 for p in dmc[c]) and len(dmc[c]) <= 4
     assert int(chk[:, 0].sum()) == 36 and all(chk[c, 4] == 255 - c for c in range(256) if chk[c, 0])
+
+
+# ----------------------------------------------------------------------------- shading backward: the error budget
+_SHADE_CASES = [(nm, mode) for nm, spec in util.SHADE_BUDGET_SCENES.items() for mode in spec["modes"]]
+_shade_scene_cache = {}
+
+
+def _shade_scene(name, mode):
+    if (name, mode) not in _shade_scene_cache:
+        sc = util.shade_budget_scene(name, mode, **util.SHADE_BUDGET_SCENES[name]["kw"])
+        util.shade_scene_check(sc)                                   # every regime present, every selection margin above its bound
+        t = lambda a: torch.tensor(a, dtype=torch.float64)
+        _shade_scene_cache[(name, mode)] = sc, dict(means=t(sc["means"]), normals=t(sc["normals"]), kd=t(sc["kd"]), ks=t(sc["ks"]),
+                                                    base=t(sc["base"]), levels=[t(l) for l in sc["levels"]])
+    return _shade_scene_cache[(name, mode)]
+
+
+@pytest.mark.parametrize("kind", util.SHADE_COTANGENTS)
+@pytest.mark.parametrize("scene,mode", _SHADE_CASES)
+def test_shade_bwd_budget_vs_float64_autograd(scene, mode, kind):
+    """oracle.shade_bwd_budget on every shading-budget scene (tests/util.py SHADE_BUDGET_SCENES; shade_scene_check asserts the regimes
+    and the selection margins): the fp32 gradients equal gso_shade_bwd's bit for bit, every budget is finite, rows with an all-zero
+    cotangent and texels no footprint touches are exact zeros with budget 0, and every element of v_means / v_normals / v_kd / v_ks /
+    v_base / v_levels[l] lies within (kappa / 2) * 2^-24 * budget of float64 autograd through oracle/torch_ref.shade.
+
+    torch_ref.cube_linear took another route than the C code for a direction without a major axis (a zero normal in 'diffuse'): it
+    sampled the centre of face +x where cube_footprint declares the footprint invalid (colour 0, no gradients); it now does the same.
+
+    Worst ratios |fp32 - float64| / (2^-24 budget) seen (util.SHADE_BUDGET_KAPPA / 2 = 2):
+    v_means 0.09, v_normals 0.28, v_kd 0.20, v_ks 0.20, v_base 0.25, v_levels[0..3] 0.13 / 0.15 / 0.13 / 0.10."""
+    sc, t64 = _shade_scene(scene, mode)
+    N = len(sc["regime"])
+    cot = util.shade_budget_cotangents(kind, N, seed=7)
+    args = (sc["means"], sc["normals"], sc["kd"], sc["ks"], sc["cam_pos"], sc["lut"], sc["base"], sc["levels"], cot)
+    g, b = oracle.shade_bwd_budget(*args, mode=mode, **sc["opts"])
+    g0 = oracle.shade_bwd(*args, mode=mode, **sc["opts"])
+    flat = lambda x: [x["v_means"], x["v_normals"], x["v_kd"], x["v_ks"], x["v_base"]] + list(x["v_levels"])
+    names = ["v_means", "v_normals", "v_kd", "v_ks", "v_base"] + [f"v_levels[{l}]" for l in range(len(sc["levels"]))]
+    # ---- float64 autograd
+    leaves = [t64[k].clone().requires_grad_(True) for k in ("means", "normals", "kd", "ks", "base")]
+    lv = [l.clone().requires_grad_(True) for l in t64["levels"]]
+    o = sc["opts"]
+    col = tr.shade(leaves[0], leaves[1], leaves[2], leaves[3], torch.tensor(sc["cam_pos"], dtype=torch.float64),
+                   torch.tensor(sc["lut"], dtype=torch.float64), leaves[4], lv, min_roughness=o["min_roughness"],
+                   max_metallic=o["max_metallic"], mode=mode, env_min_r=o["env_min_roughness"], env_max_r=o["env_max_roughness"])
+    (col * torch.tensor(cot, dtype=torch.float64)).sum().backward()
+    want = [np.zeros(x.shape) if x.grad is None else x.grad.numpy() for x in leaves + lv]
+    dead = ~cot.any(1)
+    assert dead.sum() >= N // 7
+    for nm, a, a0, bb, w in zip(names, flat(g), flat(g0), flat(b), want):
+        assert a.view(np.int32).tobytes() == a0.view(np.int32).tobytes(), nm          # the same bits as gso_shade_bwd
+        assert np.isfinite(bb).all(), nm
+        if a.shape[0] == N and a.ndim == 2:
+            assert not a[dead].any() and not bb[dead].any(), nm
+        else:
+            assert not a[bb == 0].any() and (w[bb == 0] == 0).all(), nm               # untouched texels
+            assert (bb == 0).any() or a.shape[1] <= 32, nm
+        r = util.assert_within_budget(f"{scene}/{mode}/{kind} {nm}", a, w, bb, util.SHADE_BUDGET_KAPPA / 2)
+        print(f"    {nm:12s} {r:6.3f}")

@@ -511,3 +511,355 @@ def proj_budget_cotangents(kind, V, seed):
     for a in (vm, vc, vo, vd):
         a[3::7] = 0.0
     return vm, vc, vo, (vd if kind == "depth" else None)
+
+
+# ----------------------------------------------------------------------------- shading backward against the oracle's error budget
+# tests/test_gpu_shade_budget.py.  The constant follows the rule written beside PROJ_BUDGET_KAPPA: the smallest power of two that is
+# at least 4 x the worst ratio the kernels show on an MI355X; the CPU test (oracle against float64 autograd) has the bar kappa / 2.
+# Measured: (a) the fp32 oracle against float64 autograd on the CPU: worst ratio 0.28 (v_normals; v_means 0.09, v_kd 0.20, v_ks 0.20,
+# texels 0.25); (b) the kernels on an MI355X: gs_shade_bwd / gs_tail_bwd per-Gaussian gradients 0.00 (the oracle's bits), their texel
+# sums 0.97 (over a pre-filled pattern, with the test's own n |p| term; 0.04 over zeros); the lean pair path of gs_tail_bwd_multi
+# 0.41 (v_kd), texels 0.04.
+SHADE_BUDGET_KAPPA = 4.0
+
+_CUBE_FACES = ((2, 1, 0, -1.0, -1.0), (2, 1, 0, 1.0, -1.0), (0, 2, 1, 1.0, 1.0), (0, 2, 1, 1.0, -1.0), (0, 1, 2, 1.0, -1.0), (0, 1, 2, -1.0, -1.0))
+
+
+def cube_face_point(s, x, y):
+    """direction [n,3] of the face coordinates (x, y) of face s (face_point of oracle/gs_oracle_shade.c), float64, not normalised"""
+    one = np.ones_like(x)
+    return np.stack([(one, -y, -x), (-one, -y, x), (x, one, y), (x, -one, -y), (x, -y, one), (-x, -y, -one)][s], -1)
+
+
+def cube_face_coords(d):
+    """(face, xn, yn) of directions [n,3] in float64 (select_face / cube_footprint of the oracle); face -1 for a zero direction"""
+    d = np.asarray(d, np.float64)
+    ax, ay, az = np.abs(d).T
+    f = np.where(az > np.maximum(ax, ay), 4, np.where(ay > ax, 2, 0))
+    c = np.where(f == 4, d[:, 2], np.where(f == 2, d[:, 1], d[:, 0]))
+    f = f + (c < 0)
+    xn = np.zeros(len(d)); yn = np.zeros(len(d))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for s, (a, b, cc, sx, sy) in enumerate(_CUBE_FACES):
+            m = f == s
+            xn[m] = sx * d[m, a] / np.abs(d[m, cc]); yn[m] = sy * d[m, b] / np.abs(d[m, cc])
+    return np.where(np.abs(d).max(1) > 0, f, -1), xn, yn
+
+
+SHADE_DIR_REGIMES = tuple(f"face{s}" for s in range(6)) + tuple(f"edge{s}{e}" for s in range(6) for e in range(4)) + \
+    tuple(f"corner{s}{k}" for s in range(6) for k in range(4)) + ("axis",)
+# Gaussians placed exactly ON a decision boundary, where the arithmetic is exact in fp32 and in float64 alike (roughness = ks[0] with
+# min_roughness = 0, compared with constants both sides hold as the same fp32 values): regime -> the margin slots that may be 0
+SHADE_ON_BOUNDARY = dict(r_eq_min=("rough", "lam"), r_eq_max=("rough", "lam"), r_eq_one=("rough", "lam"))
+
+
+def _shade_env(levels_res, base_res, seed):
+    """signed texels with magnitudes spread over three decades"""
+    r = np.random.RandomState(4000 + seed)
+    tex = lambda R: (r.randn(6, R, R, 3) * 10.0 ** r.uniform(-2.0, 1.0, (6, R, R, 1))).astype(np.float32)
+    return tex(base_res), [tex(R) for R in levels_res]
+
+
+def shade_budget_scene(name, mode, levels_res=(64, 32, 16), base_res=16, min_roughness=0.0, max_metallic=1.0, env_min_r=0.08,
+                       env_max_r=0.5, random_lut=False, n_per=34, n_pile=300, seed=0, geometry=None):
+    """A shading-budget scene for one mode: per-Gaussian inputs (no rasterisation) built regime by regime, `regime` [N] naming the
+    regime each Gaussian was built for.  The lookup direction (the normal in 'diffuse', the reflection vector otherwise) drives
+    the cube regimes of SHADE_DIR_REGIMES; the others are 'zero_normal' (diffuse), the FG-LUT clamps 'ndv_hi' / 'rough_hi', the view
+    regimes 'backface' / 'grazing' / 'tiny_d' (0 < d < 1e-6, exact: the camera straight above along z) / 'at_camera' / 'len' (1e-3
+    .. 1e3), the mip regimes 'r_lt_min' / 'r_eq_min' (integer level, f == 0) / 'seg_lo' / 'r_eq_max' / 'seg_hi' / 'r_eq_one', the
+    materials 'metal0' / 'metal1' / 'kd_dark', 'plain', and the pile-ups 'pile_a' / 'pile_b' (hundreds of footprints on the same few
+    texels).  Candidates whose selections sit within their error bound of a boundary are dropped at construction (the builder draws
+    half as many again), those of SHADE_ON_BOUNDARY excepted.  geometry = (means, [cam_pos, ...]): keep the given means (the regimes
+    that place the mean are left out; the direction regimes are built for the first camera, the margins hold for every camera) --
+    the tail kernels' scenes, whose Gaussians come from a projection scene.  shade_scene_check
+    asserts the regimes and the margins."""
+    import oracle
+    r = np.random.RandomState(3000 + seed)
+    base, levels = _shade_env(levels_res, base_res, seed)
+    f32 = lambda x: float(np.float32(x))
+    opts = dict(min_roughness=f32(min_roughness), max_metallic=f32(max_metallic), env_min_roughness=f32(env_min_r),
+                env_max_roughness=f32(env_max_r))
+    if random_lut:
+        lut = r.uniform(0.0, 1.0, (256, 256, 2)).astype(np.float32)
+    else:
+        import geosplatting_amd as gs
+        lut = gs.get_fg_lut(torch.device("cpu"))[0].numpy()
+    Rmax = max(levels_res) if mode != "diffuse" else base_res
+    cam = np.array([0.3, -0.2, 2.5], np.float32).astype(np.float64) if geometry is None else np.asarray(geometry[1][0], np.float64)
+    regs = list(SHADE_DIR_REGIMES) + ["ndv_hi", "rough_hi", "backface", "grazing", "r_lt_min", "seg_lo", "seg_hi", "metal0", "metal1",
+                                      "kd_dark", "plain"]
+    if min_roughness == 0.0:                                       # roughness = ks[0] exactly: it can sit ON a boundary
+        regs += ["r_eq_min", "r_eq_max", "r_eq_one"]
+    if mode == "diffuse":
+        regs.append("zero_normal")
+    if geometry is None:
+        regs += ["tiny_d", "at_camera", "len"]
+    elif mode != "diffuse":
+        regs.remove("axis")                                        # (an exactly axis-aligned reflection needs the view along the axis)
+    counts = [(g, n_per) for g in regs] + [("pile_a", n_pile), ("pile_b", n_pile)]
+    pile_dirs = dict(pile_a=np.array([0.31, 0.22, 1.0]), pile_b=np.array([-1.0, 0.4, -0.15]))
+    unit = lambda v: v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+    def draw(g, n, given_means):
+        s = r.randint(0, 6, n); xn = r.uniform(-0.8, 0.8, n); yn = r.uniform(-0.8, 0.8, n)
+        near = lambda k: r.uniform(1.0 - 0.9 / Rmax, 1.0 - 0.02 / Rmax, k)
+        if g.startswith("face"):
+            s[:] = int(g[4])
+        elif g.startswith("edge"):
+            s[:] = int(g[4]); e = int(g[5])
+            if e < 2:
+                xn = near(n) * (1 if e == 1 else -1)
+            else:
+                yn = near(n) * (1 if e == 3 else -1)
+        elif g.startswith("corner"):
+            s[:] = int(g[6]); k = int(g[7])
+            xn = near(n) * (1 if k & 1 else -1); yn = near(n) * (1 if k & 2 else -1)
+        elif g == "axis":
+            xn[:] = 0.0; yn[:] = 0.0; s = np.arange(n) % 6
+        D = np.zeros((n, 3))
+        for f in range(6):
+            m = s == f
+            D[m] = cube_face_point(f, xn[m], yn[m])
+        if g != "axis":
+            D = unit(D)
+        if g in pile_dirs:
+            D = unit(pile_dirs[g] + 0.004 * r.randn(n, 3))
+        if given_means is None:
+            w = unit(r.randn(n, 3))
+            w = np.where((w * D).sum(-1, keepdims=True) < -0.4, -w, w)
+            ln = r.uniform(1.5, 4.0, n)
+            if g == "len":
+                ln = 10.0 ** r.permutation(np.linspace(-3.0, 3.0, n))
+            if g == "axis":
+                w = D.copy()                                                   # the view along the normal: the reflection is the axis itself
+            if g == "tiny_d":
+                w = np.tile([0.0, 0.0, 1.0], (n, 1)); ln = r.randint(1, 5, n).astype(np.float64)
+            means = (cam - w * ln[:, None]).astype(np.float32)
+            if g == "at_camera":
+                means = np.tile(cam.astype(np.float32), (n, 1))
+            if g == "axis":                                                    # exact: one coordinate differs from the camera's
+                means = np.tile(cam.astype(np.float32), (n, 1)).astype(np.float64)
+                means = (means - D * r.randint(1, 4, n)[:, None]).astype(np.float32)
+        else:
+            means = given_means
+        v = cam - means.astype(np.float64)
+        ln = np.linalg.norm(v, axis=-1, keepdims=True)
+        wo = np.where(ln < 1e-6, [0.0, 0.0, 1.0], v / np.maximum(ln, 1e-6))
+        if given_means is not None:                                            # keep the reflection away from -wo: mirror the target
+            D = np.where((wo * D).sum(-1, keepdims=True) < -0.4, -D, D) if not (g.startswith(("face", "edge", "corner", "pile")) or g == "axis") else D
+        normals = D.copy() if mode == "diffuse" else unit(D + wo)
+        if g == "axis" and mode != "diffuse":
+            normals = D.copy()
+        perp = unit(np.cross(wo, unit(r.randn(n, 3))))
+        if g == "backface":
+            normals = unit(-wo * r.uniform(0.1, 1.0, (n, 1)) + perp)
+        elif g == "grazing":
+            normals = unit(perp + wo * r.uniform(1e-5, 1e-3, (n, 1)))
+        elif g == "ndv_hi":
+            normals = unit(wo + perp * r.uniform(0.0, 0.03, (n, 1)))
+        elif g == "tiny_d":
+            phi = r.uniform(0, 2 * np.pi, n)
+            normals = np.stack([np.cos(phi), np.sin(phi), r.uniform(1e-7, 9e-7, n)], -1)
+        elif g == "zero_normal":
+            normals = np.zeros((n, 3))
+        ks = np.stack([r.uniform(0.1, 0.95, n), r.uniform(0.05, 0.95, n)], -1)
+        if g in SHADE_DIR_REGIMES or g in pile_dirs:                 # roughness stratified: every direction regime reaches every level
+            ks[:, 0] = r.permutation(np.linspace(0.1, 0.95, n))
+        kd = r.uniform(0.1, 0.9, (n, 3))
+        ksr = lambda rough: (np.float32(rough) - np.float32(min_roughness)) / (np.float32(1.0) - np.float32(min_roughness))
+        if g == "rough_hi":
+            ks[:, 0] = r.uniform(0.9985, 1.0, n)
+        elif g == "r_lt_min":
+            ks[:, 0] = r.uniform(0.0, ksr(env_min_r) * 0.9, n)
+        elif g == "r_eq_min":
+            ks[:, 0] = ksr(env_min_r)
+        elif g == "seg_lo":
+            ks[:, 0] = r.uniform(ksr(env_min_r) * 1.05 + 0.01, ksr(env_max_r) * 0.98, n)
+        elif g == "r_eq_max":
+            ks[:, 0] = ksr(env_max_r)
+        elif g == "seg_hi":
+            ks[:, 0] = r.uniform(ksr(env_max_r) * 1.02, 0.99, n)
+        elif g == "r_eq_one":
+            ks[:, 0] = 1.0
+        elif g == "metal0":
+            ks[:, 1] = 0.0
+        elif g == "metal1":
+            ks[:, 1] = 1.0
+        elif g == "kd_dark":
+            kd = r.uniform(0.0, 0.04, (n, 3))
+        return means, normals.astype(np.float32), kd.astype(np.float32), ks.astype(np.float32)
+
+    cams = [cam] if geometry is None else [np.asarray(c, np.float64) for c in geometry[1]]
+    if geometry is not None:                                       # rows beyond the regimes' blocks: plain
+        rest = len(geometry[0]) - sum(n for _, n in counts)
+        assert rest >= 0, (name, rest)
+        counts += [("plain", rest)] if rest else []
+
+    def margins_ok(g, means, normals, kd, ks):
+        ok = np.ones(len(means), bool)
+        cot = np.ones((len(means), 3), np.float32)
+        for c in cams:
+            mg = oracle.shade_bwd_budget(means, normals, kd, ks, c.astype(np.float32), lut, base, levels, cot, mode=mode,
+                                         return_margins=True, **opts)[2]
+            ok &= _shade_margins_ok(mg, [g] * len(means))
+        return ok
+
+    parts = []
+    at = 0
+    for g, n in counts:
+        if geometry is None:
+            k = n + n // 2
+            means, normals, kd, ks = draw(g, k, None)
+            take = np.nonzero(margins_ok(g, means, normals, kd, ks))[0][:n]
+            assert len(take) == n, (name, mode, g, len(take))
+            means, normals, kd, ks = means[take], normals[take], kd[take], ks[take]
+        else:                                                      # every row keeps its mean: rows that fail are drawn again
+            gm = np.asarray(geometry[0], np.float32)[at:at + n]
+            means, normals, kd, ks = draw(g, n, gm)
+            for attempt in range(12):
+                bad = ~margins_ok(g, means, normals, kd, ks)
+                if not bad.any():
+                    break
+                _, n2, kd2, ks2 = draw(g, n, gm)
+                normals[bad], kd[bad], ks[bad] = n2[bad], kd2[bad], ks2[bad]
+            assert not bad.any(), (name, mode, g, int(bad.sum()))
+        parts.append((means, normals, kd, ks, [g] * n))
+        at += n
+    cat = lambda i: np.concatenate([p[i] for p in parts])
+    regime = np.array(sum((p[4] for p in parts), []))
+    order = r.permutation(len(regime)) if geometry is None else np.arange(len(regime))
+    return dict(name=name, mode=mode, means=cat(0)[order], normals=cat(1)[order], kd=cat(2)[order], ks=cat(3)[order],
+                cam_pos=cam.astype(np.float32), regime=regime[order], lut=lut, base=base, levels=levels, opts=opts, seed=seed)
+
+
+def _shade_margins_ok(margins, regime):
+    """per Gaussian: every selection margin exceeds its forward error bound (a quantity that is exact and not on a boundary has bound
+    0 or a margin far above it), the slots SHADE_ON_BOUNDARY lists for the Gaussian's regime excepted"""
+    import oracle
+    ok = np.ones(len(regime), bool)
+    for j, slot in enumerate(oracle.SHADE_MARGINS):
+        good = margins[:, j, 0] > 2.0 * margins[:, j, 1]
+        exempt = np.array([slot in SHADE_ON_BOUNDARY.get(g, ()) for g in regime])
+        ok &= good | exempt
+    return ok
+
+
+def shade_scene_check(sc):
+    """Asserts on the oracle's forward of a shading-budget scene that every selection margin exceeds (twice) its error bound -- so
+    that fp32, float64 and a kernel with a one-ulp reciprocal select alike -- and that every regime the scene names really occurs
+    in at least 30 Gaussians.  Returns the margins."""
+    import oracle
+    N = len(sc["regime"])
+    cot = np.ones((N, 3), np.float32)
+    _, _, mg = oracle.shade_bwd_budget(sc["means"], sc["normals"], sc["kd"], sc["ks"], sc["cam_pos"], sc["lut"], sc["base"], sc["levels"],
+                                       cot, mode=sc["mode"], return_margins=True, **sc["opts"])
+    bad = ~_shade_margins_ok(mg, sc["regime"])
+    assert not bad.any(), (sc["name"], sc["mode"], sorted(set(sc["regime"][bad])))
+    for g, slots in SHADE_ON_BOUNDARY.items():                        # ... and those really sit ON the boundary
+        m = sc["regime"] == g
+        if m.any() and sc["mode"] != "diffuse":
+            assert (mg[m, 4, 0] == 0).all(), g
+    # ---- the regimes, recomputed in float64 from the fp32 inputs
+    o = sc["opts"]
+    cam = sc["cam_pos"].astype(np.float64)
+    v = cam - sc["means"].astype(np.float64)
+    ln = np.linalg.norm(v, axis=-1)
+    wo = np.where(ln[:, None] < 1e-6, [0.0, 0.0, 1.0], v / np.maximum(ln, 1e-6)[:, None])
+    nrm = sc["normals"].astype(np.float64)
+    d = (nrm * wo).sum(-1)
+    D = nrm if sc["mode"] == "diffuse" else 2.0 * d[:, None] * nrm - wo
+    face, xn, yn = cube_face_coords(D)
+    rough = sc["ks"][:, 0].astype(np.float64) * (1.0 - o["min_roughness"]) + o["min_roughness"]
+    metal = sc["ks"][:, 1].astype(np.float64) * o["max_metallic"]
+    res = [sc["base"].shape[1]] if sc["mode"] == "diffuse" else [l.shape[1] for l in sc["levels"]]
+    L = len(sc["levels"])
+    over = lambda c, R: ((c + 1) * 0.5 * R - 0.5 < 0) | ((c + 1) * 0.5 * R - 0.5 > R - 1)
+    ox = np.all([over(xn, R) for R in res], 0); oy = np.all([over(yn, R) for R in res], 0)          # at EVERY level in use
+    ix = ~np.any([over(xn, R) for R in res], 0); iy = ~np.any([over(yn, R) for R in res], 0)
+    pred = {}
+    for s in range(6):
+        pred[f"face{s}"] = (face == s) & ix & iy
+        for e in range(4):
+            side = (xn < 0, xn > 0, yn < 0, yn > 0)[e]
+            pred[f"edge{s}{e}"] = (face == s) & side & ((ox & iy) if e < 2 else (oy & ix))
+        for k in range(4):
+            pred[f"corner{s}{k}"] = (face == s) & ox & oy & ((xn > 0) == bool(k & 1)) & ((yn > 0) == bool(k & 2))
+    pred["axis"] = (np.abs(D) > 0).sum(1) == 1
+    pred["zero_normal"] = face < 0
+    pred["ndv_hi"] = d > 1.0 - 1.0 / 512.0
+    pred["rough_hi"] = rough > 1.0 - 1.0 / 512.0
+    pred["backface"] = d < 0
+    pred["grazing"] = (d > 1e-6) & (d < 1e-3)
+    pred["tiny_d"] = (d > 0) & (d < 1e-6)
+    pred["at_camera"] = ln == 0
+    pred["len"] = np.ones(N, bool)
+    emin, emax = o["env_min_roughness"], o["env_max_roughness"]
+    pred["r_lt_min"] = rough < emin
+    pred["r_eq_min"] = rough == emin
+    pred["seg_lo"] = (rough > emin) & (rough < emax)
+    pred["r_eq_max"] = rough == emax
+    pred["seg_hi"] = (rough > emax) & (rough < 1.0)
+    pred["r_eq_one"] = rough == 1.0
+    pred["metal0"] = metal == 0
+    pred["metal1"] = metal == o["max_metallic"]
+    pred["kd_dark"] = (sc["kd"] < 0.04).all(1)
+    pred["plain"] = (sc["kd"] > 0.04).all(1)
+    pred["pile_a"] = pred["pile_b"] = np.ones(N, bool)
+    names = sorted(set(sc["regime"]))
+    for g in names:
+        m = sc["regime"] == g
+        assert m.sum() >= 30 and pred[g][m].all(), (sc["name"], sc["mode"], g, int(m.sum()), int((~pred[g][m]).sum()))
+    if "len" in names:
+        m = sc["regime"] == "len"
+        assert ln[m].min() < 1e-2 and ln[m].max() > 1e2
+    for g in ("pile_a", "pile_b"):                                    # hundreds of footprints on a handful of texels of every level
+        m = sc["regime"] == g
+        for R in res:
+            tx = np.floor((xn[m] + 1) * 0.5 * R - 0.5); ty = np.floor((yn[m] + 1) * 0.5 * R - 0.5)
+            assert len(set(zip(face[m], tx, ty))) <= 9 and m.sum() >= 100, (g, R)
+    if sc["mode"] != "diffuse":                                       # every direction regime is fetched at EVERY level (as l0 or l1)
+        lam = np.array([oracle.mip_from_roughness(x, emin, emax, L) for x in (sc["ks"][:, 0] * np.float32(1.0 - o["min_roughness"])
+                                                                             + np.float32(o["min_roughness"]))])
+        l0 = np.minimum(np.floor(np.clip(lam, 0, L - 1)), L - 1).astype(int)
+        l1 = np.where(l0 >= L - 1, -1, l0 + 1)
+        for g in names:
+            if g in SHADE_DIR_REGIMES or g.startswith("pile"):
+                m = sc["regime"] == g
+                per_level = [int(((l0[m] == l) | (l1[m] == l)).sum()) for l in range(L)]
+                assert min(per_level) >= 3, (sc["name"], g, per_level)
+    if sc["mode"] != "diffuse" and L > 2:                             # both mip segments, and an integer level with f == 0
+        lam5 = mg[:, 5, 0]
+        assert (lam5[sc["regime"] == "r_eq_min"] == 0).all()
+    return mg
+
+
+SHADE_BUDGET_SCENES = dict(
+    # (64, 32, 16) + base 16: two levels in LDS, one through HBM atomics; min_roughness = 0 so that roughness < env min occurs
+    env3=dict(modes=("pbr", "specular", "diffuse"), kw=dict(levels_res=(64, 32, 16), base_res=16, seed=0)),
+    # four levels, a caller-supplied random FG table, max_metallic < 1, min_roughness > 0
+    env4=dict(modes=("pbr",), kw=dict(levels_res=(128, 64, 32, 16), base_res=16, min_roughness=0.03125, max_metallic=0.875,
+                                      random_lut=True, seed=1)),
+    # diffuse with a 64^2 base: the base outside LDS
+    base64=dict(modes=("diffuse",), kw=dict(levels_res=(32, 16), base_res=64, seed=2)),
+    # a single level (L = 1): always the last level
+    single16=dict(modes=("specular",), kw=dict(levels_res=(16,), base_res=16, seed=3)))
+
+SHADE_COTANGENTS = ("dense", "channel", "decades")
+
+
+def shade_budget_cotangents(kind, N, seed):
+    """colour cotangents [N,3] of the shading budget tests: 'dense' random signed, 'channel' (one channel per row live), 'decades'
+    (row amplitudes spread over six decades); in every kind each seventh row is all zeros (a Gaussian that reached no pixel: its
+    gradients must be exactly 0 and it must touch no texel)"""
+    r = np.random.RandomState(seed)
+    v = r.uniform(-1, 1, (N, 3)).astype(np.float32)
+    if kind == "channel":
+        keep = r.randint(0, 3, N)
+        v = r.uniform(-1, 1, (N, 3)).astype(np.float32) * (np.arange(3)[None] == keep[:, None])
+    elif kind == "decades":
+        v = (v * 10.0 ** r.uniform(-3.0, 3.0, (N, 1))).astype(np.float32)
+    else:
+        assert kind == "dense", kind
+    v = v.astype(np.float32)
+    v[3::7] = 0.0
+    return v
