@@ -726,3 +726,75 @@ def test_shade_bwd_budget_vs_float64_autograd(scene, mode, kind):
             assert (bb == 0).any() or a.shape[1] <= 32, nm
         r = util.assert_within_budget(f"{scene}/{mode}/{kind} {nm}", a, w, bb, util.SHADE_BUDGET_KAPPA / 2)
         print(f"    {nm:12s} {r:6.3f}")
+
+
+# ----------------------------------------------------------------------------- hash-grid field: the error budget
+@pytest.mark.parametrize("scene", list(util.FIELD_BUDGET_SCENES))
+def test_field_budget_scenes_hold_their_regimes(scene):
+    """every scene of tests/test_gpu_field_budget.py, as drawn and rounded to the dyadic grid: all regimes populated, the mesh-order
+    runs inside one cell, lattice points on 1 / 2 / 3 axes, negative cells, and rows with >= 64 contributions, with exactly one,
+    with two corners of one point, in the first and in the last slab (util.field_scene_check)"""
+    for dyadic in (False, True):
+        st = util.field_scene_check(util.field_budget_scene(scene, dyadic=dyadic))
+        print(f"  {scene} dyadic={dyadic}: {st}")
+
+
+@pytest.mark.parametrize("scene", list(util.FIELD_BUDGET_SCENES))
+def test_field_budget_vs_float64_autograd(scene):
+    """oracle/field_ref.py's float32 restatements of the features, v_x and v_table (float order and fixed point) lie within
+    (kappa / 2) * 2^-24 * budget of float64 autograd through field_ref.encode, element by element, under every cotangent kind and
+    every table-gradient scale -- on the scene rounded to multiples of 2^-10, where x01 * s is exact in float32 and both sides
+    compute the same function (elsewhere the float32 cell arithmetic makes float64 a different function).  Rows no corner reaches
+    are exactly 0 in autograd; elements with no non-zero contribution have budget 0 and are exactly 0 on both sides.
+
+    Worst ratios seen (util.FIELD_BUDGET_KAPPA / 2 = 2): features 0.41, v_x 0.26, v_table float 0.67, v_table fixed 0.98."""
+    from oracle import field_ref
+    sc = util.field_budget_scene(scene, dyadic=True)
+    util.field_scene_check(sc)
+    L, log2_T = sc["L"], sc["log2_T"]
+    table = util.field_scene_table(sc)
+    s64 = torch.tensor(sc["scalings"], dtype=torch.float64)
+    f32, f64, fb = field_ref.encode_fwd(sc["x"], table, sc["scalings"], log2_T)
+    worst = dict(features=0.0, v_x=0.0, v_table_float=0.0, v_table_fixed=0.0)
+    bar = util.FIELD_BUDGET_KAPPA / 2
+    for ki, kind in enumerate(util.FIELD_COTANGENTS):
+        tgs = util.FIELD_TGS[(ki + L) % 3]
+        cot = util.field_budget_cotangents(kind, sc, seed=11)
+        x = torch.tensor(sc["x"], dtype=torch.float64, requires_grad=True)
+        t = torch.tensor(table, dtype=torch.float64, requires_grad=True)
+        f = field_ref.encode(x, t, s64, log2_T)
+        (f * torch.tensor(cot, dtype=torch.float64)).sum().backward()
+        if ki == 0:
+            assert np.array_equal(f64, f.detach().numpy())             # the oracle's float64 forward IS autograd's function here
+            worst["features"] = util.assert_within_budget(f"{scene} features", f32, f.detach().numpy(), fb, bar)
+        vt = t.grad.numpy() * tgs
+        for mode in ("float", "fixed"):
+            b = field_ref.encode_bwd_budget(sc["x"], table, sc["scalings"], log2_T, cot, tgs, mode)
+            mask = np.ones(vt.shape[0], bool); mask[b["rows"]] = False
+            assert not vt[mask].any()
+            assert np.isfinite(b["v_table_budget"]).all() and not b["v_table_f32"][b["n"] == 0].any()
+            assert np.abs(b["v_table"] - vt[b["rows"]]).max() <= 1e-12 * np.abs(vt).max()       # two float64 sums of the same addends
+            r = util.assert_within_budget(f"{scene}/{kind} v_table {mode}", b["v_table_f32"], vt[b["rows"]], b["v_table_budget"], bar)
+            worst[f"v_table_{mode}"] = max(worst[f"v_table_{mode}"], r)
+        dead = sc["regime"] == "dead"
+        assert not b["v_x_f32"][dead].any() and not b["v_x_budget"][dead].any()
+        worst["v_x"] = max(worst["v_x"], util.assert_within_budget(f"{scene}/{kind} v_x", b["v_x_f32"], x.grad.numpy(), b["v_x_budget"], bar))
+    print("  worst " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("O,I", [(1, 1), (32, 32), (3, 32), (32, 7), (17, 5)])
+def test_wgrad_budget_vs_float64(O, I):
+    """field_ref.wgrad_f32 (a float32 sum in gs_mlp_wgrad's plan order: per wave, the four-wave fold, the strided reduce) within
+    (kappa / 2) budgets of the float64 product, every element, columns of dY and X over six decades.  Worst ratio seen: 0.08."""
+    from oracle import field_ref
+    worst = 0.0
+    for N in (1, 2, 15, 16, 17, 511, 512, 513, 4097, 70001):
+        r = np.random.RandomState(N + O)
+        dY = (r.standard_normal((N, O)) * np.logspace(-6, 0, O)).astype(np.float32)
+        X = (r.standard_normal((N, I)) * np.logspace(0, -6, I)).astype(np.float32)
+        nb = field_ref.wgrad_plan_blocks(N)
+        for scale in (1.0, -0.25):
+            want, bud = field_ref.wgrad_budget(dY, X, scale, nb)
+            got = field_ref.wgrad_f32(dY, X, scale, nb)
+            worst = max(worst, util.assert_within_budget(f"wgrad {O}x{I} N={N} scale={scale}", got, want, bud, util.FIELD_BUDGET_KAPPA / 2))
+    print(f"  worst {worst:.3f}")
