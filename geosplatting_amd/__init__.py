@@ -18,6 +18,11 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == Splats + GSplatter + GSplatTrainer + ModuleOptimizers.mutate_params: vanilla-3DGS training with
                                              adaptive density control (rfstudio/graphics/_splats.py:82-184, rfstudio/model/gsplat.py,
                                              rfstudio/trainer/gsplat_trainer.py, rfstudio/optim/optimizer.py:121-191)
+  surfels.rasterization_2dgs / SurfelModel / SurfelTrainer
+                                          == gsplat.rasterization_2dgs as GSplatter calls it with rasterize_mode='2dgs'
+                                             (rfstudio/model/gsplat.py:129-150, :217-238, :312-332), that model (normal image, distortion map,
+                                             pseudo-normals from the expected depth) and its two regularisers
+                                             (rfstudio/trainer/gsplat_trainer.py:135-139, :161-164)
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -29,6 +34,7 @@ from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
+from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401
 from . import viewbatch  # noqa: F401
 from .splitsum import TextureSplitSum, as_splitsum, diffuse_cubemap, specular_cubemap  # noqa: F401
 

@@ -55,6 +55,8 @@ SYMBOLS = [
     "gs_flexicubes_ws_bytes", "gs_flexicubes_count", "gs_flexicubes_fwd", "gs_flexicubes_bwd", "gs_flexicubes_entropy_fwd",
     "gs_flexicubes_entropy_bwd", "gs_front_ws_bytes", "gs_front_fwd", "gs_isect_bin_front_ws_bytes", "gs_isect_bin_front", "gs_tail_bwd", "gs_tail_bwd_multi", "gs_tail_bwd_multi_parts", "gs_tail_priv_ws_bytes", "gs_tail_priv_reduce", "gs_smooth_gather", "gs_smooth_fold", "gs_activation_chain",
     "gs_densify_stats", "gs_densify_ws_bytes", "gs_densify_plan", "gs_densify_fill",
+    "gs_surfel_project_ws_bytes", "gs_surfel_project_fwd", "gs_surfel_project_bwd", "gs_surfel_raster_fwd", "gs_surfel_grad_stride",
+    "gs_surfel_raster_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -110,6 +112,8 @@ def lib() -> C.CDLL:
         l.gs_raster_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
         l.gs_densify_ws_bytes.restype = C.c_size_t
         l.gs_densify_ws_bytes.argtypes = [C.c_int64, C.c_int]
+        l.gs_surfel_project_ws_bytes.restype = C.c_size_t
+        l.gs_surfel_project_ws_bytes.argtypes = [C.c_int]
         _lib = l
     return _lib
 

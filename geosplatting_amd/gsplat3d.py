@@ -404,7 +404,7 @@ class GSplatModel:
 
     def _rasterize(self, camera: Camera, render_mode: str):
         if self.rasterize_mode == "2dgs":
-            raise NotImplementedError("rasterize_mode='2dgs' (rasterization_2dgs) is not part of this package")
+            raise NotImplementedError("rasterize_mode='2dgs' (rasterization_2dgs) is geosplatting_amd.SurfelModel, not GSplatModel")
         if self.rasterize_mode not in ("antialiased", "classic"):
             raise ValueError(f"Unknown rasterize_mode: {self.rasterize_mode}")
         g = self.gaussians

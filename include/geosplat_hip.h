@@ -717,6 +717,66 @@ int gs_densify_fill(int64_t N, int num_splits, void* ws, size_t ws_bytes, int64_
                     const GsDensifyTensor* table /*host*/, int n_tensors, const float* quats, const float* scales, const float* randn,
                     int64_t* indices, void* stream);
 
+/* ------------------------------------------------------------------ 2D Gaussian splatting (surfels) -- */
+/* gsplat 1.4 `rasterization_2dgs(packed=True)`, one camera, as the reference's GSplatter calls it with rasterize_mode='2dgs'
+ * (rfstudio/model/gsplat.py:129-150, :217-238, :312-332).  csrc/gs_surfel.hip.  Only the surfel projection and the ray-splat
+ * compositor are new: binning, sort and offsets are gs_isect_bin / gs_isect_offsets on (means2d, radii, depths).
+ *
+ * gs_surfel_project_fwd: scales [N,3] activated, only [:, :2] are used.  Rc = Rcw R(q), c = Rcw mean + t; culled outside
+ * [near, far]; ray transform M = K [s0 Rc[:,0] | s1 Rc[:,1] | c] (rows M0, M1, M2); with test = (1,1,-1), d = sum test M2^2 (culled
+ * when 0), f = test / d: means2d = (sum f M0 M2, sum f M1 M2), ext = means2d^2 - (sum f M0^2, sum f M1^2),
+ * radius = ceil(3 sqrt(max(1e-4, max(ext)))); culled when radius <= radius_clip or the square means2d +- radius misses the image
+ * (gs_project_fwd's inequalities).  normal = Rc[:,2], negated when normal . c > 0 (camera space, facing the camera).
+ * Packed outputs (capacity N, ascending Gaussian index): gaussian_ids, radii, means2d [V,2], depths (= c.z), ray_transforms [V,9],
+ * normals [V,3], opacities_packed, tiles_per_gauss, colors_packed [V, Dc + depth_channel]: the colours (plain [N,Dc], or, with
+ * sh_degree in 0..3, evaluated from sh_coeffs [N,sh_K,3] exactly as gs_project_fwd_vis_ex does; Dc == 3 then) followed by the depth
+ * when depth_channel is 1.  1 <= Dc + depth_channel <= 4.  counts = {V, I} (int64) as gs_project_fwd. */
+size_t gs_surfel_project_ws_bytes(int N);
+int gs_surfel_project_fwd(int N, const float* means, const float* quats, const float* scales, const float* opacities,
+                          const float* colors, int Dc, const float* sh_coeffs, int sh_K, int sh_degree, int depth_channel,
+                          const float* viewmat, const float* K, int W, int H, int tile_size, float near_plane, float far_plane,
+                          float radius_clip, int32_t* gaussian_ids, int32_t* radii, float* means2d, float* depths,
+                          float* ray_transforms, float* normals, float* opacities_packed, float* colors_packed,
+                          int32_t* tiles_per_gauss, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+
+/* The exact derivative of the above (radii are not differentiable).  The incoming gradients are rows of `stride` floats per visible
+ * Gaussian (the columns of gs_surfel_raster_bwd's v_packed, or separate arrays with their own row length): v_ray_transforms (9),
+ * v_means2d (2), v_depths (1, nullable), v_normals (3), v_opacities (1), v_colors (Dc).  Outputs [N, .], zero for invisible Gaussians:
+ * g_means, g_quats, g_scales (third column 0), g_opacities and g_colors [N,Dc] or, with sh_degree >= 0, g_sh [N,sh_K,3]. */
+int gs_surfel_project_bwd(int N, int V, int Dc, const float* means, const float* quats, const float* scales,
+                          const float* sh_coeffs, int sh_K, int sh_degree, const float* viewmat, const float* K,
+                          const int32_t* gaussian_ids, const float* v_ray_transforms, const float* v_means2d,
+                          const float* v_depths, const float* v_normals, const float* v_opacities, const float* v_colors,
+                          int stride, float* g_means, float* g_quats, float* g_scales, float* g_opacities, float* g_colors,
+                          float* g_sh, void* stream);
+
+/* Ray-splat compositor, one tile_size x tile_size tile (8 or 16) per workgroup, front to back over the tile's sorted list.  For the
+ * pixel centre p: hu = p.x M2 - M0, hv = p.y M2 - M1, z = hu x hv (skipped when z.z == 0), s = z.xy / z.z, w3 = s.s,
+ * w2 = 2 |means2d - p|^2, sigma = min(w3, w2) / 2, alpha = min(0.999, opacity exp(-sigma)); skipped when sigma < 0 or alpha < 1/255;
+ * the pixel stops when T (1 - alpha) <= 1e-4.  C = 1, 3 or 4 channels, the last one the depth when depth_channel is 1.
+ * render [H,W,C] (+ T background on the first min(3, C - depth_channel) channels), alphas [H,W], render_normals [H,W,3] (camera space),
+ * render_median [H,W] (depth of the last Gaussian composited while T > 0.5; 0 without a depth channel), and with distloss
+ * render_distort [H,W] = sum 2 (vis d (1 - T) - vis D).  State of the backward: last_ids [H,W] (list index of the last
+ * composited entry, -1 for none), final_T [H,W], final_D [H,W] (distloss). */
+int gs_surfel_raster_fwd(int W, int H, int tile_size, int C, int depth_channel, int distloss, int V, const float* ray_transforms,
+                         const float* means2d, const float* opacities, const float* colors, const float* normals,
+                         const float* background, int64_t n_isects, const int32_t* offsets, const int32_t* flatten_ids,
+                         float* render, float* alphas, float* render_normals, float* render_distort, float* render_median,
+                         int32_t* last_ids, float* final_T, float* final_D, void* stream);
+
+/* Floats per row of v_packed: v_ray_transforms [0..9), v_means2d [9..11), v_opacities [11], v_normals [12..15), v_colors [15..15+C). */
+int gs_surfel_grad_stride(void);
+
+/* Stored-state backward, back to front, alpha recomputed.  w3 < w2: the gradient of sigma goes to ray_transforms, else to means2d;
+ * an active 0.999 clamp passes none.  v_packed [V, gs_surfel_grad_stride()] is zeroed by the call;
+ * v_densify [V,2] = depths[v] * (v_ray_transforms[v][2], v_ray_transforms[v][5]). */
+int gs_surfel_raster_bwd(int W, int H, int tile_size, int C, int depth_channel, int distloss, int V, const float* ray_transforms,
+                         const float* means2d, const float* opacities, const float* colors, const float* normals,
+                         const float* depths, const float* background, int64_t n_isects, const int32_t* offsets,
+                         const int32_t* flatten_ids, const int32_t* last_ids, const float* final_T, const float* final_D,
+                         const float* v_render, const float* v_alphas, const float* v_normals, const float* v_distort,
+                         float* v_packed, float* v_densify, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
