@@ -689,6 +689,8 @@ static int surfel_raster_args(int W, int H, int tile_size, int C, int depth_chan
 
 extern "C" int gs_surfel_grad_stride(void) { return SF_REC; }
 
+// (<3, true> is built but can never be launched: surfel_raster_args and rasterization_2dgs both refuse distloss without the depth
+// channel, and C == 3 is the mode without one.  The five launchable instantiations are the ones tests/test_gpu_surfel_budget.py runs.)
 #define SF_DISPATCH(KERNEL, ...)                                                                        \
     do {                                                                                                \
         if (distloss) {                                                                                 \

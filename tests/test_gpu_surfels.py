@@ -18,8 +18,9 @@ TOL = 1e-4
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(name):
-    return R.scene_reference(name)
+def _reference(name, render_mode="RGB+ED", distloss=True, tile_size=16, with_background=True, small=False):
+    """small: the scene at the size of the added cases (R.CALL_SCENE_ARGS)"""
+    return R.scene_reference(name, render_mode, distloss, tile_size, with_background, **(R.CALL_SCENE_ARGS.get(name, {}) if small else {}))
 
 
 def _gpu_call(sc, dev, requires_grad=True, **kw):
@@ -57,10 +58,25 @@ def _tile_count_bounds(ref, ids_got, means2d_got, radii_got, tile, tw, th):
 
 @pytest.mark.parametrize("name", ["inside", "outside", "clamp"])
 def test_forward_and_backward(cuda, name):
-    sc, ref, cot, keep, grads, densify = _reference(name)
+    _check_call(cuda, _reference(name), "RGB+ED", True, 16, True)
+
+
+@pytest.mark.parametrize("name,render_mode,distloss,tile,with_bg", R.CALL_CASES,
+                         ids=[f"{c[0]}-{c[1]}-{'dist' if c[2] else 'nodist'}-t{c[3]}-{'bg' if c[4] else 'nobg'}" for c in R.CALL_CASES])
+def test_forward_and_backward_modes(cuda, name, render_mode, distloss, tile, with_bg):
+    """every render mode, with and without distloss, at tile sizes 8 and 16, with and without a background: the ED division and the
+    depth-only column routing of the projection backward are on the path of the leaf gradients ('outside' at 400 Gaussians)"""
+    _check_call(cuda, _reference(name, render_mode, distloss, tile, with_bg, small=True), render_mode, distloss, tile, with_bg)
+
+
+def _check_call(cuda, reference, render_mode, distloss, tile, with_bg):
+    sc, ref, cot, keep, grads, densify = reference
     N, H, W = sc["means"].shape[0], sc["H"], sc["W"]
+    depth_mode, expected = render_mode != "RGB", render_mode in ("ED", "RGB+ED")
     assert (1 - keep).mean().item() <= 0.01 and ref["gauss_bad"].double().mean().item() <= 0.005
-    leaves, (render, alpha, normals, nfd, distort, median, meta) = _gpu_call(sc, cuda)
+    leaves, (render, alpha, normals, nfd, distort, median, meta) = _gpu_call(
+        sc, cuda, render_mode=render_mode, distloss=distloss, tile_size=tile, backgrounds=sc["background"].to(cuda)[None] if with_bg else None)
+    assert render.shape == (1, H, W, R.MODE_CHANNELS[render_mode]) and (distort is None) == (not distloss) and (nfd is None) == (not expected)
     meta["gradient_2dgs"].retain_grad()
 
     # ---- projection and binning
@@ -82,32 +98,41 @@ def test_forward_and_backward(cuda, name):
     assert rt_err <= TOL, rt_err
     # tile offsets and the length of the list: every tile's count, exact wherever no undecided Gaussian reaches
     tw, th = meta["tile_width"], meta["tile_height"]
-    assert (tw, th) == ((W + 15) // 16, (H + 15) // 16) and meta["isect_offsets"].shape == (1, th, tw)
+    assert (tw, th) == ((W + tile - 1) // tile, (H + tile - 1) // tile) and meta["isect_offsets"].shape == (1, th, tw)
     n_isects = meta["flatten_ids"].numel()
     offsets = meta["isect_offsets"].cpu().reshape(-1).long()
     counts_got = (torch.cat((offsets[1:], torch.tensor([n_isects]))) - offsets).reshape(th, tw)
-    lo, hi = _tile_count_bounds(ref, ids_got, meta["means2d"].detach().cpu(), meta["radii"].cpu(), 16, tw, th)
+    lo, hi = _tile_count_bounds(ref, ids_got, meta["means2d"].detach().cpu(), meta["radii"].cpu(), tile, tw, th)
     assert int(offsets[0]) == 0 and bool((counts_got >= lo).all()) and bool((counts_got <= hi).all()), (counts_got, lo, hi)
     assert int(lo.sum()) <= n_isects <= int(hi.sum())
     assert n_isects == int(meta["tiles_per_gauss"].sum())
 
     # ---- images
-    images = (("render", render[0]), ("alpha", alpha[0, ..., 0]), ("normals", normals[0]), ("distort", distort[0, ..., 0]))
+    images = (("render", render[0]), ("alpha", alpha[0, ..., 0]), ("normals", normals[0]))
+    if distloss:
+        images += (("distort", distort[0, ..., 0]),)
     for key, got in images:
         err = rel_err(_masked(got, keep), _masked(ref[key], keep))
         assert err <= TOL, (key, err)
-    keep_med = keep * (~ref["median_bad"]).double()
-    assert (1 - keep_med).mean().item() <= 0.01
-    assert rel_err(_masked(median[0, ..., 0], keep_med), _masked(ref["median"], keep_med)) <= TOL
-    assert nfd.shape == (1, H, W, 3) and float(nfd[0, 0].detach().abs().max()) == 0.0
-    nfd_want = R.depth_to_normal(render[0, ..., -1:].detach().cpu().double(), sc["viewmat"].double(), sc["K"].double())
-    assert rel_err(nfd[0].detach().cpu(), nfd_want) <= TOL
+    if depth_mode:
+        keep_med = keep * (~ref["median_bad"]).double()
+        assert (1 - keep_med).mean().item() <= 0.01
+        assert rel_err(_masked(median[0, ..., 0], keep_med), _masked(ref["median"], keep_med)) <= TOL
+    else:
+        assert float(median.abs().max()) == 0.0
+    if expected:
+        assert nfd.shape == (1, H, W, 3) and float(nfd[0, 0].detach().abs().max()) == 0.0
+        nfd_want = R.depth_to_normal(render[0, ..., -1:].detach().cpu().double(), sc["viewmat"].double(), sc["K"].double())
+        assert rel_err(nfd[0].detach().cpu(), nfd_want) <= TOL
 
     # ---- gradients under the cotangent-weighted loss
     dev_keep = keep.to(cuda).float()
     loss = sum((got * cot[key].to(cuda).float() * (dev_keep if got.dim() == 2 else dev_keep[..., None])).sum() for key, got in images)
     loss.backward()
-    errs = {key: rel_err(leaves[key].grad.cpu(), grads[key]) for key in ("means", "quats", "scales", "opacities", "sh")}
+    got_grad = lambda key: torch.zeros_like(leaves[key]) if leaves[key].grad is None else leaves[key].grad
+    errs = {key: rel_err(got_grad(key).cpu(), grads[key]) for key in ("means", "quats", "scales", "opacities", "sh")}
+    # (the depth-only modes ignore the colours: no gradient reaches them on either side)
+    assert (float(grads["sh"].abs().max()) == 0 and float(got_grad("sh").abs().max()) == 0) == (render_mode in ("D", "ED"))
     # the densification signal, row by row of the Gaussians both sides project (an undecided one touches left-out pixels only)
     errs["gradient_2dgs"] = rel_err(meta["gradient_2dgs"].grad.cpu()[rows_got], densify[rows_ref])
     assert float(densify[rows_ref].abs().max()) > 0
