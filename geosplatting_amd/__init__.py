@@ -23,12 +23,17 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              (rfstudio/model/gsplat.py:129-150, :217-238, :312-332), that model (normal image, distortion map,
                                              pseudo-normals from the expected depth) and its two regularisers
                                              (rfstudio/trainer/gsplat_trainer.py:135-139, :161-164)
+  fusion.TSDFVolume / mesh_from_depth_fusion / save_obj, GSplatModel.extract_mesh, cameras.sphere_cameras
+                                          == TriangleMesh.from_depth_fusion (rfstudio/graphics/_mesh/_triangle_mesh.py:321-388) and the
+                                             MeshExport task (tests/model/test_gsplat.py:169-202): depth maps -> dense TSDF -> marching
+                                             cubes, without Open3D
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
-from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, view_matrix  # noqa: F401
+from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, sphere_cameras, view_matrix  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401
+from .fusion import TSDFVolume, mesh_from_depth_fusion, save_obj  # noqa: F401
 from .gsplat3d import GaussianSet, GSplatModel, GSplatTrainer, mutate_adam  # noqa: F401
 from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401

@@ -39,6 +39,10 @@ class GsDensifyTensor(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("floats_per_row", C.c_int), ("kind", C.c_int)]
 
 
+class GsTsdfView(C.Structure):
+    _fields_ = [("depth_alpha", C.c_void_p), ("viewmat", C.c_void_p), ("K", C.c_void_p), ("W", C.c_int), ("H", C.c_int)]
+
+
 class GsEnvGrad(C.Structure):
     _fields_ = [("base", C.c_void_p), ("levels", C.c_void_p * GS_MAX_LEVELS)]
 
@@ -57,6 +61,7 @@ SYMBOLS = [
     "gs_densify_stats", "gs_densify_ws_bytes", "gs_densify_plan", "gs_densify_fill",
     "gs_surfel_project_ws_bytes", "gs_surfel_project_fwd", "gs_surfel_project_bwd", "gs_surfel_raster_fwd", "gs_surfel_grad_stride",
     "gs_surfel_raster_bwd",
+    "gs_tsdf_integrate", "gs_tsdf_extract_ws_bytes", "gs_tsdf_extract_count", "gs_tsdf_extract_fill",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -114,6 +119,13 @@ def lib() -> C.CDLL:
         l.gs_densify_ws_bytes.argtypes = [C.c_int64, C.c_int]
         l.gs_surfel_project_ws_bytes.restype = C.c_size_t
         l.gs_surfel_project_ws_bytes.argtypes = [C.c_int]
+        l.gs_tsdf_extract_ws_bytes.restype = C.c_size_t
+        l.gs_tsdf_extract_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        l.gs_tsdf_integrate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gs_tsdf_extract_count.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.gs_tsdf_extract_fill.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

@@ -5,7 +5,7 @@ Mirrors the part of ``rfstudio.graphics.Cameras`` that the hot path consumes:
   * ``view_matrix``   : flip y/z to the OpenCV convention the rasterizer uses, analytic inverse
                                                                           rfstudio/graphics/_cameras.py:299-314
   * ``intrinsic_matrix`` : [[fx,0,cx],[0,fy,cy],[0,0,1]]                   rfstudio/graphics/_cameras.py:289-297
-  * ``from_lookat`` / ``from_orbit`` constructors                         rfstudio/graphics/_cameras.py:68-167
+  * ``from_lookat`` / ``from_orbit`` / ``from_sphere`` constructors       rfstudio/graphics/_cameras.py:68-205
 Pinned against the importable reference by tests/golden/ref_cameras.npz.
 """
 from __future__ import annotations
@@ -102,4 +102,34 @@ def orbit_cameras(num: int, radius: float, pitch_degree: float, width: int, heig
     cx, cy = width * 0.5, height * 0.5
     if focal is None:
         focal = cx / math.tan(hfov_degree * (0.5 * math.pi / 180))
+    return [Camera(c2w[i].contiguous(), float(focal), float(focal), cx, cy, width, height) for i in range(num)]
+
+
+def _rotation_z_to(up: Tensor) -> Tensor:
+    """The rotation about z x up that takes (0, 0, 1) to up / |up| (Rodrigues); the identity for up = z."""
+    u = up / up.norm()
+    z = torch.tensor([0.0, 0.0, 1.0], dtype=u.dtype)
+    c = float(u[2])
+    if c < -1.0 + 1e-6:                                           # up = -z: half a turn about x
+        return torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=u.dtype))
+    v = torch.cross(z, u, dim=-1)
+    vx = torch.tensor([[0.0, -float(v[2]), float(v[1])], [float(v[2]), 0.0, -float(v[0])], [-float(v[1]), float(v[0]), 0.0]], dtype=u.dtype)
+    return torch.eye(3, dtype=u.dtype) + vx + vx @ vx / (1.0 + c)
+
+
+def sphere_cameras(num: int, radius: float, width: int, height: int, hfov_degree: float = 90.0,
+                   center: Sequence[float] = (0.0, 0.0, 0.0), up: Sequence[float] = (0.0, 0.0, 1.0),
+                   generator: Optional[torch.Generator] = None):
+    """`num` cameras uniformly distributed on a sphere, looking at `center` (semantics of Cameras.from_sphere,
+    rfstudio/graphics/_cameras.py:170-205: pitch = asin(2 u - 1), yaw = 2 pi u', the z axis of the sampling frame turned onto `up`;
+    cx = W/2, cy = H/2, fx = fy from the horizontal field of view).  Host tensors; `generator` seeds the two draws."""
+    upv = torch.tensor(up, dtype=torch.float32)
+    c = torch.tensor(center, dtype=torch.float32)
+    pitch = torch.asin(2 * torch.rand(num, generator=generator) - 1)
+    yaw = (2 * math.pi) * torch.rand(num, generator=generator)
+    local = torch.stack((yaw.cos() * pitch.cos(), yaw.sin() * pitch.cos(), pitch.sin()), dim=-1) * radius
+    eyes = local @ _rotation_z_to(upv).T + c
+    c2w = lookat_c2w(eyes, c.expand(num, 3), upv.expand(num, 3))
+    cx, cy = width * 0.5, height * 0.5
+    focal = cx / math.tan(hfov_degree * (0.5 * math.pi / 180))
     return [Camera(c2w[i].contiguous(), float(focal), float(focal), cx, cy, width, height) for i in range(num)]

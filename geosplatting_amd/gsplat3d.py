@@ -440,6 +440,30 @@ class GSplatModel:
         return torch.cat((render, alpha), dim=-1).squeeze(0)
 
     @torch.no_grad()
+    def extract_mesh(self, resolution: int = 512, fusing_alpha_threshold: float = 0.5, num_views: int = 100, radius: float = 3.0,
+                     image_size: int = 800, up: Sequence[float] = (0.0, 0.0, 1.0),
+                     bounds=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), generator: Optional[torch.Generator] = None) -> Tuple[Tensor, Tensor]:
+        """The MeshExport task (tests/model/test_gsplat.py:169-202) -> (vertices [V,3], faces [F,3] int64): depth from `num_views`
+        cameras on a sphere of `radius` around the centre of `bounds`, fused into a dense TSDF of `resolution` voxels along the longest
+        side (voxel_size = extent / resolution, sdf_trunc = 5 voxel_size: the task's 2 / 512 and 10 / 512), marching cubes.  Renders
+        in eval mode, at most 16 views in flight."""
+        from .cameras import sphere_cameras
+        from .fusion import MAX_VIEWS, TSDFVolume
+        lo, hi = bounds
+        center = tuple(0.5 * (float(a) + float(b)) for a, b in zip(lo, hi))
+        cams = sphere_cameras(num_views, radius, image_size, image_size, center=center, up=up, generator=generator)
+        volume = TSDFVolume(int(resolution), bounds=bounds, device=self.gaussians.device)   # sdf_trunc defaults to 5 voxels
+        was_training = self.training
+        self.eval()
+        try:
+            for first in range(0, num_views, MAX_VIEWS):
+                batch = [c.to(self.gaussians.device) for c in cams[first:first + MAX_VIEWS]]
+                volume.integrate([self.render_depth(c) for c in batch], batch, alpha_trunc=fusing_alpha_threshold)
+        finally:
+            self.train(was_training)
+        return volume.extract_mesh()
+
+    @torch.no_grad()
     def update_grad_norm(self) -> None:
         """:360-374 on gs_densify_stats"""
         assert self.update_info is not None

@@ -777,6 +777,53 @@ int gs_surfel_raster_bwd(int W, int H, int tile_size, int C, int depth_channel, 
                          const float* v_render, const float* v_alphas, const float* v_normals, const float* v_distort,
                          float* v_packed, float* v_densify, void* stream);
 
+/* ------------------------------------------------------------------ TSDF depth fusion and marching cubes -- */
+/* TriangleMesh.from_depth_fusion (rfstudio/graphics/_mesh/_triangle_mesh.py:321-388) as the MeshExport task calls it
+ * (tests/model/test_gsplat.py:169-202): Open3D's uniform-volume update with depth scale 1, no colour and unit weight per
+ * observation, on a DENSE volume with explicit bounds.  csrc/gs_tsdf.hip.
+ *
+ * Volume: R0 x R1 x R2 voxels, R0 R1 R2 < 2^31; voxel n = i0 + R0 (i1 + R1 i2); `volume` holds one interleaved (tsdf, weight)
+ * float pair per voxel, (0, 0) before the first view; voxel centre = origin + (i + 0.5) voxel_size.
+ *
+ * gs_tsdf_integrate: up to GS_TSDF_MAX_VIEWS views per call (`views` is a host array; a caller with more views calls again).  Per
+ * voxel centre p, over the views in order (viewmat rigid, world -> camera, z forward):
+ *     pc = Rwc p + t,  z = pc.z;                         skipped unless z > 0
+ *     u = fx pc.x / z + cx,  v = fy pc.y / z + cy;       skipped unless 0 <= u < W and 0 <= v < H
+ *     (d, a) = depth_alpha[floor(v), floor(u)]           pixel j covers [j, j + 1): pixel centres at j + 0.5, as the rasterizer has them
+ *     skipped unless a > alpha_trunc, and unless d > 0 and d < depth_trunc (a NaN depth skips)
+ *     sdf = d - z;                                       skipped unless sdf > -sdf_trunc
+ *     val = min(1, sdf / sdf_trunc);  tsdf = (tsdf w + val) / (w + 1);  w += 1
+ *   (1 / z and 1 / (w + 1) are the hardware reciprocal, 1 ulp.)
+ *   The order of the views per voxel is fixed, so the result does not depend on how the views are split across calls.  A view whose
+ *   frustum misses a brick of voxels is skipped for that brick (same result).  No atomics.
+ *
+ * Extraction: marching cubes over the (R0-1)(R1-1)(R2-1) cubes whose corners are voxel centres; cube (i0,i1,i2) has corner k at
+ * i + (k & 1, (k >> 1) & 1, (k >> 2) & 1).  A cube is valid iff its eight weights are > 0; a corner is inside iff tsdf < 0 (exact 0 is
+ * outside).  A grid edge is owned by the voxel at its lower end and carries a vertex iff its ends differ in sign and it belongs to
+ * at least one valid cube (no unreferenced vertices).  Vertex ids ascend by (owning voxel n, then axis 0, 1, 2); the position is
+ * pa + (ta / (ta - tb)) (pb - pa) from the lower end a.  Triangles ascend by (cube linear index, then the order of
+ * csrc/gs_mc_table.h, generated by scripts/make_mc_table.py); their normals point toward positive tsdf (free space).
+ * The count -> read totals -> fill protocol of the FlexiCubes and densify entry points:
+ *   gs_tsdf_extract_ws_bytes  workspace size: 7 bytes per voxel + 16 per 256 voxels (0: resolution out of range)
+ *   gs_tsdf_extract_count     classifies into `ws`, writes counts[4] (device int64) = {vertices, triangles, valid cubes, surface cubes}
+ *   gs_tsdf_extract_fill      after the caller has read the counts and allocated: vertices [n_vertices,3] float, faces
+ *                             [n_triangles,3] int64.  `ws` and `volume` must be what the count saw.  Rows beyond the caller's totals
+ *                             are not written; totals of 2^31 or more are an error. */
+#define GS_TSDF_MAX_VIEWS 16
+typedef struct GsTsdfView {
+    const float* depth_alpha;                       /* device [H,W,2]: (depth, alpha) per pixel, what render_depth returns */
+    const float* viewmat; const float* K;           /* device: [4,4], [3,3] */
+    int W, H;
+} GsTsdfView;
+int gs_tsdf_integrate(int R0, int R1, int R2, float origin_x, float origin_y, float origin_z, float voxel_size, float sdf_trunc,
+                      float alpha_trunc, float depth_trunc, int n_views, const GsTsdfView* views /*host array*/, float* volume,
+                      void* stream);
+size_t gs_tsdf_extract_ws_bytes(int R0, int R1, int R2);
+int gs_tsdf_extract_count(int R0, int R1, int R2, const float* volume, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+int gs_tsdf_extract_fill(int R0, int R1, int R2, float origin_x, float origin_y, float origin_z, float voxel_size, const float* volume,
+                         void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_triangles, float* vertices, int64_t* faces,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
