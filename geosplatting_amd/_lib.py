@@ -62,6 +62,8 @@ SYMBOLS = [
     "gs_surfel_project_ws_bytes", "gs_surfel_project_fwd", "gs_surfel_project_bwd", "gs_surfel_raster_fwd", "gs_surfel_grad_stride",
     "gs_surfel_raster_bwd",
     "gs_tsdf_integrate", "gs_tsdf_extract_ws_bytes", "gs_tsdf_extract_count", "gs_tsdf_extract_fill",
+    "gs_meshraster_ws_bytes", "gs_meshraster_fwd", "gs_meshraster_resolve", "gs_meshraster_bwd", "gs_mesh_interp_fwd",
+    "gs_mesh_interp_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -126,6 +128,16 @@ def lib() -> C.CDLL:
         l.gs_tsdf_extract_count.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.gs_tsdf_extract_fill.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gs_meshraster_ws_bytes.restype = C.c_size_t
+        l.gs_meshraster_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+        mesh_head = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float]
+        l.gs_meshraster_fwd.argtypes = mesh_head + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.gs_meshraster_resolve.argtypes = mesh_head + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.gs_meshraster_bwd.argtypes = mesh_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gs_mesh_interp_fwd.argtypes = [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+        l.gs_mesh_interp_bwd.argtypes = [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

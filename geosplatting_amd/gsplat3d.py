@@ -463,6 +463,15 @@ class GSplatModel:
             self.train(was_training)
         return volume.extract_mesh()
 
+    def render_mesh(self, cameras, vertices: Tensor, faces: Tensor, **kw):
+        """A mesh of this model (what extract_mesh returned) seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per
+        camera -> a dict of maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them; its depth compares with
+        render_depth's."""
+        from .meshrender import render_mesh
+        if isinstance(cameras, Camera):
+            return render_mesh(vertices, faces, cameras, **kw)
+        return [render_mesh(vertices, faces, c, **kw) for c in cameras]
+
     @torch.no_grad()
     def update_grad_norm(self) -> None:
         """:360-374 on gs_densify_stats"""

@@ -1,0 +1,224 @@
+"""A differentiable triangle-mesh rasterizer for the meshes this package extracts (FlexiCubes, TSDF + marching cubes): depth, normal,
+silhouette and face-index maps from a camera.  What the reference gets from `TriangleMesh.render(cameras, shader=NormalShader() /
+DepthShader())` and `TriangleMesh.visible_faces` (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555, rfstudio/graphics/shaders.py:
+107-132) through nvdiffrast's `rasterize` and `interpolate`; both shaders set antialias=False, which is what this module matches.
+nvdiffrast is not restated line by line: the semantics below are this project's, the kernels are csrc/gs_meshraster.hip.
+
+  rasterize_mesh(verts_cam, faces, camera_or_intrinsics, *, cull='none', near=1e-2) -> rast [H,W,4]
+  interpolate(attr, rast, faces)                                                    -> [H,W,C]
+  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals) -> dict of maps
+  visible_faces(vertices, faces, camera)                                            -> sorted unique face ids
+
+Semantics of `rasterize_mesh`
+  Inputs    verts_cam [V,3] fp32 in camera space, OpenCV convention, +z forward (what Camera.view_matrix produces); faces [F,3]
+            (int32 for the kernels; int64 is converted); fx, fy, cx, cy, H, W from a Camera or a tuple (fx, fy, cx, cy, H, W).
+            xs = fx X / Z + cx, ys = fy Y / Z + cy.  Pixel j covers [j, j + 1) and has its centre at j + 0.5 (the convention of
+            render_depth and of the TSDF integration); row 0 is the top of the image.
+  Coverage  exact and watertight.  (xs, ys) are snapped to 1/256 px, X = rint(256 xs); the three edge functions are evaluated in
+            64-bit integers at (256 px + 128, 256 py + 128) and oriented by the sign of the snapped area.  A pixel is inside when
+            all three are > 0; one that lies exactly on an edge belongs to the triangle only if that edge is a top or a left edge
+            (top-left fill rule), so a pixel on an edge shared by two triangles is covered exactly once.
+  Dropped   a triangle is dropped WHOLE, never clipped, when its snapped area is zero, when any vertex has Z <= near, or when any
+            snapped coordinate lies outside +-2^22 (+-16384 px).  The reference clips at the near plane; no object-centred camera
+            of this project reaches it.
+  Culling   cull='none' rasterizes both windings.  cull='back' keeps the faces the reference keeps (_triangle_mesh.py:539),
+            (camera_pos - centroid) . ((v1 - v0) x (v2 - v0)) > 0.  In camera space the eye is the origin and the normal is
+            orthogonal to the triangle's edges, so the test is -det[v0; v1; v2] > 0, and det[v0; v1; v2] = Z0 Z1 Z2 / (fx fy) times the
+            signed screen area (xs1 - xs0)(ys2 - ys0) - (ys1 - ys0)(xs2 - xs0).  Every kept Z is positive: a face is kept iff that
+            area is NEGATIVE (decided on the snapped area, the one coverage uses).
+  Values    at a covered pixel, from the UNSNAPPED fp32 positions taken relative to the pixel centre (the rounding error then
+            scales with the triangle, not with the image): e_i = q_{i+1} x q_{i+2}, lambda_i = e_i / sum e (not clamped),
+            perspective-correct b_i = (lambda_i / Z_i) / sum_j lambda_j / Z_j, depth = 1 / sum_j lambda_j / Z_j.
+  Depth     among the triangles covering a pixel the smallest fp32 depth wins, the lower face index on equal depth; the result
+            does not depend on launch order (one 64-bit atomic min per fragment).
+  Output    rast [H,W,4] fp32 = (b0, b1, depth, face_id + 1), all zero where empty: nvdiffrast's layout with the view depth in
+            place of z / w.  At most 2^24 faces.
+  Backward  d rast[..., :3] -> d verts_cam with the face ids held fixed, through lambda, the perspective correction and the depth.
+            The face-id channel and coverage carry no gradient: silhouette gradients need nvdiffrast's antialias pass.
+
+Differences from nvdiffrast: no near clipping, no `antialias`, view depth in the third channel, y-down pixel rows.
+Every op raises GeoSplatHipError on CPU tensors; there is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple, Union
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from .cameras import Camera
+
+Intrinsics = Union[Camera, Tuple[float, float, float, float, int, int]]
+_CULL = {"none": 0, "back": 1}
+
+
+def _intrinsics(cam: Intrinsics) -> Tuple[float, float, float, float, int, int]:
+    if isinstance(cam, Camera):
+        return float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.height), int(cam.width)
+    fx, fy, cx, cy, H, W = cam
+    return float(fx), float(fy), float(cx), float(cy), int(H), int(W)
+
+
+def _faces32(faces: Tensor) -> Tensor:
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise _lib.GeoSplatHipError("faces must be int32 or int64 [F,3]")
+    return faces.to(torch.int32).contiguous()
+
+
+def _mesh_head(v: Tensor, f: Tensor, intr, near: float):
+    fx, fy, cx, cy, H, W = intr
+    return (v.shape[0], f.shape[0], _lib.ptr(v), _lib.ptr(f), fx, fy, cx, cy, H, W, float(near))
+
+
+def rasterize_raw(verts_cam: Tensor, faces32: Tensor, intr, *, cull: str = "none", near: float = 1e-2,
+                  stats: Optional[Tensor] = None) -> Tensor:
+    """The two forward launches without autograd: gs_meshraster_fwd, gs_meshraster_resolve -> rast.  `stats` (int64[4] on the
+    device, added to): fragments and atomics of the thread-per-triangle pass, then of the wave-per-triangle pass."""
+    if cull not in _CULL:
+        raise ValueError("cull must be 'none' or 'back'")
+    lib = _lib.lib()
+    H, W = intr[4], intr[5]
+    ws_bytes = lib.gs_meshraster_ws_bytes(faces32.shape[0], H, W)
+    if ws_bytes == 0:
+        raise _lib.GeoSplatHipError("mesh or image size out of range (at most 2^24 faces, H W < 2^31)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=verts_cam.device)
+    rast = torch.empty(H, W, 4, device=verts_cam.device)
+    head = _mesh_head(verts_cam, faces32, intr, near)
+    _lib.check(lib.gs_meshraster_fwd(*head, _CULL[cull], _lib.ptr(ws), ws_bytes, _lib.ptr(stats), _lib.stream()), "gs_meshraster_fwd")
+    _lib.check(lib.gs_meshraster_resolve(*head, _lib.ptr(ws), ws_bytes, _lib.ptr(rast), _lib.stream()), "gs_meshraster_resolve")
+    return rast
+
+
+class _Rasterize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts_cam: Tensor, faces32: Tensor, intr, cull: str, near: float):
+        v = verts_cam.detach().contiguous().float()
+        rast = rasterize_raw(v, faces32, intr, cull=cull, near=near)
+        ctx.save_for_backward(v, faces32, rast)
+        ctx.intr, ctx.near = intr, near
+        return rast
+
+    @staticmethod
+    def backward(ctx, d_rast: Tensor):
+        v, f, rast = ctx.saved_tensors
+        d_vc = torch.empty_like(v)
+        _lib.check(_lib.lib().gs_meshraster_bwd(*_mesh_head(v, f, ctx.intr, ctx.near), _lib.ptr(rast),
+                                                _lib.ptr(d_rast.contiguous().float()), _lib.ptr(d_vc), _lib.stream()),
+                   "gs_meshraster_bwd")
+        return d_vc, None, None, None, None
+
+
+def rasterize_mesh(verts_cam: Tensor, faces: Tensor, camera_or_intrinsics: Intrinsics, *, cull: str = "none",
+                   near: float = 1e-2) -> Tensor:
+    """-> rast [H,W,4] = (b0, b1, view depth, face_id + 1), zeros where empty; differentiable in `verts_cam` (module docstring)."""
+    _lib.require_cuda(verts_cam, faces)
+    if verts_cam.ndim != 2 or verts_cam.shape[1] != 3:
+        raise _lib.GeoSplatHipError("verts_cam must be [V,3]")
+    if cull not in _CULL:
+        raise ValueError("cull must be 'none' or 'back'")
+    return _Rasterize.apply(verts_cam, _faces32(faces), _intrinsics(camera_or_intrinsics), cull, float(near))
+
+
+class _Interpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr: Tensor, rast: Tensor, faces32: Tensor):
+        a = attr.detach().contiguous().float()
+        r = rast.detach().contiguous().float()
+        per_face_vertex = int(a.ndim == 3)
+        C, F = a.shape[-1], faces32.shape[0]
+        V = 0 if per_face_vertex else a.shape[0]
+        P = r.numel() // 4
+        out = torch.empty(*r.shape[:-1], C, device=a.device)
+        _lib.check(_lib.lib().gs_mesh_interp_fwd(P, C, F, V, per_face_vertex, _lib.ptr(r), _lib.ptr(faces32), _lib.ptr(a), _lib.ptr(out),
+                                                 _lib.stream()), "gs_mesh_interp_fwd")
+        ctx.save_for_backward(a, r, faces32)
+        ctx.dims = (P, C, F, V, per_face_vertex)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        a, r, f = ctx.saved_tensors
+        d_attr = torch.empty_like(a)
+        d_rast = torch.empty_like(r) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().gs_mesh_interp_bwd(*ctx.dims, _lib.ptr(r), _lib.ptr(f), _lib.ptr(a), _lib.ptr(d_out.contiguous().float()),
+                                                 _lib.ptr(d_attr), _lib.ptr(d_rast), _lib.stream()), "gs_mesh_interp_bwd")
+        return d_attr, d_rast, None
+
+
+def interpolate(attr: Tensor, rast: Tensor, faces: Tensor) -> Tensor:
+    """out[p] = sum_i b_i attr_i at the face rast names, b2 = 1 - b0 - b1; zeros where empty.  `attr` [V,C]: per-vertex attributes
+    through the face's vertex indices (nvdiffrast's interpolate); [F,3,C]: per-face-vertex attributes (the reference's
+    facial_vertex_attribute_map).  Differentiable in `attr` and in rast[..., :2]."""
+    _lib.require_cuda(attr, rast, faces)
+    f = _faces32(faces)
+    if rast.ndim < 2 or rast.shape[-1] != 4:
+        raise _lib.GeoSplatHipError("rast must be [...,4]")
+    if not (attr.ndim == 2 or (attr.ndim == 3 and attr.shape[1] == 3 and attr.shape[0] == f.shape[0])) or attr.shape[-1] < 1:
+        raise _lib.GeoSplatHipError("attr must be [V,C] or [F,3,C]")
+    return _Interpolate.apply(attr, rast, f)
+
+
+def _unit_or_z(v: Tensor) -> Tensor:
+    """rfstudio.graphics.math.safe_normalize: unit vectors, (0, 0, 1) where the length is below 1e-6"""
+    n = v.norm(dim=-1, keepdim=True)
+    z = torch.zeros(3, device=v.device, dtype=v.dtype)
+    z[2].fill_(1.0)
+    return torch.where(n < 1e-6, z, v / n.clamp_min(1e-6))
+
+
+def to_camera_space(vertices: Tensor, camera: Camera) -> Tensor:
+    """world -> camera (OpenCV) through Camera.view_matrix, written elementwise; plain torch, differentiable"""
+    M = camera.view_matrix.to(vertices.device, torch.float32)
+    R, t = M[:3, :3], M[:3, 3]
+    v = vertices.float()
+    return v[:, 0:1] * R[:, 0] + v[:, 1:2] * R[:, 1] + v[:, 2:3] * R[:, 2] + t
+
+
+def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Sequence[str] = ("depth", "normal", "alpha", "face"),
+                normal_type: str = "vertex", cull: str = "back", vertex_normals: Optional[Tensor] = None,
+                near: float = 1e-2) -> Dict[str, Tensor]:
+    """World-space mesh seen from `camera` -> {'rast' [H,W,4] and the requested maps}:
+      depth  [H,W,1]  interpolated view depth (DepthShader), 0 where empty
+      normal [H,W,3]  world-space normals (NormalShader): 'vertex' safe_normalize of the interpolated `vertex_normals` (default: the
+                      area-weighted gs.vertex_normals), 'flat' the unit face normal of the winning face
+      alpha  [H,W,1]  rast[..., 3:] > 0 as float
+      face   [H,W,1]  int64 face index, -1 where empty (ShadingContext.face_indices)
+    depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not."""
+    _lib.require_cuda(vertices, faces)
+    unknown = set(outputs) - {"depth", "normal", "alpha", "face"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    if normal_type not in ("vertex", "flat"):
+        raise ValueError("normal_type must be 'vertex' or 'flat'")
+    f32 = _faces32(faces)
+    vc = to_camera_space(vertices, camera)
+    rast = rasterize_mesh(vc, f32, camera, cull=cull, near=near)
+    out: Dict[str, Tensor] = {"rast": rast}
+    if "depth" in outputs:
+        out["depth"] = interpolate(vc[:, 2:3].contiguous(), rast, f32)
+    if "normal" in outputs:
+        if normal_type == "vertex":
+            if vertex_normals is None:
+                from .mesh import vertex_normals as compute_vertex_normals
+                vertex_normals = compute_vertex_normals(vertices.float(), faces.to(torch.int64))
+            out["normal"] = _unit_or_z(interpolate(vertex_normals, rast, f32))
+        else:
+            fl = faces.to(torch.int64)
+            v = vertices.float()
+            fn = _unit_or_z(torch.cross(v[fl[:, 1]] - v[fl[:, 0]], v[fl[:, 2]] - v[fl[:, 0]], dim=-1))
+            out["normal"] = fn[(rast[..., 3].long() - 1).clamp_min(0)]          # (face_attribute_map: face 0 where empty)
+    if "alpha" in outputs:
+        out["alpha"] = (rast[..., 3:] > 0).float()
+    if "face" in outputs:
+        out["face"] = rast[..., 3:].long() - 1
+    return out
+
+
+def visible_faces(vertices: Tensor, faces: Tensor, camera: Camera, *, cull: str = "none", near: float = 1e-2) -> Tensor:
+    """TriangleMesh.visible_faces: the sorted unique ids of the faces that own at least one pixel (no culling, as there)."""
+    _lib.require_cuda(vertices, faces)
+    with torch.no_grad():
+        rast = rasterize_mesh(to_camera_space(vertices, camera), faces, camera, cull=cull, near=near)
+    ids = rast[..., 3]
+    return (ids[ids > 0].long() - 1).unique()

@@ -229,6 +229,15 @@ class Stage1Model:
         return get_geometry(self.grid, self.deform_params, self.sdf_params, self.weight_params, scale=self.scale,
                             resolution=self.resolution, sdf_weight=self.sdf_weight)
 
+    def render_mesh(self, cameras, **kw):
+        """The extracted FlexiCubes mesh seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per camera -> a dict of
+        maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them.  Differentiable in the geometry parameters."""
+        from .meshrender import render_mesh
+        (v, f), _ = self.get_geometry()
+        if isinstance(cameras, Camera):
+            return render_mesh(v, f, cameras, **kw)
+        return [render_mesh(v, f, c, **kw) for c in cameras]
+
     def get_envmap(self):
         """:780-785 -> (TextureSplitSum, white-balance regulariser)"""
         white = self.cubemap.mean(-1, keepdim=True)

@@ -824,6 +824,44 @@ int gs_tsdf_extract_fill(int R0, int R1, int R2, float origin_x, float origin_y,
                          void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_triangles, float* vertices, int64_t* faces,
                          void* stream);
 
+/* ------------------------------------------------------------------ triangle-mesh rasterizer ------------- */
+/* What TriangleMesh.render / visible_faces (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555) get from nvdiffrast's rasterize and
+ * interpolate with the NormalShader / DepthShader (antialias = False); a restatement of the semantics.  csrc/gs_meshraster.hip.
+ *
+ * Inputs: camera-space vertices vc [V,3] (OpenCV, +z forward), faces [F,3] int32 (F <= 2^24), fx fy cx cy, H W, near.
+ *   xs = fx X / Z + cx,  ys = fy Y / Z + cy;  pixel j covers [j, j + 1), centre j + 0.5, row 0 on top.
+ * Coverage: (xs, ys) are snapped to 1/256 px (rint); the three edge functions are 64-bit integers evaluated at
+ *   (256 px + 128, 256 py + 128) and oriented by the sign of the snapped area; a pixel is inside when all three are > 0, or = 0 on a
+ *   top or left edge (top-left rule: a pixel on a shared edge belongs to exactly one triangle).  A triangle is DROPPED whole (no
+ *   clipping) when its snapped area is 0, any Z <= near, any snapped coordinate is outside +-2^22, or an index is outside [0, V).
+ * cull: 0 none; 1 'back' keeps (camera - centroid) . ((v1 - v0) x (v2 - v0)) > 0, which is: snapped signed area
+ *   (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) < 0.
+ * Values at a covered pixel, from the unsnapped fp32 positions relative to the pixel centre q_i = (xs_i, ys_i) - centre:
+ *   e_i = q_{i+1} x q_{i+2},  lambda_i = e_i / sum e (not clamped),  b_i = (lambda_i / Z_i) / sum_j lambda_j / Z_j,
+ *   depth = 1 / sum_j lambda_j / Z_j   (evaluated as b_i = e_i / Z_i / N, depth = sum e / N, N = sum_j e_j / Z_j).
+ * Depth test: the smallest fp32 depth wins, the lower face index on equal depth; a 64-bit atomic min of (depth bits << 32 | face),
+ *   so the result does not depend on launch order.
+ *
+ *   gs_meshraster_ws_bytes  8 bytes per pixel + 4 per face + 32 (0: sizes out of range)
+ *   gs_meshraster_fwd       fills the key buffer in `ws`.  `stats` (optional, device uint64[4], ADDED to) = {fragments and atomics of
+ *                           the thread-per-triangle pass, fragments and atomics of the wave-per-triangle pass}
+ *   gs_meshraster_resolve   ws -> rast [H,W,4] = (b0, b1, depth, face + 1), zeros where empty
+ *   gs_meshraster_bwd       d_rast [H,W,4] (channels 0..2 used) -> d_vc [V,3] (overwritten), face ids fixed; no gradient from coverage
+ *   gs_mesh_interp_fwd      out [P,C] = b0 a0 + b1 a1 + (1 - b0 - b1) a2 with a_i = attr[faces[f][i]] (attr [V,C]) or, with
+ *                           per_face_vertex, attr[f][i] (attr [F,3,C]); zeros where empty
+ *   gs_mesh_interp_bwd      d_out -> d_attr (overwritten; fp32 atomic adds) and d_rast [P,4] = (d b0, d b1, 0, 0) (may be null) */
+size_t gs_meshraster_ws_bytes(int64_t F, int H, int W);
+int gs_meshraster_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                      float near, int cull, void* ws, size_t ws_bytes, uint64_t* stats, void* stream);
+int gs_meshraster_resolve(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H,
+                          int W, float near, const void* ws, size_t ws_bytes, float* rast, void* stream);
+int gs_meshraster_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                      float near, const float* rast, const float* d_rast, float* d_vc, void* stream);
+int gs_mesh_interp_fwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vertex, const float* rast, const int32_t* faces,
+                       const float* attr, float* out, void* stream);
+int gs_mesh_interp_bwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vertex, const float* rast, const int32_t* faces,
+                       const float* attr, const float* d_out, float* d_attr, float* d_rast, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
