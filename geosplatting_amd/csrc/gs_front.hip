@@ -45,7 +45,22 @@ __device__ __forceinline__ unsigned wave_max_u32_lane63(unsigned v)
     return v;
 }
 
-__global__ void __launch_bounds__(GS_PROJ_BLOCK)
+// Shape of the front kernel: a workgroup of GS_FRONT_BLOCK threads handles one chunk of the chained scan, GS_FRONT_ITEMS Gaussians
+// per thread, block-strided (item k of thread tid is Gaussian chunk * GS_FRONT_CHUNK + k * GS_FRONT_BLOCK + tid: every load and
+// store stays coalesced).  Inside the engine's step the front runs in the wave slots the compositor and the background tails leave
+// free, so a resident wave is the scarce thing: each carries the loads, projections and texture taps of several independent
+// Gaussians through one block lifetime (one ticket, one aggregate, one look-back, one histogram flush per chunk).  The call shape
+// (gs_project.hip) keeps GS_PROJ_BLOCK-sized chunks of one Gaussian per thread.
+#define GS_FRONT_BLOCK 256
+#define GS_FRONT_ITEMS 2
+#define GS_FRONT_WAVES (GS_FRONT_BLOCK / 64)
+#define GS_FRONT_CHUNK (GS_FRONT_BLOCK * GS_FRONT_ITEMS)
+#define GS_FRONT_PARTS (GS_FRONT_ITEMS * GS_FRONT_WAVES)       // partials of the block scan, in ascending Gaussian order: item-major
+
+// Registers: 128 VGPRs, no scratch, 22 SGPRs spilled to VGPR lanes, four waves per SIMD -- but only under the waves-per-SIMD hint
+// (130 VGPRs and three waves without it; the one-item kernel took 99).  The kernel sits AT the cap: 512 x 2 and 256 x 4 spill to
+// scratch, and so may this shape after a change of the code or the compiler -- read the resource-usage remarks.
+__global__ void __launch_bounds__(GS_FRONT_BLOCK) __attribute__((amdgpu_waves_per_eu(4)))     // (<= 128 VGPRs)
 front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
                  const float* __restrict__ opacities, const float* __restrict__ normals, const float* __restrict__ kd,
                  const float* __restrict__ ks, const float* __restrict__ viewmat, const float* __restrict__ K,
@@ -57,23 +72,23 @@ front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
                  unsigned* __restrict__ tile_counts /* [tile_w * tile_h] or NULL */, int32_t* __restrict__ packed_index /* [N] or NULL */,
                  int tight_tiles)
 {
-    // intersections per TILE, counted here -- in Gaussian-index order, where neighbours on the surface share their tiles (a block of
-    // 512 Gaussians touches a few dozen tiles; in the depth order of the emission it touched ~1 900 of the 2 500, one atomic each) --
+    // intersections per TILE, counted here -- in Gaussian-index order, where neighbours on the surface share their tiles (a chunk of
+    // Gaussians touches a few dozen tiles; in the depth order of the emission it touched ~1 900 of the 2 500, one atomic each) --
     // in an LDS histogram flushed with one atomic per touched tile: the binning turns the counters into the tile offsets
     extern __shared__ unsigned s_th[];
     const int n_tiles = tile_w * tile_h;
-    if (tile_counts) for (int t = threadIdx.x; t < n_tiles; t += GS_PROJ_BLOCK) s_th[t] = 0u;
+    if (tile_counts) for (int t = threadIdx.x; t < n_tiles; t += GS_FRONT_BLOCK) s_th[t] = 0u;
     __shared__ int s_chunk;
-    __shared__ int s_wv[GS_PROJ_WAVES];
-    __shared__ int s_wi[GS_PROJ_WAVES];
-    __shared__ unsigned s_wmx[GS_PROJ_WAVES], s_wmn[GS_PROJ_WAVES];
+    __shared__ int s_wv[GS_FRONT_PARTS];
+    __shared__ int s_wi[GS_FRONT_PARTS];
+    __shared__ unsigned s_wmx[GS_FRONT_WAVES], s_wmn[GS_FRONT_WAVES];
     __shared__ long long s_base[2];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_chunk = (int)atomicAdd(ctrl, 1u);
     __syncthreads();
     const int chunk = s_chunk;
-    const int n = chunk * GS_PROJ_BLOCK + tid;
+    const int n0 = chunk * GS_FRONT_CHUNK + tid;              // item k: n0 + k * GS_FRONT_BLOCK
 
     u64* agg_v = desc;
     u64* agg_i = desc + n_chunks;
@@ -81,32 +96,48 @@ front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
     u64* pre_i = desc + 3 * (size_t)n_chunks;
 
     const GsCam cam = load_cam(viewmat, K);
-    ProjFwd p;
-    p.valid = false; p.radius = 0;
-    int ntiles = 0;
-    int tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
-    float mean[3] = { 0.f, 0.f, 0.f };
-    float op = 0.0f, hx = -1.0f, hy = -1.0f;
-    if (n < N) {
-        mean[0] = means[3 * (size_t)n]; mean[1] = means[3 * (size_t)n + 1]; mean[2] = means[3 * (size_t)n + 2];
-        const float4 q = *reinterpret_cast<const float4*>(quats + 4 * (size_t)n);
-        const float quat[4] = { q.x, q.y, q.z, q.w };
-        const float scale[3] = { scales[3 * (size_t)n], scales[3 * (size_t)n + 1], scales[3 * (size_t)n + 2] };
-        p = project_exact(cam, mean, quat, scale, (float)W, (float)H, eps2d, near_plane, far_plane, radius_clip);
-        if (p.valid) {
-            tile_range_exact(p.m2x, p.m2y, p.radius, tile_size, tile_w, tile_h, tx0, ty0, tx1, ty1);
-            op = opacities[n] * p.comp;
-            if (!alpha_extent(p.ca, p.cb, p.cc, op, hx, hy)) { hx = -1.0f; hy = -1.0f; }
+
+    // ---- every parameter load of every item, before the first use.  A row past the end reads row N - 1 (a load under a branch
+    //      would drain the loads in flight at the join) and is marked invalid below.
+    float mean[GS_FRONT_ITEMS][3], scale[GS_FRONT_ITEMS][3], opac[GS_FRONT_ITEMS];
+    float4 qv[GS_FRONT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+        const int n = n0 + k * GS_FRONT_BLOCK;
+        const size_t nn = (size_t)(n < N ? n : N - 1);
+        mean[k][0] = means[3 * nn]; mean[k][1] = means[3 * nn + 1]; mean[k][2] = means[3 * nn + 2];
+        qv[k] = *reinterpret_cast<const float4*>(quats + 4 * nn);
+        scale[k][0] = scales[3 * nn]; scale[k][1] = scales[3 * nn + 1]; scale[k][2] = scales[3 * nn + 2];
+        opac[k] = opacities[nn];
+    }
+
+    // ---- the projections
+    ProjFwd p[GS_FRONT_ITEMS];
+    int ntiles[GS_FRONT_ITEMS];
+    unsigned rect0[GS_FRONT_ITEMS], rect1[GS_FRONT_ITEMS];    // tx0 | ty0 << 16, tx1 | ty1 << 16
+    float op[GS_FRONT_ITEMS], hx[GS_FRONT_ITEMS], hy[GS_FRONT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+        const int n = n0 + k * GS_FRONT_BLOCK;
+        const float quat[4] = { qv[k].x, qv[k].y, qv[k].z, qv[k].w };
+        p[k] = project_exact(cam, mean[k], quat, scale[k], (float)W, (float)H, eps2d, near_plane, far_plane, radius_clip);
+        if (n >= N) { p[k].valid = false; p[k].radius = 0; }
+        int tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
+        ntiles[k] = 0; op[k] = 0.0f; hx[k] = -1.0f; hy[k] = -1.0f;
+        if (p[k].valid) {
+            tile_range_exact(p[k].m2x, p[k].m2y, p[k].radius, tile_size, tile_w, tile_h, tx0, ty0, tx1, ty1);
+            op[k] = opac[k] * p[k].comp;
+            if (!alpha_extent(p[k].ca, p[k].cb, p[k].cc, op[k], hx[k], hy[k])) { hx[k] = -1.0f; hy[k] = -1.0f; }
             if (tight_tiles) {
                 // gsplat's tile rectangle is the square of radius ceil(3 sigma_max); a pixel can only composite this Gaussian inside
                 // the axis-aligned extent of {alpha >= 1/255} (alpha_extent: the SAME conservative extents the compositor culls its
                 // quadrants with, so dropping the tiles outside them changes no pixel).  A caller that returns gsplat's `meta` keeps
                 // the square; the engine does not: 22 % fewer intersections to sort, stream and cull on the bench scene.
-                if (hx < 0.0f) { tx1 = tx0; ty1 = ty0; }                  // can never reach alpha_min: no tile at all
+                if (hx[k] < 0.0f) { tx1 = tx0; ty1 = ty0; }               // can never reach alpha_min: no tile at all
                 else {
                     const float ts = (float)tile_size;
-                    const float fx0 = floorf((p.m2x - hx) / ts), fy0 = floorf((p.m2y - hy) / ts);
-                    const float fx1 = ceilf((p.m2x + hx) / ts), fy1 = ceilf((p.m2y + hy) / ts);
+                    const float fx0 = floorf((p[k].m2x - hx[k]) / ts), fy0 = floorf((p[k].m2y - hy[k]) / ts);
+                    const float fx1 = ceilf((p[k].m2x + hx[k]) / ts), fy1 = ceilf((p[k].m2y + hy[k]) / ts);
                     const int ax0 = fx0 < 0.0f ? 0 : (fx0 > (float)tile_w ? tile_w : (int)fx0), ax1 = fx1 < 0.0f ? 0 : (fx1 > (float)tile_w ? tile_w : (int)fx1);
                     const int ay0 = fy0 < 0.0f ? 0 : (fy0 > (float)tile_h ? tile_h : (int)fy0), ay1 = fy1 < 0.0f ? 0 : (fy1 > (float)tile_h ? tile_h : (int)fy1);
                     tx0 = max(tx0, ax0); tx1 = min(tx1, ax1); ty0 = max(ty0, ay0); ty1 = min(ty1, ay1);
@@ -114,46 +145,74 @@ front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
                     if (ty1 < ty0) ty1 = ty0;
                 }
             }
-            ntiles = (tx1 - tx0) * (ty1 - ty0);
+            ntiles[k] = (tx1 - tx0) * (ty1 - ty0);
         }
+        rect0[k] = (unsigned)tx0 | ((unsigned)ty0 << 16);
+        rect1[k] = (unsigned)tx1 | ((unsigned)ty1 << 16);
     }
 
-    // ---- block-level scan of (valid, ntiles); the chunk's aggregate goes out at once
-    const u64 bal = __ballot(p.valid);
-    const int v_excl_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    int i_incl = ntiles;
-    i_incl = gs_wave_incl_scan(i_incl);
-    const unsigned dbits = p.valid ? __float_as_uint(p.depth) : 0u;
+    // ---- block-level scan of (valid, ntiles) over GS_FRONT_ITEMS x waves partials; the chunk's aggregate goes out at once
+    int v_excl_wave[GS_FRONT_ITEMS];
+    unsigned dbits[GS_FRONT_ITEMS];
+    bool any_valid = false;
     {
-        const unsigned mx = wave_max_u32_lane63(dbits), mn = wave_max_u32_lane63(p.valid ? ~dbits : 0u);
-        if (lane == 63) { s_wv[wave] = __popcll(bal); s_wi[wave] = i_incl; s_wmx[wave] = mx; s_wmn[wave] = mn; }
+        unsigned dmx = 0u, dmn = 0u;
+#pragma unroll
+        for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+            const u64 bal = __ballot(p[k].valid);
+            v_excl_wave[k] = __popcll(bal & ((1ull << lane) - 1ull));
+            const int i_incl = gs_wave_incl_scan(ntiles[k]);
+            if (lane == 63) { s_wv[k * GS_FRONT_WAVES + wave] = __popcll(bal); s_wi[k * GS_FRONT_WAVES + wave] = i_incl; }
+            dbits[k] = p[k].valid ? __float_as_uint(p[k].depth) : 0u;
+            const unsigned nb = p[k].valid ? ~dbits[k] : 0u;
+            dmx = dbits[k] > dmx ? dbits[k] : dmx; dmn = nb > dmn ? nb : dmn;
+            any_valid = any_valid || p[k].valid;
+        }
+        const unsigned mx = wave_max_u32_lane63(dmx), mn = wave_max_u32_lane63(dmn);
+        if (lane == 63) { s_wmx[wave] = mx; s_wmn[wave] = mn; }
     }
     __syncthreads();
-    int v_before = 0, i_before = 0, aggV = 0, aggI = 0;
+    int aggV = 0, aggI = 0;                                   // (v_excl_wave[k] becomes the item's slot within the chunk)
 #pragma unroll
-    for (int w = 0; w < GS_PROJ_WAVES; ++w) {
-        if (w < wave) { v_before += s_wv[w]; i_before += s_wi[w]; }
-        aggV += s_wv[w]; aggI += s_wi[w];
+    for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+#pragma unroll
+        for (int w = 0; w < GS_FRONT_WAVES; ++w) {
+            if (w == wave) v_excl_wave[k] += aggV;
+            aggV += s_wv[k * GS_FRONT_WAVES + w]; aggI += s_wi[k * GS_FRONT_WAVES + w];
+        }
     }
     if (wave == 0 && lane == 0 && chunk > 0) { desc_store(&agg_v[chunk], (u64)aggV); desc_store(&agg_i[chunk], (u64)aggI); }
 
-    const bool range_wave = wave == GS_PROJ_WAVES - 1;        // (not the first one: that one walks the look-back)
+    const bool range_wave = wave == GS_FRONT_WAVES - 1;       // (not the first one: that one walks the look-back)
     unsigned long long cur_mx = 0ull, cur_mn = 0ull;
     if (range_wave && lane == 0 && aggV != 0) {
         cur_mx = __hip_atomic_load(counts + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         cur_mn = __hip_atomic_load(counts + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 
-    // ---- shading of the visible Gaussians (texture taps in flight while the predecessors publish)
-    float color[3] = { 0.f, 0.f, 0.f };
-    if (p.valid && vis != nullptr) {                          // (vis == NULL: geometry only -- keys, rectangles, counts, slots)
-        const float nrm[3] = { normals[3 * (size_t)n], normals[3 * (size_t)n + 1], normals[3 * (size_t)n + 2] };
-        const float kdn[3] = { kd[3 * (size_t)n], kd[3 * (size_t)n + 1], kd[3 * (size_t)n + 2] };
-        const float2 ks2 = *reinterpret_cast<const float2*>(ks + 2 * (size_t)n);
-        const float ksn[2] = { ks2.x, ks2.y };
+    // ---- shading of the visible Gaussians (texture taps in flight while the predecessors publish).  ONE branch for all items of
+    //      a lane: inside it the attribute loads of every item go out together, then the taps of every item (an item that is not
+    //      visible is shaded like any Gaussian of gs_shade_fwd and its colour dropped).
+    float color[GS_FRONT_ITEMS][3];
+#pragma unroll
+    for (int k = 0; k < GS_FRONT_ITEMS; ++k) { color[k][0] = 0.f; color[k][1] = 0.f; color[k][2] = 0.f; }
+    if (any_valid && vis != nullptr) {                        // (vis == NULL: geometry only -- keys, rectangles, counts, slots)
+        float nrm[GS_FRONT_ITEMS][3], kdn[GS_FRONT_ITEMS][3], ksn[GS_FRONT_ITEMS][2];
+#pragma unroll
+        for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+            const int n = n0 + k * GS_FRONT_BLOCK;
+            const size_t nn = (size_t)(n < N ? n : N - 1);
+            nrm[k][0] = normals[3 * nn]; nrm[k][1] = normals[3 * nn + 1]; nrm[k][2] = normals[3 * nn + 2];
+            kdn[k][0] = kd[3 * nn]; kdn[k][1] = kd[3 * nn + 1]; kdn[k][2] = kd[3 * nn + 2];
+            const float2 ks2 = *reinterpret_cast<const float2*>(ks + 2 * nn);
+            ksn[k][0] = ks2.x; ksn[k][1] = ks2.y;
+        }
         const float cp[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
-        ShadeTmp t;
-        shade_one<false>(mean, nrm, kdn, ksn, cp, min_roughness, max_metallic, mode, env, color, t);
+#pragma unroll
+        for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+            ShadeTmp t;
+            shade_one<false>(mean[k], nrm[k], kdn[k], ksn[k], cp, min_roughness, max_metallic, mode, env, color[k], t);
+        }
     }
     // depth range of the view (the engine sizes its 24-bit keys by it, one step later).  The maxima only grow, so a relaxed -- possibly
     // stale, never too large -- read of the current value decides whether this BLOCK can still raise it: a handful of atomics per
@@ -165,15 +224,23 @@ front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
     if (range_wave && lane == 0 && aggV != 0) {
         unsigned mx = 0u, mn = 0u;
 #pragma unroll
-        for (int w = 0; w < GS_PROJ_WAVES; ++w) { mx = s_wmx[w] > mx ? s_wmx[w] : mx; mn = s_wmn[w] > mn ? s_wmn[w] : mn; }
+        for (int w = 0; w < GS_FRONT_WAVES; ++w) { mx = s_wmx[w] > mx ? s_wmx[w] : mx; mn = s_wmn[w] > mn ? s_wmn[w] : mn; }
         if ((unsigned long long)mx > cur_mx) atomicMax(counts + 3, (unsigned long long)mx);
         if ((unsigned long long)mn > cur_mn) atomicMax(counts + 2, (unsigned long long)mn);
     }
-    unsigned key = dbits;
-    if (key_limit != 0u) {
-        const bool fits = dbits >= key_base && (dbits - key_base) < key_limit;
-        if (p.valid && !fits && status) status[3] = 1;                        // (sticky; the engine then falls back to 32-bit keys)
-        key = fits ? dbits - key_base : (dbits < key_base ? 0u : key_limit - 1u);
+    unsigned key[GS_FRONT_ITEMS];
+    {
+        bool outside = false;
+#pragma unroll
+        for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+            key[k] = dbits[k];
+            if (key_limit != 0u) {
+                const bool fits = dbits[k] >= key_base && (dbits[k] - key_base) < key_limit;
+                outside = outside || (p[k].valid && !fits);
+                key[k] = fits ? dbits[k] - key_base : (dbits[k] < key_base ? 0u : key_limit - 1u);
+            }
+        }
+        if (outside && status) status[3] = 1;                                     // (sticky; the engine then falls back to 32-bit keys)
     }
 
     // ---- decoupled look-back across chunks (wave 0): see project_fwd_kernel
@@ -224,27 +291,34 @@ front_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
         }
     }
     __syncthreads();
-    if (packed_index && n < N) packed_index[n] = p.valid ? (int32_t)(s_base[0] + v_before + v_excl_wave) : -1;
-    if (p.valid) {
-        const long long slot = s_base[0] + v_before + v_excl_wave;
-        if (vis != nullptr) {
-            float4* rec = vis + 4 * slot;
-            rec[0] = make_float4(p.m2x, p.m2y, 0.5f * p.ca, p.cb);
-            rec[1] = make_float4(0.5f * p.cc, op, hx, hy);
-            rec[2] = make_float4(color[0], color[1], color[2], 0.0f);
-            rec[3] = make_float4(p.comp, __int_as_float(n), p.depth, __int_as_float(p.radius));
+    const long long slot_base = s_base[0];
+#pragma unroll
+    for (int k = 0; k < GS_FRONT_ITEMS; ++k) {
+        const int n = n0 + k * GS_FRONT_BLOCK;
+        const long long slot = slot_base + v_excl_wave[k];
+        if (packed_index && n < N) packed_index[n] = p[k].valid ? (int32_t)slot : -1;
+        if (p[k].valid) {
+            if (vis != nullptr) {
+                float4* rec = vis + 4 * slot;
+                rec[0] = make_float4(p[k].m2x, p[k].m2y, 0.5f * p[k].ca, p[k].cb);
+                rec[1] = make_float4(0.5f * p[k].cc, op[k], hx[k], hy[k]);
+                rec[2] = make_float4(color[k][0], color[k][1], color[k][2], 0.0f);
+                rec[3] = make_float4(p[k].comp, __int_as_float(n), p[k].depth, __int_as_float(p[k].radius));
+            }
+            if (depth_keys != nullptr) {
+                depth_keys[slot] = key[k];
+                rects[slot] = make_uint2(rect0[k], rect1[k]);
+            }
+            if (tile_counts) {
+                const int tx0 = (int)(rect0[k] & 0xffffu), ty0 = (int)(rect0[k] >> 16), tx1 = (int)(rect1[k] & 0xffffu), ty1 = (int)(rect1[k] >> 16);
+                for (int i = ty0; i < ty1; ++i)
+                    for (int j = tx0; j < tx1; ++j) atomicAdd(&s_th[i * tile_w + j], 1u);
+            }
         }
-        if (depth_keys != nullptr) {
-            depth_keys[slot] = key;
-            rects[slot] = make_uint2((unsigned)tx0 | ((unsigned)ty0 << 16), (unsigned)tx1 | ((unsigned)ty1 << 16));
-        }
-        if (tile_counts)
-            for (int i = ty0; i < ty1; ++i)
-                for (int j = tx0; j < tx1; ++j) atomicAdd(&s_th[i * tile_w + j], 1u);
     }
     if (tile_counts) {
         __syncthreads();
-        for (int t = threadIdx.x; t < n_tiles; t += GS_PROJ_BLOCK) { const unsigned c = s_th[t]; if (c) atomicAdd(tile_counts + t, c); }
+        for (int t = threadIdx.x; t < n_tiles; t += GS_FRONT_BLOCK) { const unsigned c = s_th[t]; if (c) atomicAdd(tile_counts + t, c); }
     }
 }
 
@@ -259,7 +333,9 @@ front_setup_kernel(unsigned* __restrict__ ws, int ws_words, unsigned long long* 
 }
 
 #define GS_FRONT_HIST_MAX 8192               // tiles whose counters fit a block's LDS histogram (32 KB); gs_isect_bin_front agrees
-extern "C" size_t gs_front_ws_bytes(int N) { return (gs_project_ws_bytes(N) + 15) & ~(size_t)15; }
+// ticket + error flag (16 bytes), then four u64 rows of one word per chunk of GS_FRONT_CHUNK Gaussians (gs_project_dev.h)
+static int front_chunks(int N) { return N > 0 ? (N + GS_FRONT_CHUNK - 1) / GS_FRONT_CHUNK : 1; }
+extern "C" size_t gs_front_ws_bytes(int N) { return (16 + 4 * (size_t)front_chunks(N) * sizeof(u64) + 15) & ~(size_t)15; }
 
 extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const float* scales, const float* opacities,
                             const float* normals, const float* kd, const float* ks, const float* viewmat, const float* K,
@@ -289,8 +365,8 @@ extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const
                        dim3(256), 0, s, (unsigned*)ws, ws_words, (unsigned long long*)counts4, tile_counts, tile_counts ? n_tiles : 0);
     GS_CHECK_LAUNCH();
     if (N == 0) return GS_OK;
-    const int n_chunks = (N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK;
-    hipLaunchKernelGGL(front_fwd_kernel, dim3(n_chunks), dim3(GS_PROJ_BLOCK), hist ? (size_t)n_tiles * sizeof(unsigned) : 0, s, N, means, quats, scales, opacities, normals, kd, ks,
+    const int n_chunks = front_chunks(N);
+    hipLaunchKernelGGL(front_fwd_kernel, dim3(n_chunks), dim3(GS_FRONT_BLOCK), hist ? (size_t)n_tiles * sizeof(unsigned) : 0, s, N, means, quats, scales, opacities, normals, kd, ks,
                        viewmat, K, cam_pos, min_roughness, max_metallic, mode, e, W, H, tile_size, tile_w, tile_h, eps2d, near_plane,
                        far_plane, radius_clip, key_bits == 24 ? key_base : 0u, key_bits == 24 ? (1u << 24) : 0u, (float4*)vis_records,
                        depth_keys, (uint2*)tile_rects, (unsigned*)ws, (u64*)((char*)ws + 16), n_chunks, (unsigned long long*)counts4,

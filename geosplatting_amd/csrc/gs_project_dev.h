@@ -151,7 +151,9 @@ __device__ __forceinline__ void tile_range_exact(float mx, float my, int radius,
 // read with relaxed agent-scope atomic loads (L1-bypassing, the "data is the flag" hand-off): no fence is
 // needed because nothing but the granule itself crosses workgroups.
 #define GS_PROJ_BLOCK 512         // chunk of the chained scan = workgroup (alone: 1024 is 10 % faster than 256; under the three-stream overlap of the engine the 1024-thread blocks wait for residency next to the LDS-heavy compositor blocks: 512 -> +3 % views/s); 256 -> 1024 quarters the same-address ticket
-                                   // atomics and descriptor traffic of the look-back: 0.185 -> 0.135 ms (stage incl. glue)
+                                   // atomics and descriptor traffic of the look-back: 0.185 -> 0.135 ms (stage incl. glue).
+                                   // This is the chunk of the rasterization() call shape (gs_project.hip) only: the engine's front
+                                   // kernel has its own shape (GS_FRONT_BLOCK x GS_FRONT_ITEMS Gaussians per chunk, gs_front.hip)
 #define GS_PROJ_WAVES (GS_PROJ_BLOCK / 64)
 #define GS_VALID_BIT  (1ull << 63)
 #define GS_SPIN_LIMIT (1 << 22)
