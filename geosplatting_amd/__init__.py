@@ -27,11 +27,13 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == TriangleMesh.from_depth_fusion (rfstudio/graphics/_mesh/_triangle_mesh.py:321-388) and the
                                              MeshExport task (tests/model/test_gsplat.py:169-202): depth maps -> dense TSDF -> marching
                                              cubes, without Open3D
-  meshrender.rasterize_mesh / interpolate / render_mesh / visible_faces, Stage1Model.render_mesh, GSplatModel.render_mesh
+  meshrender.rasterize_mesh / interpolate / mesh_edge_topology / antialias / render_mesh / visible_faces / silhouette_loss,
+  Stage1Model.render_mesh, GSplatModel.render_mesh
                                           == TriangleMesh.render(cameras, shader=NormalShader() / DepthShader()) and
                                              TriangleMesh.visible_faces (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555,
-                                             rfstudio/graphics/shaders.py:107-132): nvdiffrast's rasterize + interpolate restated
-                                             (no antialias, no near clipping): depth, normal, silhouette and face-index maps
+                                             rfstudio/graphics/shaders.py:107-132): nvdiffrast's rasterize + interpolate + antialias
+                                             restated (no near clipping): depth, normal, silhouette and face-index maps, with
+                                             silhouette gradients to the vertices through antialias
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -42,7 +44,8 @@ from .fusion import TSDFVolume, mesh_from_depth_fusion, save_obj  # noqa: F401
 from .gsplat3d import GaussianSet, GSplatModel, GSplatTrainer, mutate_adam  # noqa: F401
 from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401
-from .meshrender import interpolate, rasterize_mesh, render_mesh, visible_faces  # noqa: F401
+from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topology, rasterize_mesh, render_mesh,  # noqa: F401
+                         silhouette_loss, visible_faces)
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
 from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401

@@ -64,6 +64,7 @@ SYMBOLS = [
     "gs_tsdf_integrate", "gs_tsdf_extract_ws_bytes", "gs_tsdf_extract_count", "gs_tsdf_extract_fill",
     "gs_meshraster_ws_bytes", "gs_meshraster_fwd", "gs_meshraster_resolve", "gs_meshraster_bwd", "gs_mesh_interp_fwd",
     "gs_mesh_interp_bwd",
+    "gs_mesh_topology_bytes", "gs_mesh_topology_build", "gs_meshaa_fwd", "gs_meshaa_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -138,6 +139,12 @@ def lib() -> C.CDLL:
                                          C.c_void_p]
         l.gs_mesh_interp_bwd.argtypes = [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gs_mesh_topology_bytes.restype = C.c_size_t
+        l.gs_mesh_topology_bytes.argtypes = [C.c_int64]
+        l.gs_mesh_topology_build.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        aa_head = mesh_head + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        l.gs_meshaa_fwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gs_meshaa_bwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

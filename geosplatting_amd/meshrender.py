@@ -1,13 +1,16 @@
 """A differentiable triangle-mesh rasterizer for the meshes this package extracts (FlexiCubes, TSDF + marching cubes): depth, normal,
-silhouette and face-index maps from a camera.  What the reference gets from `TriangleMesh.render(cameras, shader=NormalShader() /
-DepthShader())` and `TriangleMesh.visible_faces` (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555, rfstudio/graphics/shaders.py:
-107-132) through nvdiffrast's `rasterize` and `interpolate`; both shaders set antialias=False, which is what this module matches.
-nvdiffrast is not restated line by line: the semantics below are this project's, the kernels are csrc/gs_meshraster.hip.
+silhouette and face-index maps from a camera.  What the reference gets from `TriangleMesh.render(cameras, shader=...)` and
+`TriangleMesh.visible_faces` (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555, rfstudio/graphics/shaders.py:107-132) through
+nvdiffrast's `rasterize`, `interpolate` and `antialias`.  nvdiffrast is not restated line by line: the semantics below are this
+project's, the kernels are csrc/gs_meshraster.hip and csrc/gs_meshaa.hip.
 
   rasterize_mesh(verts_cam, faces, camera_or_intrinsics, *, cull='none', near=1e-2) -> rast [H,W,4]
   interpolate(attr, rast, faces)                                                    -> [H,W,C]
-  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals) -> dict of maps
+  mesh_edge_topology(faces)                                                         -> EdgeTopology
+  antialias(color, rast, verts_cam, faces, camera_or_intrinsics, *, topology, cull, near) -> [H,W,C]
+  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, antialias) -> dict of maps
   visible_faces(vertices, faces, camera)                                            -> sorted unique face ids
+  silhouette_loss(alpha, target_mask)                                               -> scalar
 
 Semantics of `rasterize_mesh`
   Inputs    verts_cam [V,3] fp32 in camera space, OpenCV convention, +z forward (what Camera.view_matrix produces); faces [F,3]
@@ -34,9 +37,33 @@ Semantics of `rasterize_mesh`
   Output    rast [H,W,4] fp32 = (b0, b1, depth, face_id + 1), all zero where empty: nvdiffrast's layout with the view depth in
             place of z / w.  At most 2^24 faces.
   Backward  d rast[..., :3] -> d verts_cam with the face ids held fixed, through lambda, the perspective correction and the depth.
-            The face-id channel and coverage carry no gradient: silhouette gradients need nvdiffrast's antialias pass.
+            The face-id channel and coverage carry no gradient here: silhouette gradients come from `antialias`.
 
-Differences from nvdiffrast: no near clipping, no `antialias`, view depth in the third channel, y-down pixel rows.
+Semantics of `antialias` (the reference's `dr.antialias(rgba, rast, projected, indices)`, on by default in its mesh shaders)
+  Topology  mesh_edge_topology(faces): for every half-edge (f, i) -- edge i of face f runs between its vertices i + 1 and i + 2,
+            opposite vertex i -- the other faces on the same undirected edge, any number of them (extracted meshes need not be
+            manifold).  It depends on `faces` alone: build it once and pass it for every view and step.
+  Pairs     pixels p and q = p + (1, 0) or p + (0, 1), both in the image, whose face-id channels differ.
+  Foregr.   the pixel of the pair with a face and the smaller rast[..., 2]; an empty pixel loses, the lower face id wins equal
+            depths.  a = that pixel, b = the other, T = the face at a.
+  Exit edge with T's snapped integer edge functions and top-left biases, exactly as coverage uses them: edge i separates the pair
+            when E_i(a) + bias_i >= 0 and E_i(b) + bias_i < 0.  The exit edge is the separating edge with the smallest
+            E_i(a) / (E_i(a) - E_i(b)), compared exactly (128-bit cross products), ties to the lower i.  No separating edge (T covers
+            b too and is occluded there): the pair blends nothing.
+  Silhou.   the pair blends only if no other face on the exit edge has its opposite vertex strictly on the far side of the edge's
+            line from T's opposite vertex (sign of the snapped 64-bit cross product).  A face the rasterizer would drop or cull does
+            not count: `cull` and `near` must be the values `rast` was made with.  Boundary edges and creases whose faces fold onto
+            the same side are silhouettes.
+  Weight    q1, q2 = the UNSNAPPED fp32 positions of the exit edge's endpoints relative to a's pixel centre, s = +-1 from a to b.
+            Horizontal pair: x* = (q1x q2y - q1y q2x) / (q2y - q1y), where the edge's line meets the row (vertical: x and y
+            exchanged).  d = clamp(s x*, 0, 1).  d > 0.5: out[b] += (d - 0.5) (color[a] - color[b]); d < 0.5:
+            out[a] += (0.5 - d) (color[b] - color[a]).  out = color + the sum over a pixel's (at most four) pairs.
+  Backward  d color: the transpose of the blend.  d verts_cam: through d, with every discrete decision and the snap held fixed (the
+            unsnapped positions of the exit edge's two vertices, xs = fx X / Z + cx); zero where d is clamped.  No gradient to rast.
+
+Differences from nvdiffrast: no near clipping, view depth in the third channel, y-down pixel rows; in `antialias`, the pairs, the
+foreground, the exit edge and the silhouette test are decided on the snapped integer positions (and depth ties on the face id) while
+the weight comes from the unsnapped ones, and a silhouette is tested against every face on the edge, not against one neighbour.
 Every op raises GeoSplatHipError on CPU tensors; there is no CPU path.
 """
 from __future__ import annotations
@@ -159,6 +186,118 @@ def interpolate(attr: Tensor, rast: Tensor, faces: Tensor) -> Tensor:
     return _Interpolate.apply(attr, rast, f)
 
 
+class EdgeTopology:
+    """The half-edge neighbourhoods of a face array, on the device (module docstring; layout in csrc/gs_meshaa.hip).  Valid for as
+    long as `faces` is unchanged, for any vertex positions and any camera."""
+
+    def __init__(self, buffer: Tensor, n_faces: int):
+        self.buffer, self.n_faces = buffer, int(n_faces)
+
+    def neighbours(self):
+        """Host copy, for inspection: for every half-edge 3 f + i the sorted list of (other face, index of its opposite vertex)."""
+        F = self.n_faces
+        slots = 16
+        while slots < 6 * F:
+            slots *= 2
+        words = self.buffer.cpu()[8 * slots:8 * slots + 4 * (slots + 6 * F)].view(torch.int32).tolist()
+        head, slot, nxt = words[:slots], words[slots:slots + 3 * F], words[slots + 3 * F:]
+        out = []
+        for h in range(3 * F):
+            group, k = [], head[slot[h]] if slot[h] >= 0 else -1
+            while k >= 0 and len(group) <= 3 * F:
+                if k // 3 != h // 3:
+                    group.append((k // 3, k % 3))
+                k = nxt[k]
+            out.append(sorted(group))
+        return out
+
+
+def mesh_edge_topology(faces: Tensor) -> EdgeTopology:
+    """faces [F,3] -> the EdgeTopology `antialias` needs; built on the device, reusable while `faces` is unchanged."""
+    _lib.require_cuda(faces)
+    f = _faces32(faces)
+    lib = _lib.lib()
+    F = f.shape[0]
+    n = lib.gs_mesh_topology_bytes(F)
+    if n == 0:
+        raise _lib.GeoSplatHipError("at most 2^24 faces")
+    buf = torch.empty(n, dtype=torch.uint8, device=f.device)
+    _lib.check(lib.gs_mesh_topology_build(F, _lib.ptr(f), _lib.ptr(buf), n, _lib.stream()), "gs_mesh_topology_build")
+    return EdgeTopology(buf, F)
+
+
+def _aa_head(v: Tensor, f: Tensor, intr, near: float, cull: str, topo: EdgeTopology, C: int, rast: Tensor, color: Tensor):
+    return (*_mesh_head(v, f, intr, near), _CULL[cull], _lib.ptr(topo.buffer), topo.buffer.numel(), C, _lib.ptr(rast), _lib.ptr(color))
+
+
+def antialias_raw(color: Tensor, rast: Tensor, verts_cam: Tensor, faces32: Tensor, intr, topo: EdgeTopology, *, cull: str = "none",
+                  near: float = 1e-2, debug: bool = False):
+    """gs_meshaa_fwd without autograd on contiguous fp32 tensors -> out, or (out, decisions int32 [H,W,2]) with `debug`: per pixel p
+    the pairs (p, p + (1,0)) and (p, p + (0,1)); 0 = nothing blended, else 1 + exit edge + 4 (0 zero weight, 1 p receives, 2 the
+    other pixel receives) + 16 (the foreground is the other pixel)."""
+    H, W = intr[4], intr[5]
+    C = color.shape[-1]
+    out = torch.empty_like(color)
+    dbg = torch.empty(H, W, 2, dtype=torch.int32, device=color.device) if debug else None
+    _lib.check(_lib.lib().gs_meshaa_fwd(*_aa_head(verts_cam, faces32, intr, near, cull, topo, C, rast, color), _lib.ptr(out),
+                                        _lib.ptr(dbg), _lib.stream()), "gs_meshaa_fwd")
+    return (out, dbg) if debug else out
+
+
+class _Antialias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color: Tensor, verts_cam: Tensor, rast: Tensor, faces32: Tensor, topo: EdgeTopology, intr, cull: str, near: float):
+        c = color.detach().contiguous().float()
+        v = verts_cam.detach().contiguous().float()
+        r = rast.detach().contiguous().float()
+        out = antialias_raw(c, r, v, faces32, intr, topo, cull=cull, near=near)
+        ctx.save_for_backward(c, v, r, faces32)
+        ctx.topo, ctx.intr, ctx.cull, ctx.near = topo, intr, cull, near
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        c, v, r, f = ctx.saved_tensors
+        g = d_out.contiguous().float()
+        d_color = torch.empty_like(c)
+        d_vc = torch.empty_like(v) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().gs_meshaa_bwd(*_aa_head(v, f, ctx.intr, ctx.near, ctx.cull, ctx.topo, c.shape[-1], r, c), _lib.ptr(g),
+                                            _lib.ptr(d_color), _lib.ptr(d_vc), _lib.stream()), "gs_meshaa_bwd")
+        return d_color, d_vc, None, None, None, None, None, None
+
+
+def antialias(color: Tensor, rast: Tensor, verts_cam: Tensor, faces: Tensor, camera_or_intrinsics: Intrinsics, *,
+              topology: Optional[EdgeTopology] = None, cull: str = "none", near: float = 1e-2) -> Tensor:
+    """color [H,W,C] -> [H,W,C] with the silhouette pixels blended across the outline (module docstring); differentiable in `color` and
+    in `verts_cam`, not in `rast`.  `cull` and `near` must be the values `rast` was made with; `topology` (mesh_edge_topology(faces))
+    is built here when none is passed."""
+    _lib.require_cuda(color, rast, verts_cam, faces)
+    if cull not in _CULL:
+        raise ValueError("cull must be 'none' or 'back'")
+    intr = _intrinsics(camera_or_intrinsics)
+    f = _faces32(faces)
+    if verts_cam.ndim != 2 or verts_cam.shape[1] != 3:
+        raise _lib.GeoSplatHipError("verts_cam must be [V,3]")
+    if rast.shape != (intr[4], intr[5], 4):
+        raise _lib.GeoSplatHipError("rast must be [H,W,4]")
+    if color.ndim != 3 or color.shape[:2] != rast.shape[:2] or color.shape[2] < 1:
+        raise _lib.GeoSplatHipError("color must be [H,W,C] with C >= 1")
+    if topology is None:
+        topology = mesh_edge_topology(f)
+    elif topology.n_faces != f.shape[0] or topology.buffer.device != color.device:
+        raise _lib.GeoSplatHipError("topology was built for another face array or device")
+    return _Antialias.apply(color, verts_cam, rast, f, topology, intr, cull, float(near))
+
+
+_antialias = antialias
+
+
+def silhouette_loss(alpha: Tensor, target_mask: Tensor) -> Tensor:
+    """Mean squared error between an antialiased `alpha` map and a target mask of the same number of elements: the mask term a mesh
+    gets once its outline has a gradient (render_mesh(..., antialias=True))."""
+    return ((alpha - target_mask.to(alpha.dtype).reshape(alpha.shape)) ** 2).mean()
+
+
 def _unit_or_z(v: Tensor) -> Tensor:
     """rfstudio.graphics.math.safe_normalize: unit vectors, (0, 0, 1) where the length is below 1e-6"""
     n = v.norm(dim=-1, keepdim=True)
@@ -177,14 +316,17 @@ def to_camera_space(vertices: Tensor, camera: Camera) -> Tensor:
 
 def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Sequence[str] = ("depth", "normal", "alpha", "face"),
                 normal_type: str = "vertex", cull: str = "back", vertex_normals: Optional[Tensor] = None,
-                near: float = 1e-2) -> Dict[str, Tensor]:
+                near: float = 1e-2, antialias: bool = False, topology: Optional[EdgeTopology] = None) -> Dict[str, Tensor]:
     """World-space mesh seen from `camera` -> {'rast' [H,W,4] and the requested maps}:
       depth  [H,W,1]  interpolated view depth (DepthShader), 0 where empty
       normal [H,W,3]  world-space normals (NormalShader): 'vertex' safe_normalize of the interpolated `vertex_normals` (default: the
                       area-weighted gs.vertex_normals), 'flat' the unit face normal of the winning face
       alpha  [H,W,1]  rast[..., 3:] > 0 as float
       face   [H,W,1]  int64 face index, -1 where empty (ShadingContext.face_indices)
-    depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not."""
+    depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not, unless `antialias` is set: then the
+    requested maps among depth, normal and alpha go through `antialias` together as one [H,W,5] image (the way the reference
+    antialiases its rgba), normal is normalised again, and alpha lies strictly between 0 and 1 along the outline with a gradient to
+    the vertices of the outline's faces.  face and rast are never changed.  `topology`: mesh_edge_topology(faces), to reuse it."""
     _lib.require_cuda(vertices, faces)
     unknown = set(outputs) - {"depth", "normal", "alpha", "face"}
     if unknown:
@@ -212,6 +354,12 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
         out["alpha"] = (rast[..., 3:] > 0).float()
     if "face" in outputs:
         out["face"] = rast[..., 3:].long() - 1
+    names = [k for k in ("depth", "normal", "alpha") if k in out]
+    if antialias and names:
+        widths = [out[k].shape[-1] for k in names]
+        blended = _antialias(torch.cat([out[k] for k in names], -1), rast, vc, f32, camera, topology=topology, cull=cull, near=near)
+        for k, part in zip(names, blended.split(widths, -1)):
+            out[k] = _unit_or_z(part) if k == "normal" else part
     return out
 
 

@@ -231,7 +231,8 @@ class Stage1Model:
 
     def render_mesh(self, cameras, **kw):
         """The extracted FlexiCubes mesh seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per camera -> a dict of
-        maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them.  Differentiable in the geometry parameters."""
+        maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them.  Differentiable in the geometry parameters; with
+        antialias=True the outline is too (meshrender.antialias), so that silhouette_loss on 'alpha' can move it."""
         from .meshrender import render_mesh
         (v, f), _ = self.get_geometry()
         if isinstance(cameras, Camera):

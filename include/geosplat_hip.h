@@ -862,6 +862,42 @@ int gs_mesh_interp_fwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vert
 int gs_mesh_interp_bwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vertex, const float* rast, const int32_t* faces,
                        const float* attr, const float* d_out, float* d_attr, float* d_rast, void* stream);
 
+/* ------------------------------------------------------------------ mesh silhouette antialiasing --------- */
+/* What TriangleMesh.render gets from `dr.antialias(rgba, rast, projected, indices)` (_triangle_mesh.py:552-553); a restatement of the
+ * semantics, not of nvdiffrast.  csrc/gs_meshaa.hip; faces are loaded, snapped and culled by the rasterizer's own device code.
+ *
+ * Topology: for every half-edge (f, i) -- edge i of face f runs between its vertices i + 1 and i + 2, opposite vertex i -- the other
+ *   half-edges on the same undirected edge, any number of them.  The indices are labels (nothing is read through them); a half-edge
+ *   whose two indices are equal has no neighbours.  Depends on `faces` only: build once, reuse across views and steps.
+ * Pairs: pixels p and q = p + (1, 0) or p + (0, 1) whose rast[..., 3] differ.  Foreground a: the one with a face and the smaller
+ *   rast[..., 2]; an empty pixel loses, the lower face id wins equal depths.  T = the face at a, b = the other pixel.
+ * Exit edge: with T's snapped integer edge functions and top-left biases, edge i separates when E_i(a) + bias_i >= 0 and
+ *   E_i(b) + bias_i < 0; the exit edge has the smallest E_i(a) / (E_i(a) - E_i(b)) (128-bit cross products), ties to the lower i.
+ *   None: the pair blends nothing.
+ * Silhouette: the pair blends only if no other face on the exit edge, among those the rasterizer keeps (near, range, area, cull),
+ *   has its opposite vertex strictly on the other side of the edge's line from T's (sign of the snapped 64-bit cross product).
+ * Weight: q1, q2 = unsnapped fp32 positions of the edge's endpoints relative to a's centre, s = +-1 from a to b;
+ *   horizontal pair x* = (q1x q2y - q1y q2x) / (q2y - q1y) (vertical: x and y exchanged);  d = clamp(s x*, 0, 1);
+ *   d > 0.5: out[b] += (d - 0.5) (color[a] - color[b]);   d < 0.5: out[a] += (0.5 - d) (color[b] - color[a]).
+ *   out = color + the sum over a pixel's (at most four) pairs.  `cull` and `near` must be the rasterizer's.
+ *
+ *   gs_mesh_topology_bytes  size of the topology object for F faces: at most 60 bytes per half-edge (0: F out of range)
+ *   gs_mesh_topology_build  faces [F,3] -> topo.  No workgroup waits on another.
+ *   gs_meshaa_fwd           color [H,W,C] -> out [H,W,C]; a gather without atomics: two runs are bit-identical.  dbg (optional,
+ *                           int32 [H,W,2]): the decisions of the pairs (p, p + (1,0)) and (p, p + (0,1)): 0 nothing blended, else
+ *                           1 + exit edge + 4 (0: zero weight, 1: p receives, 2: the other pixel receives) + 16 (foreground is the other)
+ *   gs_meshaa_bwd           d_out -> d_color [H,W,C] and d_vc [V,3] (both overwritten; d_vc may be null): d color is the transpose of
+ *                           the blend, d vc goes through d with the decisions and the snap fixed, zero where d is clamped; six fp32
+ *                           atomic adds per blended pair.  No gradient to rast. */
+size_t gs_mesh_topology_bytes(int64_t F);
+int gs_mesh_topology_build(int64_t F, const int32_t* faces, void* topo, size_t topo_bytes, void* stream);
+int gs_meshaa_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                  float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color, float* out,
+                  int32_t* dbg, void* stream);
+int gs_meshaa_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                  float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
+                  const float* d_out, float* d_color, float* d_vc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

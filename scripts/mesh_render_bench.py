@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time the mesh rasterizer (csrc/gs_meshraster.hip through geosplatting_amd.meshrender) at 800 x 800 on the meshes this project
-extracts, and count its atomics.
+"""Time the mesh rasterizer and its antialias pass (csrc/gs_meshraster.hip, csrc/gs_meshaa.hip through geosplatting_amd.meshrender) at
+800 x 800 on the meshes this project extracts, and count the rasterizer's atomics.
 
     python scripts/mesh_render_bench.py [--meshes flexicubes96,tsdf512,ico3,ico5,ico7,plane] [--size 800] [--runs 20] [--warmup 3]
                                         [--lib PATH/libgeosplat_hip.so] [--out FILE.json]
@@ -17,6 +17,9 @@ Per mesh, device events around `runs` calls after `warmup`, the median per call:
   fwd_ms      gs_meshraster_fwd: key fill, thread-per-triangle pass, wave-per-triangle pass
   resolve_ms  gs_meshraster_resolve
   bwd_ms      gs_meshraster_bwd with a random d rast (includes zeroing d vc)
+  topology_ms gs_mesh_topology_build: table fill and insertion of the 3 F half-edges (once per face array, not per view)
+  aa_fwd_ms   gs_meshaa_fwd on a 5-channel image (what render_mesh(antialias=True) passes: depth, normal, alpha)
+  aa_bwd_ms   gs_meshaa_bwd with a random d out (includes zeroing d vc); aa_pairs counts the blended pairs of the view
   render_fwd_ms / render_bwd_ms   render_mesh(depth, normal, alpha, face) and the backward of sum(depth) + sum(normal): what a user
               calls, with the torch plumbing (view transform, vertex normals, normalisation) included
 Counts come from ONE extra forward with the statistics buffer, outside the timed calls: fragments (covered pixel, triangle) and 64-bit
@@ -130,6 +133,28 @@ def main():
             _lib.check(lib.gs_meshraster_bwd(*head, _lib.ptr(rast), _lib.ptr(d_rast), _lib.ptr(d_vc), _lib.stream()), "gs_meshraster_bwd")
 
         t_fwd, t_res, t_bwd = timed(fwd, a.runs, a.warmup), timed(resolve, a.runs, a.warmup), timed(bwd, a.runs, a.warmup)
+        topo_bytes = lib.gs_mesh_topology_bytes(f32.shape[0])
+        topo = torch.empty(topo_bytes, dtype=torch.uint8, device=dev)
+        C = 5
+        color, d_out = torch.rand(H, W, C, device=dev), torch.randn(H, W, C, device=dev)
+        aa_out, d_color = torch.empty_like(color), torch.empty_like(color)
+        dbg = torch.empty(H, W, 2, dtype=torch.int32, device=dev)
+        aa_head = (*head, 1, _lib.ptr(topo), topo_bytes, C, _lib.ptr(rast), _lib.ptr(color))
+
+        def topology():
+            _lib.check(lib.gs_mesh_topology_build(f32.shape[0], _lib.ptr(f32), _lib.ptr(topo), topo_bytes, _lib.stream()),
+                       "gs_mesh_topology_build")
+
+        def aa_fwd(debug=None):
+            _lib.check(lib.gs_meshaa_fwd(*aa_head, _lib.ptr(aa_out), _lib.ptr(debug), _lib.stream()), "gs_meshaa_fwd")
+
+        def aa_bwd():
+            _lib.check(lib.gs_meshaa_bwd(*aa_head, _lib.ptr(d_out), _lib.ptr(d_color), _lib.ptr(d_vc), _lib.stream()), "gs_meshaa_bwd")
+
+        t_topo = timed(topology, a.runs, a.warmup)
+        aa_fwd(dbg)
+        aa_pairs = int((dbg > 0).sum())
+        t_aaf, t_aab = timed(aa_fwd, a.runs, a.warmup), timed(aa_bwd, a.runs, a.warmup)
         vg = v.detach().clone().requires_grad_()
         kept = {}
 
@@ -152,10 +177,13 @@ def main():
             "fwd_ms": t_fwd[0], "fwd_ms_min_max": t_fwd[1:], "resolve_ms": t_res[0], "resolve_ms_min_max": t_res[1:],
             "bwd_ms": t_bwd[0], "bwd_ms_min_max": t_bwd[1:], "bwd_float_atomics": 9 * covered,
             "atomics_per_us": atomics / (t_fwd[0] * 1e3),
+            "topology_ms": t_topo[0], "topology_ms_min_max": t_topo[1:], "topology_bytes": int(topo_bytes),
+            "aa_fwd_ms": t_aaf[0], "aa_fwd_ms_min_max": t_aaf[1:], "aa_bwd_ms": t_aab[0], "aa_bwd_ms_min_max": t_aab[1:],
+            "aa_pairs": aa_pairs, "aa_bwd_float_atomics": 6 * aa_pairs,
             "render_fwd_ms": t_rf[0], "render_fwd_plus_bwd_ms": t_rfb[0], "render_bwd_ms": t_rfb[0] - t_rf[0],
         }
         print(name, json.dumps(results["meshes"][name]), flush=True)
-        del v, f, f32, vc, ws, rast, d_rast, d_vc, vg, kept
+        del v, f, f32, vc, ws, rast, d_rast, d_vc, vg, kept, topo, color, d_out, aa_out, d_color, dbg
         torch.cuda.empty_cache()
     print(json.dumps(results))
     if a.out:
