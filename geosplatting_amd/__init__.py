@@ -34,6 +34,11 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              rfstudio/graphics/shaders.py:107-132): nvdiffrast's rasterize + interpolate + antialias
                                              restated (no near clipping): depth, normal, silhouette and face-index maps, with
                                              silhouette gradients to the vertices through antialias
+  meshshade.texture2d / Texture2D / shade_pixels, render_mesh(outputs=(..., 'color'), kd=, ks=, uvs=, envmap=)
+                                          == TriangleMesh.render(cameras, shader=PBRShader(envmap=...)) and
+                                             PrettyShader(occlusion_type='none') (rfstudio/graphics/shaders.py:44-105, 199-233):
+                                             dr.texture's 2-D lookup ('wrap' / 'clamp') and the per-pixel split-sum PBR shader, with
+                                             gradients to the textures, the environment, the normals and the positions
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -46,6 +51,7 @@ from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401
 from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topology, rasterize_mesh, render_mesh,  # noqa: F401
                          silhouette_loss, visible_faces)
+from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
 from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401

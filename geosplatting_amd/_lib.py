@@ -65,6 +65,7 @@ SYMBOLS = [
     "gs_meshraster_ws_bytes", "gs_meshraster_fwd", "gs_meshraster_resolve", "gs_meshraster_bwd", "gs_mesh_interp_fwd",
     "gs_mesh_interp_bwd",
     "gs_mesh_topology_bytes", "gs_mesh_topology_build", "gs_meshaa_fwd", "gs_meshaa_bwd",
+    "gs_tex2d_fwd", "gs_tex2d_bwd", "gs_meshshade_fwd", "gs_meshshade_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -145,6 +146,13 @@ def lib() -> C.CDLL:
         aa_head = mesh_head + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         l.gs_meshaa_fwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p]
         l.gs_meshaa_bwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        tex_head = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.gs_tex2d_fwd.argtypes = tex_head + [C.c_void_p, C.c_void_p]
+        l.gs_tex2d_bwd.argtypes = tex_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        shade_head = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
+        l.gs_meshshade_fwd.argtypes = shade_head + [C.c_void_p, C.c_void_p]
+        l.gs_meshshade_bwd.argtypes = shade_head + [C.c_void_p] * 8
         _lib = l
     return _lib
 

@@ -265,11 +265,13 @@ static __global__ void __launch_bounds__(MR_BLOCK) aa_fwd_kernel(AaCtx K, int C,
         for (int c = 0; c < C; ++c) o[c] = cp[c];
         return;
     }
+    // explicit FMAs: left to contraction, the vectorised pairs of channels were fused and the odd last channel was not, so a channel's
+    // bits depended on C and on its position in the image
     for (int c = 0; c < C; ++c) {
         const float mine = cp[c];
         float acc = mine;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc += wk[k] * (color[(size_t)ok[k] * C + c] - mine);
+        for (int k = 0; k < 4; ++k) acc = __builtin_fmaf(wk[k], color[(size_t)ok[k] * C + c] - mine, acc);
         o[c] = acc;
     }
 }
@@ -321,7 +323,7 @@ static __global__ void __launch_bounds__(MR_BLOCK) aa_bwd_kernel(AaCtx K, int C,
     for (int c = 0; c < C; ++c) {
         float acc = g[c];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc += wk[k] * d_out[(size_t)tk[k] * C + c];
+        for (int k = 0; k < 4; ++k) acc = __builtin_fmaf(wk[k], d_out[(size_t)tk[k] * C + c], acc);
         o[c] = acc;
     }
 }

@@ -78,6 +78,24 @@ __device__ __forceinline__ float mip_from_roughness(float r, float min_r, float 
     return m;
 }
 
+// The two pyramid levels of a trilinear lookup at level `bias`, in cube_mip_fetch's and shade_pair_pre's own expressions: l1 < 0 = level
+// l0 alone (the last one, f = 0); `clamped`: the level carries no gradient (outside [0, L - 1], or the last level).  For a backward that
+// recomputes a forward which went through cube_mip_fetch (gs_meshshade.hip).  (cube_mip_fetch and shade_pair_pre keep their inline
+// copies: routing them through this helper changed the register allocation of the engine's front and tail kernels.)
+struct MipSelect { int l0, l1; float f; bool clamped; };
+__device__ __forceinline__ MipSelect mip_select(int L, float bias)
+{
+    const float lam = fminf(fmaxf(bias, 0.0f), (float)(L - 1));
+    const int lf = (int)floorf(lam);
+    const bool last = lf >= L - 1;
+    MipSelect m;
+    m.l0 = last ? L - 1 : lf;
+    m.l1 = last ? -1 : lf + 1;
+    m.f = last ? 0.0f : lam - (float)m.l0;
+    m.clamped = last || (bias < 0.0f || bias > (float)(L - 1));
+    return m;
+}
+
 struct MipSample {
     float out[3], dd[9], dmip[3];
     CubeFp fp0, fp1;

@@ -466,7 +466,8 @@ class GSplatModel:
     def render_mesh(self, cameras, vertices: Tensor, faces: Tensor, **kw):
         """A mesh of this model (what extract_mesh returned) seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per
         camera -> a dict of maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them; its depth compares with
-        render_depth's.  antialias=True (and topology=mesh_edge_topology(faces), to build it once) blends the outline, meshrender.antialias."""
+        render_depth's.  antialias=True (and topology=mesh_edge_topology(faces), to build it once) blends the outline, meshrender.antialias.
+        outputs=(..., 'color') with kd=, ks=, uvs=, envmap=, occlusion=, min_visibility=, bend_back_normal= shades it (meshshade.py)."""
         from .meshrender import render_mesh
         if isinstance(cameras, Camera):
             return render_mesh(vertices, faces, cameras, **kw)

@@ -8,7 +8,8 @@ project's, the kernels are csrc/gs_meshraster.hip and csrc/gs_meshaa.hip.
   interpolate(attr, rast, faces)                                                    -> [H,W,C]
   mesh_edge_topology(faces)                                                         -> EdgeTopology
   antialias(color, rast, verts_cam, faces, camera_or_intrinsics, *, topology, cull, near) -> [H,W,C]
-  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, antialias) -> dict of maps
+  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, antialias,
+              kd, ks, uvs, envmap, occlusion, min_visibility, bend_back_normal)     -> dict of maps ('color': meshshade.py)
   visible_faces(vertices, faces, camera)                                            -> sorted unique face ids
   silhouette_loss(alpha, target_mask)                                               -> scalar
 
@@ -316,45 +317,71 @@ def to_camera_space(vertices: Tensor, camera: Camera) -> Tensor:
 
 def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Sequence[str] = ("depth", "normal", "alpha", "face"),
                 normal_type: str = "vertex", cull: str = "back", vertex_normals: Optional[Tensor] = None,
-                near: float = 1e-2, antialias: bool = False, topology: Optional[EdgeTopology] = None) -> Dict[str, Tensor]:
+                near: float = 1e-2, antialias: bool = False, topology: Optional[EdgeTopology] = None,
+                kd=None, ks=None, uvs: Optional[Tensor] = None, envmap=None, occlusion: str = "texture",
+                min_visibility: float = 0.0, bend_back_normal: bool = False) -> Dict[str, Tensor]:
     """World-space mesh seen from `camera` -> {'rast' [H,W,4] and the requested maps}:
       depth  [H,W,1]  interpolated view depth (DepthShader), 0 where empty
       normal [H,W,3]  world-space normals (NormalShader): 'vertex' safe_normalize of the interpolated `vertex_normals` (default: the
                       area-weighted gs.vertex_normals), 'flat' the unit face normal of the winning face
       alpha  [H,W,1]  rast[..., 3:] > 0 as float
       face   [H,W,1]  int64 face index, -1 where empty (ShadingContext.face_indices)
+      color  [H,W,3]  PBRShader: meshshade.shade_pixels on the interpolated world positions, the normal map of `normal_type` and the
+                      interpolated `uvs` [F,3,2] (per face-vertex), with the Texture2D `kd`, `ks` under the TextureSplitSum `envmap`;
+                      `occlusion`, `min_visibility`, `bend_back_normal` as there.  `uvs=None` is allowed only with 1x1 textures and means
+                      zeros (PrettyShader).  0 where empty.  Differentiable in the textures, the environment and `vertices`.
     depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not, unless `antialias` is set: then the
-    requested maps among depth, normal and alpha go through `antialias` together as one [H,W,5] image (the way the reference
+    requested maps among depth, normal, color and alpha go through `antialias` together as one image (the way the reference
     antialiases its rgba), normal is normalised again, and alpha lies strictly between 0 and 1 along the outline with a gradient to
     the vertices of the outline's faces.  face and rast are never changed.  `topology`: mesh_edge_topology(faces), to reuse it."""
     _lib.require_cuda(vertices, faces)
-    unknown = set(outputs) - {"depth", "normal", "alpha", "face"}
+    unknown = set(outputs) - {"depth", "normal", "alpha", "face", "color"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
     if normal_type not in ("vertex", "flat"):
         raise ValueError("normal_type must be 'vertex' or 'flat'")
+    want_color = "color" in outputs
+    if want_color:
+        from .meshshade import _OCCLUSION, _as_texture
+        if kd is None or ks is None or envmap is None:
+            raise ValueError("outputs 'color' needs kd, ks and envmap")
+        if occlusion not in _OCCLUSION:
+            raise ValueError("occlusion must be 'texture' or 'none' ('ao' and 'ssao' are not provided)")
+        kd, ks = _as_texture(kd, "kd"), _as_texture(ks, "ks")
+        if uvs is None and not (kd.data.shape[:2] == (1, 1) and ks.data.shape[:2] == (1, 1)):
+            raise ValueError("uvs=None is allowed only with 1x1 textures")
     f32 = _faces32(faces)
+    if want_color and uvs is not None and tuple(uvs.shape) != (f32.shape[0], 3, 2):
+        raise _lib.GeoSplatHipError("uvs must be [F,3,2]")
     vc = to_camera_space(vertices, camera)
     rast = rasterize_mesh(vc, f32, camera, cull=cull, near=near)
     out: Dict[str, Tensor] = {"rast": rast}
     if "depth" in outputs:
         out["depth"] = interpolate(vc[:, 2:3].contiguous(), rast, f32)
-    if "normal" in outputs:
+    if "normal" in outputs or want_color:
         if normal_type == "vertex":
             if vertex_normals is None:
                 from .mesh import vertex_normals as compute_vertex_normals
                 vertex_normals = compute_vertex_normals(vertices.float(), faces.to(torch.int64))
-            out["normal"] = _unit_or_z(interpolate(vertex_normals, rast, f32))
+            normal_map = _unit_or_z(interpolate(vertex_normals, rast, f32))
         else:
             fl = faces.to(torch.int64)
             v = vertices.float()
             fn = _unit_or_z(torch.cross(v[fl[:, 1]] - v[fl[:, 0]], v[fl[:, 2]] - v[fl[:, 0]], dim=-1))
-            out["normal"] = fn[(rast[..., 3].long() - 1).clamp_min(0)]          # (face_attribute_map: face 0 where empty)
+            normal_map = fn[(rast[..., 3].long() - 1).clamp_min(0)]            # (face_attribute_map: face 0 where empty)
+        if "normal" in outputs:
+            out["normal"] = normal_map
+    if want_color:
+        from .meshshade import shade_pixels
+        position = interpolate(vertices.float().contiguous(), rast, f32)
+        uv = interpolate(uvs.float(), rast, f32) if uvs is not None else torch.zeros(*rast.shape[:2], 2, device=rast.device)
+        out["color"] = shade_pixels(position, normal_map, uv, rast, kd, ks, camera.c2w[:, 3].to(rast.device), envmap,
+                                    occlusion=occlusion, min_visibility=min_visibility, bend_back_normal=bend_back_normal)
     if "alpha" in outputs:
         out["alpha"] = (rast[..., 3:] > 0).float()
     if "face" in outputs:
         out["face"] = rast[..., 3:].long() - 1
-    names = [k for k in ("depth", "normal", "alpha") if k in out]
+    names = [k for k in ("depth", "normal", "color", "alpha") if k in out]
     if antialias and names:
         widths = [out[k].shape[-1] for k in names]
         blended = _antialias(torch.cat([out[k] for k in names], -1), rast, vc, f32, camera, topology=topology, cull=cull, near=near)

@@ -232,7 +232,9 @@ class Stage1Model:
     def render_mesh(self, cameras, **kw):
         """The extracted FlexiCubes mesh seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per camera -> a dict of
         maps ('depth', 'normal', 'alpha', 'face', 'rast'), or a list of them.  Differentiable in the geometry parameters; with
-        antialias=True the outline is too (meshrender.antialias), so that silhouette_loss on 'alpha' can move it."""
+        antialias=True the outline is too (meshrender.antialias), so that silhouette_loss on 'alpha' can move it.  outputs=(..., 'color')
+        with kd=, ks=, uvs=, envmap=, occlusion=, min_visibility=, bend_back_normal= shades the mesh (meshshade.shade_pixels), with
+        gradients to the textures, the environment and the geometry."""
         from .meshrender import render_mesh
         (v, f), _ = self.get_geometry()
         if isinstance(cameras, Camera):

@@ -898,6 +898,59 @@ int gs_meshaa_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, f
                   float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
                   const float* d_out, float* d_color, float* d_vc, void* stream);
 
+/* ------------------------------------------------------------------ mesh shading: 2-D textures, split-sum PBR per pixel ------ */
+/* What TriangleMesh.render(cameras, shader=PBRShader(envmap=...)) and PrettyShader(occlusion_type='none') compute per pixel
+ * (rfstudio/graphics/shaders.py:44-105, 199-233), on a G-buffer.  csrc/gs_meshshade.hip.
+ *
+ * 2-D lookup  tex [Ht,Wt,C] fp32, C in 1..4, uv [P,2]; dr.texture(tex[None], uv, filter_mode='linear'), no mip chain.
+ *   wrap:  u' = u - floor(u), x = u' Wt - 0.5, ix0 = floor(x) (may be -1), fx = x - ix0, taps at ix0 mod Wt and (ix0 + 1) mod Wt;
+ *          y likewise with Ht.
+ *   clamp: x = clamp(u Wt - 0.5, 0, Wt - 1), taps ix0 and min(ix0 + 1, Wt - 1) (the FG-LUT lookup, for C channels); the gradient
+ *          is 0 in a clamped coordinate.
+ *   value: top + fy (bot - top), top = t00 + fx (t10 - t00), bot = t01 + fx (t11 - t01), contraction off.
+ *   The uv gradient is the derivative of the selected cell's bilinear patch.  A non-finite uv row gives zeros and no gradient.
+ *   Tap indices are reduced into range in integer arithmetic, after the conversion of a value clamped to a finite range.
+ * Texture2D.sample(uv) = the wrap lookup at (u (1 - 1/Wt) + 0.5/Wt, v (1 - 1/Ht) + 0.5/Ht) (_texture.py:168-175).
+ *
+ * Shading  rast [H,W,4] (only rast[..., 3] > 0 is read), position [H,W,3] world space, normal [H,W,3] unit, uv [H,W,2],
+ *   kd [kd_h,kd_w,3], ks [ks_h,ks_w,3] = (occlusion, roughness, metallic), cam_pos[3] on the device.  Per covered pixel:
+ *     kd, ks = Texture2D.sample(uv);  rough = ks[1], metal = ks[2];  spec = (1 - metal) 0.04 + kd metal;  diff = kd (1 - metal)
+ *     wo = safe_normalize(cam_pos - position) ((0,0,1) below 1e-6);  d = n.wo
+ *     bend_back_normal: n <- (d > 0 ? n : -n), d <- n.wo, ndv = d;   otherwise ndv = max(d, 1e-4)
+ *     fg = LUT(ndv, rough) with clamp;  refl = 2 d n - wo
+ *     l_diff = cube(base, n);  l_spec = cube_mip(levels, refl, mip_from_roughness(rough))      (TextureSplitSum.sample)
+ *     visibility = max(1 - ks[0], min_visibility) (GS_OCC_TEXTURE) or 1 (GS_OCC_NONE)
+ *     colour = (l_diff diff + l_spec (spec fg[0] + fg[1])) visibility
+ *   A pixel with rast[..., 3] <= 0, or with a non-finite position, normal or uv, gets colour 0 and no gradient anywhere (the
+ *   reference shades empty pixels from face 0 and hides them behind alpha 0).
+ *   Gradients: every selection (texel, LUT cell, cube face, mip level, the ndv and visibility clamps, the bend) takes the
+ *   derivative of the selected piece; 0 where a clamp is active.
+ *
+ *   gs_tex2d_fwd      out [P,C]; one thread per sample.
+ *   gs_tex2d_bwd      d_uv [P,2] overwritten; d_tex [Ht,Wt,C] ACCUMULATED into (caller zeroes).
+ *   gs_meshshade_fwd  color [H,W,3]; one thread per pixel, a gather without atomics: two runs are bit-identical.
+ *   gs_meshshade_bwd  d_position, d_normal [H,W,3], d_uv [H,W,2] overwritten without atomics (bit-identical between runs, zero at
+ *                     empty pixels); d_kd, d_ks and env_grad (base and every level) ACCUMULATED into (caller zeroes).  Arrays
+ *                     that fit the block's LDS budget are summed there and flushed once per block: a 1x1 texture receives at
+ *                     most one global atomic per channel and block.
+ * All four return GS_EINVAL before touching the device for C outside 1..4, a texture dimension, H or W below 1, an unknown boundary
+ * or occlusion mode, or a null required pointer.  P == 0 is a no-op. */
+#define GS_TEX_WRAP      0
+#define GS_TEX_CLAMP     1
+#define GS_OCC_TEXTURE   0
+#define GS_OCC_NONE      1
+int gs_tex2d_fwd(int64_t P, int Ht, int Wt, int C, int boundary, const float* tex, const float* uv, float* out, void* stream);
+int gs_tex2d_bwd(int64_t P, int Ht, int Wt, int C, int boundary, const float* tex, const float* uv, const float* d_out,
+                 float* d_uv, float* d_tex, void* stream);
+int gs_meshshade_fwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                     int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                     const GsEnv* env /*host*/, int occlusion, float min_visibility, int bend_back_normal, float* color, void* stream);
+int gs_meshshade_bwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                     int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                     const GsEnv* env /*host*/, int occlusion, float min_visibility, int bend_back_normal, const float* d_color,
+                     float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks, const GsEnvGrad* env_grad /*host*/,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
