@@ -53,6 +53,7 @@ from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topolog
                          silhouette_loss, visible_faces)
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
+from .raytrace import MeshBVH, shadow_visibility  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
 from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401
 from . import viewbatch  # noqa: F401

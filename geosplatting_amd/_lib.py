@@ -66,6 +66,7 @@ SYMBOLS = [
     "gs_mesh_interp_bwd",
     "gs_mesh_topology_bytes", "gs_mesh_topology_build", "gs_meshaa_fwd", "gs_meshaa_bwd",
     "gs_tex2d_fwd", "gs_tex2d_bwd", "gs_meshshade_fwd", "gs_meshshade_bwd",
+    "gs_bvh_bytes", "gs_bvh_ws_bytes", "gs_bvh_build", "gs_ray_occluded", "gs_ray_closest",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -153,6 +154,15 @@ def lib() -> C.CDLL:
                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
         l.gs_meshshade_fwd.argtypes = shade_head + [C.c_void_p, C.c_void_p]
         l.gs_meshshade_bwd.argtypes = shade_head + [C.c_void_p] * 8
+        l.gs_bvh_bytes.restype = C.c_size_t
+        l.gs_bvh_bytes.argtypes = [C.c_int64]
+        l.gs_bvh_ws_bytes.restype = C.c_size_t
+        l.gs_bvh_ws_bytes.argtypes = [C.c_int64]
+        l.gs_bvh_build.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        ray_head = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                    C.c_float, C.c_float]
+        l.gs_ray_occluded.argtypes = ray_head + [C.c_void_p, C.c_void_p]
+        l.gs_ray_closest.argtypes = ray_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

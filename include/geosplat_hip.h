@@ -951,6 +951,54 @@ int gs_meshshade_bwd(int H, int W, const float* rast, const float* position, con
                      float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks, const GsEnvGrad* env_grad /*host*/,
                      void* stream);
 
+/* ------------------------------------------------------------------ ray-mesh queries: LBVH, shadow and closest-hit rays ------ */
+/* What the reference's OptiX stages get from optix_build_bvh(ctx, vertices, indices, rebuild=1) and from the shadow test of
+ * optix_env_shade (rfstudio/graphics/_mesh/_optix/c_src/envsampling/kernel.cu:101-118); a restatement of the semantics.
+ * csrc/gs_bvh.hip.  No backward: the reference ignores the shadow boundary gradient (kernel.cu:97-99).
+ *
+ * Mesh: vertices [V,3] fp32, faces [F,3] int32, 1 <= F <= 2^30 (node indices are int32 and there are 2 F - 1 nodes; the Morton
+ *   codes are 30 bits wide and need no limit of their own), V < 2^31.  A face with an index outside [0, V) or with a non-finite
+ *   coordinate is INVALID: never hit, and its vertices are in no box.  A zero-area face is never hit.
+ * Node buffer (the contract the tests walk): 2 F - 1 nodes of 32 bytes, 16-byte aligned,
+ *     struct { float lo[3], hi[3]; int32_t left; int32_t skip; }
+ *   Nodes 0 .. F - 2 are internal (node 0 is the root), node F - 1 + i is the leaf of the i-th face in (Morton code, face index)
+ *   order; with F = 1 node 0 is that leaf.  Internal: left = left child, and the right child is nodes[left].skip.  Leaf: left =
+ *   face index.  skip = the node that follows this node's subtree in depth-first (left before right) order, -1 after the last.
+ *   lo / hi = exact min / max over the vertices of the valid faces below the node; (+inf, -inf) when there are none.  The Morton
+ *   code of a face: 10 bits per axis of its centroid inside the bounds of the valid faces, x in the highest bit; invalid faces
+ *   sort last.  The tree is Karras 2012 over the stably sorted codes, equal codes told apart by their sorted position: two builds
+ *   of the same mesh give the same bytes.
+ * Ray: origin o, direction d (any length; t is in units of |d|), 0-based ray r = p S + s uses origins[p] and dirs[r]
+ *   (dirs_per_point = 1, dirs [P,S,3]) or dirs[s] (dirs_per_point = 0, dirs [S,3] shared by all points).  A ray with a non-finite
+ *   origin or a zero or non-finite direction misses everything.
+ * Triangle test: Woop, Benthin, Wald, "Watertight Ray/Triangle Intersection" (JCGT 2013): kz = the axis of the largest |d|, kx, ky
+ *   the next two (swapped when d[kz] < 0), Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz]; per vertex A = v - o,
+ *   Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz]; U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax in fp32 without
+ *   contraction, recomputed in fp64 when one of them is exactly 0.  Hit iff U, V, W are all >= 0 or all <= 0, det = U + V + W != 0,
+ *   and tmin < t < tmax (both strict) for t = ((U Az + V Bz) + W Cz) / det with Az = Sz A[kz] -- the fp32 value the kernel computes.
+ *   Both sides, no culling.  A ray through a shared edge or vertex hits at least one of the triangles around it.
+ *   Barycentrics (b1, b2) = (V, W) / det weigh vertices 1 and 2.
+ * gs_ray_occluded: out[r] = 1 iff some face is hit.  gs_ray_closest: the hit with the smallest fp32 t, the lowest face index among
+ *   equal t (the rasterizer's depth rule); a miss gives t = +inf, face = -1, bary = 0.  Neither depends on traversal order.
+ * bvh = NULL: every ray tests every face with the same device routine.  That form defines the semantics; with a node buffer the
+ *   result is the same bit for bit (the box test is conservative).  A traversal visits at most 2 F - 1 nodes and range-checks every
+ *   index it reads, so a corrupt node buffer gives misses, not a hang or a fault.
+ *
+ *   gs_bvh_bytes      32 (2 F - 1) (0: F out of range)          gs_bvh_ws_bytes   build workspace, about 60 bytes per face (0: same)
+ *   gs_bvh_build      a full build into `bvh`; rebuilding after the vertices moved is the same call.  No workgroup waits on another.
+ * All return GS_EINVAL before touching the device for F < 1 ("empty mesh"), F > 2^30 ("too many faces"), a buffer or workspace that
+ * is too small, negative P or S, P S >= 2^31, or a null required pointer.  P S == 0 is a no-op. */
+size_t gs_bvh_bytes(int64_t F);
+size_t gs_bvh_ws_bytes(int64_t F);
+int gs_bvh_build(int64_t V, int64_t F, const float* vertices, const int32_t* faces, void* bvh, size_t bvh_bytes, void* ws,
+                 size_t ws_bytes, void* stream);
+int gs_ray_occluded(int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh /* NULL: brute force */,
+                    int64_t P, int S, const float* origins /*[P,3]*/, const float* dirs, int dirs_per_point /* 1: [P,S,3], 0: [S,3] */,
+                    float tmin, float tmax, uint8_t* out /*[P,S]*/, void* stream);
+int gs_ray_closest(int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh /* NULL: brute force */,
+                   int64_t P, int S, const float* origins /*[P,3]*/, const float* dirs, int dirs_per_point, float tmin, float tmax,
+                   float* t /*[P,S]*/, int32_t* face /*[P,S]*/, float* bary /*[P,S,2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
