@@ -39,10 +39,15 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              PrettyShader(occlusion_type='none') (rfstudio/graphics/shaders.py:44-105, 199-233):
                                              dr.texture's 2-D lookup ('wrap' / 'clamp') and the per-pixel split-sum PBR shader, with
                                              gradients to the textures, the environment, the normals and the positions
+  envshade.env_shade / LatLngEnvMap / make_perms, RenderableAttrs.splat_mc
+                                          == optix_env_shade, TextureLatLng.compute_pdf_ and RenderableAttrs.splat_mc without the denoiser
+                                             (rfstudio/graphics/_mesh/_optix/ops.py, _texture.py:287-305, rfstudio/model/geosplat.py:134-244):
+                                             Monte-Carlo shading of a lat-long light with MIS and inline shadow rays on a MeshBVH
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
 from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, sphere_cameras, view_matrix  # noqa: F401
+from .envshade import LatLngEnvMap, env_shade, make_perms  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401
 from .fusion import TSDFVolume, mesh_from_depth_fusion, save_obj  # noqa: F401

@@ -67,6 +67,7 @@ SYMBOLS = [
     "gs_mesh_topology_bytes", "gs_mesh_topology_build", "gs_meshaa_fwd", "gs_meshaa_bwd",
     "gs_tex2d_fwd", "gs_tex2d_bwd", "gs_meshshade_fwd", "gs_meshshade_bwd",
     "gs_bvh_bytes", "gs_bvh_ws_bytes", "gs_bvh_build", "gs_ray_occluded", "gs_ray_closest",
+    "gs_envshade_fwd", "gs_envshade_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -163,6 +164,10 @@ def lib() -> C.CDLL:
                     C.c_float, C.c_float]
         l.gs_ray_occluded.argtypes = ray_head + [C.c_void_p, C.c_void_p]
         l.gs_ray_closest.argtypes = ray_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        env_head = ([C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                    C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
+        l.gs_envshade_fwd.argtypes = env_head + [C.c_void_p] * 7
+        l.gs_envshade_bwd.argtypes = env_head + [C.c_int] + [C.c_void_p] * 8
         _lib = l
     return _lib
 

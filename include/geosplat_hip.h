@@ -999,6 +999,53 @@ int gs_ray_closest(int64_t V, int64_t F, const float* vertices, const int32_t* f
                    int64_t P, int S, const float* origins /*[P,3]*/, const float* dirs, int dirs_per_point, float tmin, float tmax,
                    float* t /*[P,S]*/, int32_t* face /*[P,S]*/, float* bary /*[P,S,2]*/, void* stream);
 
+/* ------------------------------------------------------------------ Monte-Carlo environment shading on the ray routines --------- */
+/* What the reference's stage 2 gets from optix_env_shade (rfstudio/graphics/_mesh/_optix: ops.py, c_src/envsampling/kernel.cu,
+ * c_src/bsdf.h); a restatement of the semantics.  csrc/gs_envshade.hip; tests/envshade_ref.py states the same in float64.
+ *
+ * Points: mask [P], ro (shadow-ray origins), gb_pos, gb_normal, gb_kd, gb_ks [P,3] fp32, one view_pos [3].  gb_ks = (occlusion factor,
+ *   roughness, metallic).  Light: light [H,W,3] lat-long radiance and its tables pdf [H,W], rows [H] (CDF over rows), cols [H,W] (CDF
+ *   inside each row), H, W >= 2.  perms [T, n^2] int32 (T >= 1 permutations of 0 .. n^2 - 1), n = n_samples_x >= 1, 0 <= rnd_seed < 2^31.
+ *   bsdf: 0 pbr, 1 diffuse, 2 white (1 and 2: Lambert only).  Mesh and node buffer as for the ray queries; the node buffer is required.
+ * Per point p with mask > 0 (the others get zeros):
+ *   stream  state = out(seed) ^ out(p) with out() the PCG output function and the LCG s -> 747796405 s + 2891336453 (mod 2^32); draws
+ *     in order: light table = draw % T, bsdf table = draw % T, then per iteration i < n^2 five uniforms (draw & 0xFFFFFF) / 2^24.  Sample
+ *     (p, i) has the same numbers however the work is laid out (a lane enters the stream 2 + 5 i draws in).
+ *   light sample  (sx, sy) = ((perm % n, perm / n) + (u0, u1)) / n in fp32 without contraction; row from `rows`, column from that row
+ *     of `cols` by ceil(log2(size - 1)) + 1 bisection steps on min(x, 0.99999994f), position inside the texel = remainder / width;
+ *     direction (sin t sin f, cos t, -sin t cos f), f = (2 u - 1) pi, t = v pi.  Its density: pdf[nearest texel of the direction]
+ *     W H / (2 pi^2 max(sin t, 1e-4)); the BSDF's mixture pdf of it is 1 when min(n.wo, n.wi) < 1e-6.
+ *   bsdf sample  pDiffuse = (1 - metallic) Y(kd) / (that + Y(Schlick(f0, cos))) (1 when both are 0); u4 < pDiffuse: cosine lobe on the
+ *     branchless basis of the unit normal, otherwise the GGX lobe of visible normals (Heitz 2018) at alpha = roughness^2, reflected;
+ *     pdf = the mixture, a component added only when its weight exceeds 1e-6; pDiffuse < 1e-4 with the diffuse lobe chosen returns the
+ *     normal with pdf 1; a viewer at or below the horizon of the GGX lobe gives the zero direction with pdf 0.
+ *   each of the 2 n^2 samples  L = light[nearest texel], diffuse = max(n.wi / pi, 0), specular (pbr only) = F D G / (4 n.wo) with every
+ *     cosine clamped to [1e-4, 1 - 1e-4], alpha = clamp(roughness^2, 0.08^2, 1), f0 = (0.04 (1 - m) + kd m)(1 - ks.x), 0 unless n.wo and
+ *     n.wi exceed 1e-4; w = 1 / (n^2 max(pdf_light + pdf_bsdf, 1e-4)); vis = 0 if the ray (ro, wi) hits any face for 0 < t < 1e16, else 1;
+ *     V = vis shadow_scale + 1 - shadow_scale.  diff += diffuse L V w, spec += specular L V w, resi += (diffuse, mean specular)(1 - V) w.
+ * gs_envshade_fwd  diff, spec [P,3], resi [P,2] overwritten, no atomics: the same inputs give the same bits.  log_dirs [P, 2 n^2, 3],
+ *   log_pdf_sum, log_vis [P, 2 n^2]: all three or none; slot 2 i is the light sample of iteration i, 2 i + 1 its BSDF sample; only
+ *   slots of points with mask > 0 are written.  Without them that code is not compiled into the kernel that runs.
+ * gs_envshade_bwd  regenerates the samples from ITS rnd_seed; directions, pdfs and V are constants (no gradient through them, none to
+ *   resi).  gb_pos_grad, gb_normal_grad, gb_kd_grad, gb_ks_grad [P,3] overwritten without atomics; light_grad [H,W,3] ACCUMULATED into
+ *   on nearest texels (caller zeroes) with float atomics, after merging the adds of a wave that share a texel in up to merge_rounds
+ *   leader rounds (-1: default).
+ * lanes_per_point: 1 (a thread per point), 16 or 64 lanes share a point's iterations; 0 picks the default.  The arrangement changes
+ *   the order of the per-point sums, nothing else.
+ * Both return GS_EINVAL before touching the device for negative P, H or W below 2, T or n below 1, a seed outside [0, 2^31), an
+ *   unknown bsdf or arrangement, an empty mesh, or a null required pointer.  P == 0 is a no-op. */
+int gs_envshade_fwd(int64_t P, const float* mask, const float* ro, const float* gb_pos, const float* gb_normal, const float* view_pos,
+                    const float* gb_kd, const float* gb_ks, int H, int W, const float* light, const float* pdf, const float* rows,
+                    const float* cols, int T, int n_samples_x, const int32_t* perms, int64_t rnd_seed, int bsdf, float shadow_scale,
+                    int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh, int lanes_per_point, float* diff,
+                    float* spec, float* resi, float* log_dirs, float* log_pdf_sum, float* log_vis, void* stream);
+int gs_envshade_bwd(int64_t P, const float* mask, const float* ro, const float* gb_pos, const float* gb_normal, const float* view_pos,
+                    const float* gb_kd, const float* gb_ks, int H, int W, const float* light, const float* pdf, const float* rows,
+                    const float* cols, int T, int n_samples_x, const int32_t* perms, int64_t rnd_seed, int bsdf, float shadow_scale,
+                    int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh, int lanes_per_point,
+                    int merge_rounds, const float* diff_grad, const float* spec_grad, float* gb_pos_grad, float* gb_normal_grad,
+                    float* gb_kd_grad, float* gb_ks_grad, float* light_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
