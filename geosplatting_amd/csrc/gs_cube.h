@@ -214,10 +214,11 @@ __device__ __forceinline__ void gs_add_scoped(float* p, float v)
 // contiguous floats), so their six atomics are issued by SIX adjacent lanes of one instruction and merge into ONE
 // memory-side request (two when the 24 bytes straddle a cache line or, on a face edge, the second texel lives
 // elsewhere).  Halves the request count of the shading backward, which sits at the fabric's atomic request rate.
-// LDS-staged form of wave_commit6 (below): every lane writes its two pointers and six values into a wave-private
-// [10 words][64 lanes] tile, then reads the (pointer, value) pair it has to issue -- 8 writes + 12 reads per call instead of
-// 60 ds_bpermute, which made the LDS pipe of the CU (8.3 M LDS instructions per launch, 7.4 M of them permutes) a bottleneck
-// of the shading backward.  `stage` = 640 floats of LDS owned by this wave; all 64 lanes call together.
+// The transposition goes through LDS: every lane writes its two pointers and six values into a wave-private
+// [10 words][64 lanes] tile, then reads the (pointer, value) pair it has to issue -- 8 writes + 12 reads per call.  (History: the
+// first form fetched them with 60 ds_bpermute per call, which made the LDS pipe of the CU -- 8.3 M LDS instructions per launch,
+// 7.4 M of them permutes -- a bottleneck of the shading backward; removed.)  `stage` = 640 floats of LDS owned by this wave; all
+// 64 lanes call together.
 template <bool XCD_LOCAL>
 __device__ __forceinline__ void wave_commit6_lds(float* stage, float* pa, float* pb, const float (&v)[6])
 {
@@ -242,36 +243,9 @@ __device__ __forceinline__ void wave_commit6_lds(float* stage, float* pa, float*
     }
 }
 
-template <bool XCD_LOCAL>
-__device__ __forceinline__ void wave_commit6(float* pa, float* pb, const float (&v)[6])
-{
-    const int lane = (int)(threadIdx.x & 63);
-    const unsigned long long ka = (unsigned long long)pa, kb = (unsigned long long)pb;
-    const int alo = (int)(unsigned)ka, ahi = (int)(unsigned)(ka >> 32), blo = (int)(unsigned)kb, bhi = (int)(unsigned)(kb >> 32);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int q = 64 * k + lane;
-        const int src = q / 6, ch = q - 6 * src;
-        const int sa = src << 2;
-        // ds_bpermute: this lane READS the operand of lane `src`; fetch both pointers and all six values, pick by ch
-        const unsigned a_lo = (unsigned)__builtin_amdgcn_ds_bpermute(sa, alo), a_hi = (unsigned)__builtin_amdgcn_ds_bpermute(sa, ahi);
-        const unsigned b_lo = (unsigned)__builtin_amdgcn_ds_bpermute(sa, blo), b_hi = (unsigned)__builtin_amdgcn_ds_bpermute(sa, bhi);
-        float x[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) x[c] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(sa, __builtin_bit_cast(int, v[c])));
-        const bool second = ch >= 3;
-        float* base = (float*)(((unsigned long long)(second ? b_hi : a_hi) << 32) | (second ? b_lo : a_lo));
-        const int c3 = second ? ch - 3 : ch;
-        float val = x[0];
-#pragma unroll
-        for (int c = 1; c < 6; ++c) val = (ch == c) ? x[c] : val;
-        if (base != nullptr) gs_add_scoped<XCD_LOCAL>(base + c3, val);
-    }
-}
-
 // commit one row pair per lane, transposed (a lane without one passes two null pointers)
 template <bool XCD_LOCAL>
-__device__ __forceinline__ void wave_add6(float* pa, float* pb, const float (&v)[6], float* stage = nullptr)
+__device__ __forceinline__ void wave_add6(float* pa, float* pb, const float (&v)[6], float* stage)
 {
     float* enda = nullptr; float* endb = nullptr;
     float pv[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
@@ -280,14 +254,13 @@ __device__ __forceinline__ void wave_add6(float* pa, float* pb, const float (&v)
 #pragma unroll
         for (int c = 0; c < 6; ++c) pv[c] = v[c];
     }
-    if (stage) wave_commit6_lds<XCD_LOCAL>(stage, enda, endb, pv);
-    else wave_commit6<XCD_LOCAL>(enda, endb, pv);
+    wave_commit6_lds<XCD_LOCAL>(stage, enda, endb, pv);
 }
 
 // all 64 lanes of the wave must call this together (lanes without work pass valid == false)
 template <bool XCD_LOCAL>
 __device__ __forceinline__ void cube_scatter_wave(float* grad_tex, const CubeFp& fp, const float* g, float scale, bool valid,
-                                                  float* stage = nullptr)
+                                                  float* stage)
 {
 #pragma unroll
     for (int row = 0; row < 2; ++row) {

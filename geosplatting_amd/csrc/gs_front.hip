@@ -377,8 +377,7 @@ extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // tail: A7 + S1-S3 backward of one view, accumulated into the caller's gradient buffers (always +=)
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
+__global__ void __launch_bounds__(GS_SHADE_BWD_BLOCK)
 tail_bwd_kernel(GsCount vc, const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
                 const float* __restrict__ opacities, const float* __restrict__ normals, const float* __restrict__ kd,
                 const float* __restrict__ ks, const float* __restrict__ viewmat, const float* __restrict__ K,
@@ -390,7 +389,7 @@ tail_bwd_kernel(GsCount vc, const float* __restrict__ means, const float* __rest
     extern __shared__ __attribute__((aligned(16))) float s_grad[];
     for (int i = threadIdx.x; i < eg.lds_floats; i += blockDim.x) s_grad[i] = 0.0f;
     __syncthreads();
-    float* const stage = s_grad + eg.stage_off + (threadIdx.x >> 6) * 640;            // (the tail always stages its row-pair commits)
+    float* const stage = s_grad + eg.stage_off + (threadIdx.x >> 6) * 640;
     // this XCD's private copy of the mid-sized levels (workgroup-scope atomics resolve in the XCD's own L2), or nullptr
     float* const priv = eg.priv ? eg.priv + (long long)gs_xcc_id() * eg.priv_stride : nullptr;
     const float cp[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
@@ -436,57 +435,15 @@ tail_bwd_kernel(GsCount vc, const float* __restrict__ means, const float* __rest
                     float color[3];
                     shade_one<true>(mean, normal, kdn, ksn, cp, min_roughness, max_metallic, mode, env, color, t);
                     scatter = true;
-                    // ---- the arithmetic of shade_bwd_kernel (gs_shade.hip), same order
-                    float v_diff[3] = { 0, 0, 0 }, v_rf[3] = { 0, 0, 0 };
+                    float s_mean[3], v_n[3], o_kd[3], o_ks[2];
+                    shade_one_bwd(t, normal, kdn, g, mode, min_roughness, max_metallic, v_ls, v_ld, o_kd, v_n, o_ks, s_mean);
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        if (mode == GS_MODE_PBR)          { v_diff[c] = g[c]; v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
-                        else if (mode == GS_MODE_DIFFUSE) { v_ld[c] = g[c] * t.diff[c]; v_diff[c] = g[c] * t.ld[c]; }
-                        else                              { v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
+                    for (int k = 0; k < 3; ++k) {
+                        if (!t.wo_const) o_mean[k] += s_mean[k];
+                        v_normals[3 * (size_t)n + k] += v_n[k]; v_kd[3 * (size_t)n + k] += o_kd[k];
                     }
-                    float v_A = 0.0f, v_B = 0.0f, v_metal = 0.0f, o_kd[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float v_spec = v_rf[c] * t.fg[0];
-                        v_A += v_rf[c] * t.spec[c];
-                        v_B += v_rf[c];
-                        o_kd[c] = v_spec * t.metal + v_diff[c] * (1.0f - t.metal);
-                        v_metal += v_spec * (kdn[c] - 0.04f) - v_diff[c] * kdn[c];
-                    }
-                    const float v_ndv = v_A * t.dfg_du[0] + v_B * t.dfg_du[1];
-                    float v_rough = v_A * t.dfg_dv[0] + v_B * t.dfg_dv[1];
-                    float v_mip = 0.0f, v_refl[3] = { 0, 0, 0 }, v_n[3] = { 0, 0, 0 };
-                    if (mode != GS_MODE_DIFFUSE) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            v_mip += v_ls[c] * t.ls.dmip[c];
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) v_refl[k] += v_ls[c] * t.ls.dd[c * 3 + k];
-                        }
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) v_n[k] += v_ld[c] * t.ld_dd[c * 3 + k];
-                    }
-                    v_rough += v_mip * t.dmip_dr;
-                    float v_d = 2.0f * (v_refl[0] * normal[0] + v_refl[1] * normal[1] + v_refl[2] * normal[2]);
-                    float v_wo[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) { v_n[k] += 2.0f * t.d * v_refl[k]; v_wo[k] = -v_refl[k]; }
-                    if (t.d >= 1e-6f) v_d += v_ndv;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) { v_n[k] += v_d * t.wo[k]; v_wo[k] += v_d * normal[k]; }
-                    if (!t.wo_const) {
-                        const float dot = t.wo[0] * v_wo[0] + t.wo[1] * v_wo[1] + t.wo[2] * v_wo[2];
-                        const float l = fmaxf(t.len, 1e-6f);
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) o_mean[k] += -((v_wo[k] - t.wo[k] * dot) / l);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) { v_normals[3 * (size_t)n + k] += v_n[k]; v_kd[3 * (size_t)n + k] += o_kd[k]; }
                     float2 o = *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n);
-                    o.x += v_rough * (1.0f - min_roughness); o.y += v_metal * max_metallic;
+                    o.x += o_ks[0]; o.y += o_ks[1];
                     *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = o;
                 }
 #pragma unroll
@@ -494,44 +451,18 @@ tail_bwd_kernel(GsCount vc, const float* __restrict__ means, const float* __rest
             }
         }
         // ---- texel gradients: LDS-private copies for the small levels, row-pair atomics for the rest (as shade_bwd_kernel)
+        const CommitTagged commit{ priv };
         if (mode != GS_MODE_DIFFUSE) {
-            const int l0 = scatter ? t.ls.l0 : 0, l1 = scatter ? t.ls.l1 : -1;
-            const float w0 = (l1 < 0) ? 1.0f : 1.0f - t.ls.f;
-            const bool lds0 = scatter && eg.lds_level[l0] >= 0;
-            if (lds0) cube_scatter_lds(s_grad + eg.lds_level[l0], t.ls.fp0, v_ls, w0);
-            const bool loc0 = priv != nullptr && eg.priv_level[l0] >= 0;
-            cube_scatter_wave_tagged(scatter && !lds0 ? (loc0 ? priv + eg.priv_level[l0] : eg.levels[l0]) : nullptr, loc0, t.ls.fp0, v_ls, w0,
-                                     scatter && !lds0, stage);
-            const bool has1 = scatter && l1 >= 0;
-            const int l1s = has1 ? l1 : 0;
-            const bool lds1 = has1 && eg.lds_level[l1s] >= 0;
-            if (lds1) cube_scatter_lds(s_grad + eg.lds_level[l1], t.ls.fp1, v_ls, t.ls.f);
-            const bool loc1 = priv != nullptr && eg.priv_level[l1s] >= 0;
-            cube_scatter_wave_tagged(has1 && !lds1 ? (loc1 ? priv + eg.priv_level[l1s] : eg.levels[l1s]) : nullptr, loc1, t.ls.fp1, v_ls, t.ls.f,
-                                     has1 && !lds1, stage);
+            const int l0 = scatter ? t.ls.l0 : -1, l1 = scatter ? t.ls.l1 : -1;
+            env_scatter_wave(eg, s_grad, stage, commit, false, l0, t.ls.fp0, v_ls, (l1 < 0) ? 1.0f : 1.0f - t.ls.f);
+            env_scatter_wave(eg, s_grad, stage, commit, false, l1, t.ls.fp1, v_ls, t.ls.f);
         } else {
-            const bool ldsb = scatter && eg.lds_base >= 0;
-            if (ldsb) cube_scatter_lds(s_grad + eg.lds_base, t.ld_fp, v_ld, 1.0f);
-            cube_scatter_wave_tagged(scatter && !ldsb ? eg.base : nullptr, false, t.ld_fp, v_ld, 1.0f, scatter && !ldsb, stage);
+            env_scatter_wave(eg, s_grad, stage, commit, true, scatter ? 0 : -1, t.ld_fp, v_ld, 1.0f);
         }
     }
     // ---- flush the private copies
     __syncthreads();
-    if (eg.lds_base >= 0) {
-        const int cnt = 18 * env.base_res * env.base_res;
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const float x = s_grad[eg.lds_base + i];
-            if (x != 0.0f) gs_atomic_add(eg.base + i, x);
-        }
-    }
-    for (int l = 0; l < env.L; ++l) {
-        if (eg.lds_level[l] < 0) continue;
-        const int cnt = 18 * env.res[l] * env.res[l];
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const float x = s_grad[eg.lds_level[l] + i];
-            if (x != 0.0f) gs_atomic_add(eg.levels[l] + i, x);
-        }
-    }
+    env_lds_flush(s_grad, eg, env);
 }
 
 // XCD-private copies of the mid-sized specular levels (not in LDS, at most GS_TAIL_PRIV_MAXRES^2 texels per face): float offsets
@@ -548,6 +479,22 @@ static size_t tail_priv_floats(const EnvDev& e, int mode, long long* level_off)
         for (int l = 0; l < e.L; ++l)
             if (e.res[l] > 32 && e.res[l] <= tail_priv_maxres()) { level_off[l] = off; off += 18ll * e.res[l] * e.res[l]; }
     return (size_t)((off + 63) / 64 * 64);
+}
+
+// eg.priv*: the optional XCD-private copies of the mid-sized levels in `priv_ws` (caller-zeroed, accumulated over the views of a
+// step, folded by gs_tail_priv_reduce), or none.  `fn`: the entry point, for the message.
+static int tail_priv_to_dev(const char* fn, const EnvDev& e, int mode, void* priv_ws, size_t priv_ws_bytes, EnvGradDev& eg)
+{
+    const size_t floats = tail_priv_floats(e, mode, eg.priv_level);
+    eg.priv_base = -1;
+    if (priv_ws != nullptr && floats > 0) {
+        if (priv_ws_bytes < floats * sizeof(float) * GS_XCD_COPIES) { gs_set_error("%s: private workspace too small", fn); return GS_ENOSPC; }
+        eg.priv = (float*)priv_ws; eg.priv_stride = (long long)floats;
+    } else {
+        eg.priv = nullptr; eg.priv_stride = 0;
+        for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.priv_level[l] = -1;
+    }
+    return GS_OK;
 }
 
 extern "C" size_t gs_tail_priv_ws_bytes(const GsEnv* env, int mode)
@@ -590,38 +537,17 @@ extern "C" int gs_tail_bwd(int V_cap, const int64_t* counts_dev /* NULL: V_cap i
     GS_CHECK_ARG(env_to_dev(env, e) == 0, "bad GsEnv");
     GS_CHECK_ARG(env_grad != nullptr && vis_records != nullptr && v_packed != nullptr, "null argument");
     EnvGradDev eg;
-    eg.base = env_grad->base;
-    for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.levels[l] = l < e.L ? env_grad->levels[l] : nullptr;
-    if (mode == GS_MODE_DIFFUSE) GS_CHECK_ARG(eg.base != nullptr, "env_grad->base required in diffuse mode");
-    else for (int l = 0; l < e.L; ++l) GS_CHECK_ARG(eg.levels[l] != nullptr, "env_grad->levels[l] required");
+    { const int rc = env_grad_to_dev(__func__, env_grad, e, mode, eg); if (rc != GS_OK) return rc; }
     ShadeBwdPlan plan;
-    { const int rc = shade_bwd_plan(e, mode, V_cap, nullptr, 0, eg, plan, true); if (rc != GS_OK) return rc; }
-    // optional XCD-private copies of the mid-sized levels (caller-zeroed, accumulated over the views of a step, folded by
-    // gs_tail_priv_reduce)
-    {
-        const size_t floats = tail_priv_floats(e, mode, eg.priv_level);
-        if (priv_ws != nullptr && floats > 0) {
-            if (priv_ws_bytes < floats * sizeof(float) * GS_XCD_COPIES) { gs_set_error("gs_tail_bwd: private workspace too small"); return GS_ENOSPC; }
-            eg.priv = (float*)priv_ws; eg.priv_stride = (long long)floats;
-        } else {
-            eg.priv = nullptr; eg.priv_stride = 0;
-            for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.priv_level[l] = -1;
-        }
-    }
+    { const int rc = shade_bwd_plan(e, mode, V_cap, GS_SHADE_BWD_BLOCK, nullptr, 0, eg, plan); if (rc != GS_OK) return rc; }
+    { const int rc = tail_priv_to_dev(__func__, e, mode, priv_ws, priv_ws_bytes, eg); if (rc != GS_OK) return rc; }
     if (V_cap == 0) return GS_OK;
-    hipStream_t s = (hipStream_t)stream;
     const GsCount vc{ (long long)V_cap, (const long long*)counts_dev };
-#define GS_TAIL_LAUNCH(B)                                                                                                              \
-    do {                                                                                                                               \
-        GS_CHECK_HIP(hipFuncSetAttribute((const void*)tail_bwd_kernel<B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes)); \
-        hipLaunchKernelGGL((tail_bwd_kernel<B>), dim3(plan.blocks), dim3(B), plan.lds_bytes, s, vc, means, quats, scales, opacities, normals, \
-                           kd, ks, viewmat, K, cam_pos, min_roughness, max_metallic, mode, e, W, H, eps2d, (const float4*)vis_records,   \
-                           v_packed, rec_stride, v_means, v_quats, v_scales, v_opacities, v_normals, v_kd, v_ks, eg);                    \
-        GS_CHECK_LAUNCH();                                                                                                             \
-    } while (0)
-    if (plan.block == 1024) GS_TAIL_LAUNCH(1024); else if (plan.block == 768) GS_TAIL_LAUNCH(768); else if (plan.block == 256) GS_TAIL_LAUNCH(256);
-    else GS_TAIL_LAUNCH(512);
-#undef GS_TAIL_LAUNCH
+    GS_CHECK_HIP(hipFuncSetAttribute((const void*)tail_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    hipLaunchKernelGGL(tail_bwd_kernel, dim3(plan.blocks), dim3(GS_SHADE_BWD_BLOCK), plan.lds_bytes, (hipStream_t)stream, vc, means, quats,
+                       scales, opacities, normals, kd, ks, viewmat, K, cam_pos, min_roughness, max_metallic, mode, e, W, H, eps2d,
+                       (const float4*)vis_records, v_packed, rec_stride, v_means, v_quats, v_scales, v_opacities, v_normals, v_kd, v_ks, eg);
+    GS_CHECK_LAUNCH();
     return GS_OK;
 }
 
@@ -870,7 +796,7 @@ tail_shade_pairs_kernel(int N, TailViewsDev views, const float* __restrict__ mea
         }
     }
     // ---- flush the private copies
-    __syncthreads();
+    __syncthreads();                                                // (env_lds_flush, inline: the call changes this kernel's instructions)
     if (eg.lds_base >= 0) {
         const int cnt = 18 * env.base_res * env.base_res;
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
@@ -900,22 +826,10 @@ extern "C" int gs_tail_bwd_multi_parts(int parts, int N, int n_views, const GsTa
     EnvDev e;
     GS_CHECK_ARG(env_to_dev(env, e) == 0, "bad GsEnv");
     EnvGradDev eg;
-    eg.base = env_grad->base;
-    for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.levels[l] = l < e.L ? env_grad->levels[l] : nullptr;
-    if (mode == GS_MODE_DIFFUSE) GS_CHECK_ARG(eg.base != nullptr, "env_grad->base required in diffuse mode");
-    else for (int l = 0; l < e.L; ++l) GS_CHECK_ARG(eg.levels[l] != nullptr, "env_grad->levels[l] required");
-    ShadeBwdPlan plan;
-    { const int rc = shade_bwd_plan(e, mode, N, nullptr, 0, eg, plan, true, GS_TAILP_BLOCK); if (rc != GS_OK) return rc; }
-    {
-        const size_t floats = tail_priv_floats(e, mode, eg.priv_level);
-        if (priv_ws != nullptr && floats > 0) {
-            if (priv_ws_bytes < floats * sizeof(float) * GS_XCD_COPIES) { gs_set_error("gs_tail_bwd_multi: private workspace too small"); return GS_ENOSPC; }
-            eg.priv = (float*)priv_ws; eg.priv_stride = (long long)floats;
-        } else {
-            eg.priv = nullptr; eg.priv_stride = 0;
-            for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.priv_level[l] = -1;
-        }
-    }
+    { const int rc = env_grad_to_dev(__func__, env_grad, e, mode, eg); if (rc != GS_OK) return rc; }
+    ShadeBwdPlan plan;                                                  // (its LDS layout; the pair kernels size their own grid)
+    { const int rc = shade_bwd_plan(e, mode, N, GS_TAILP_BLOCK, nullptr, 0, eg, plan); if (rc != GS_OK) return rc; }
+    { const int rc = tail_priv_to_dev("gs_tail_bwd_multi", e, mode, priv_ws, priv_ws_bytes, eg); if (rc != GS_OK) return rc; }
     if (N == 0) return GS_OK;
     hipStream_t s = (hipStream_t)stream;
     for (int v0 = 0; v0 < n_views; v0 += GS_TAIL_MAX_VIEWS) {             // more than 8 views: further launches ADD to the first

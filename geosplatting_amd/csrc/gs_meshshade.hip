@@ -23,7 +23,6 @@
 #include "gs_shade_dev.h"
 
 #define GS_MS_BLOCK 512                       // backward block (2 waves per SIMD: 256 registers for the recomputed forward)
-#define GS_MS_LDS_FLOATS (128 * 1024 / 4)     // LDS budget of the private gradient copies
 #define GS_MS_TEX_LDS_FLOATS 8192             // a 2-D texture of at most this many floats gets a private copy
 
 struct Tex2Dev { const float* data; int W, H; };
@@ -295,13 +294,8 @@ meshshade_fwd_kernel(long long P, const float* __restrict__ rast, const float* _
     color[3 * p] = out[0]; color[3 * p + 1] = out[1]; color[3 * p + 2] = out[2];
 }
 
-struct MsGradDev {
-    float* kd; float* ks; float* base;
-    float* levels[GS_MAX_LEVELS];
-    int lds_kd, lds_ks, lds_base;              // float offsets of the private LDS copies, or -1
-    int lds_level[GS_MAX_LEVELS];
-    int lds_floats, stage_off;
-};
+// the two 2-D textures' gradients, beside the environment's (EnvGradDev): pointers and float offsets of the private LDS copies, or -1
+struct MsGradDev { float* kd; float* ks; int lds_kd, lds_ks; };
 
 // texel gradients of one 3-channel 2-D texture; all 64 lanes of the wave call together (`act`: this lane has a contribution)
 __device__ __forceinline__ void ms_tex_scatter(float* glob, float* s_grad, int lds_off, const Tex2Dev& tex, const Tex2Fp& fp,
@@ -338,24 +332,16 @@ __device__ __forceinline__ void ms_tex_scatter(float* glob, float* s_grad, int l
     }
 }
 
-// texel gradients of one cube level; all 64 lanes call together
-__device__ __forceinline__ void ms_cube_scatter(float* glob, float* s_grad, int lds_off, const CubeFp& fp, const float* v, float scale,
-                                                bool act, float* stage)
-{
-    if (lds_off >= 0) { if (act) cube_scatter_lds(s_grad + lds_off, fp, v, scale); }
-    else cube_scatter_wave<false>(act ? glob : nullptr, fp, v, scale, act, stage);
-}
-
 __global__ void __launch_bounds__(GS_MS_BLOCK)
 meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* __restrict__ position, const float* __restrict__ normal,
                      const float* __restrict__ uv, Tex2Dev kd, Tex2Dev ks, const float* __restrict__ cam_pos, EnvDev env, MsCfg cfg,
                      const float* __restrict__ d_color, float* __restrict__ d_position, float* __restrict__ d_normal,
-                     float* __restrict__ d_uv, MsGradDev mg)
+                     float* __restrict__ d_uv, MsGradDev mg, EnvGradDev eg)
 {
     extern __shared__ __attribute__((aligned(16))) float s_grad[];
-    for (int i = threadIdx.x; i < mg.lds_floats; i += blockDim.x) s_grad[i] = 0.0f;
+    for (int i = threadIdx.x; i < eg.lds_floats; i += blockDim.x) s_grad[i] = 0.0f;
     __syncthreads();
-    float* const stage = s_grad + mg.stage_off + (threadIdx.x >> 6) * 640;
+    float* const stage = s_grad + eg.stage_off + (threadIdx.x >> 6) * 640;
     const float cam[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
     const long long span = (long long)gridDim.x * blockDim.x;
     const int n_iter = (int)((P + span - 1) / span);                  // wave-uniform: every lane reaches the wave-wide commits
@@ -449,21 +435,15 @@ meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* _
         // ---- texel gradients (wave-wide: inactive lanes take part with nothing to add)
         ms_tex_scatter(mg.kd, s_grad, mg.lds_kd, kd, t.kd_fp, v_kd, act, stage);
         ms_tex_scatter(mg.ks, s_grad, mg.lds_ks, ks, t.ks_fp, v_ks, act, stage);
-        ms_cube_scatter(mg.base, s_grad, mg.lds_base, fp_b, v_ld, 1.0f, act, stage);
-        {
-            const bool lds0 = mg.lds_level[l0] >= 0;
-            const float w0 = l1 < 0 ? 1.0f : 1.0f - f;
-            if (lds0) { if (act) cube_scatter_lds(s_grad + mg.lds_level[l0], fp0, v_ls, w0); }
-            cube_scatter_wave<false>(act && !lds0 ? mg.levels[l0] : nullptr, fp0, v_ls, w0, act && !lds0, stage);
-            const bool has1 = act && l1 >= 0;
-            const int l1s = has1 ? l1 : 0;
-            const bool lds1 = mg.lds_level[l1s] >= 0;
-            if (lds1) { if (has1) cube_scatter_lds(s_grad + mg.lds_level[l1s], fp1, v_ls, f); }
-            cube_scatter_wave<false>(has1 && !lds1 ? mg.levels[l1s] : nullptr, fp1, v_ls, f, has1 && !lds1, stage);
-        }
+        const CommitDevice commit{};
+        env_scatter_wave(eg, s_grad, stage, commit, true, act ? 0 : -1, fp_b, v_ld, 1.0f);
+        env_scatter_wave(eg, s_grad, stage, commit, false, act ? l0 : -1, fp0, v_ls, l1 < 0 ? 1.0f : 1.0f - f);
+        env_scatter_wave(eg, s_grad, stage, commit, false, act ? l1 : -1, fp1, v_ls, f);
     }
     // ---- flush the private copies: one global atomic per non-zero float and block
     __syncthreads();
+    // (kd, ks: lds_flush_array, inline -- with the two calls the compiler contracts four more multiply-adds of the chain rule above, and
+    // d_position / d_normal / d_uv no longer have the bits they had)
     if (mg.lds_kd >= 0) {
         const int cnt = 3 * kd.W * kd.H;
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_kd + i]; if (v != 0.0f) gs_atomic_add(mg.kd + i, v); }
@@ -472,15 +452,7 @@ meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* _
         const int cnt = 3 * ks.W * ks.H;
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_ks + i]; if (v != 0.0f) gs_atomic_add(mg.ks + i, v); }
     }
-    if (mg.lds_base >= 0) {
-        const int cnt = 18 * env.base_res * env.base_res;
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_base + i]; if (v != 0.0f) gs_atomic_add(mg.base + i, v); }
-    }
-    for (int l = 0; l < env.L; ++l) {
-        if (mg.lds_level[l] < 0) continue;
-        const int cnt = 18 * env.res[l] * env.res[l];
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_level[l] + i]; if (v != 0.0f) gs_atomic_add(mg.levels[l] + i, v); }
-    }
+    env_lds_flush(s_grad, eg, env);
 }
 
 static int meshshade_check(const char* fn, int H, int W, int kd_h, int kd_w, int ks_h, int ks_w, int occlusion, const GsEnv* env, EnvDev& e)
@@ -522,28 +494,18 @@ extern "C" int gs_meshshade_bwd(int H, int W, const float* rast, const float* po
     GS_CHECK_ARG(rast != nullptr && position != nullptr && normal != nullptr && uv != nullptr && kd != nullptr && ks != nullptr &&
                  cam_pos != nullptr && d_color != nullptr && d_position != nullptr && d_normal != nullptr && d_uv != nullptr &&
                  d_kd != nullptr && d_ks != nullptr && env_grad != nullptr && env_grad->base != nullptr, "null pointer");
-    for (int l = 0; l < e.L; ++l) GS_CHECK_ARG(env_grad->levels[l] != nullptr, "env_grad->levels[l] required");
     const long long P = (long long)H * W;
-    MsGradDev mg;
-    mg.kd = d_kd; mg.ks = d_ks; mg.base = env_grad->base;
-    for (int l = 0; l < GS_MAX_LEVELS; ++l) { mg.levels[l] = l < e.L ? env_grad->levels[l] : nullptr; mg.lds_level[l] = -1; }
+    EnvGradDev eg;
+    { const int rc = env_grad_to_dev(__func__, env_grad, e, GS_MODE_PBR, eg); if (rc != GS_OK) return rc; }
+    eg.priv = nullptr; eg.priv_stride = 0; eg.priv_base = -1;
+    for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.priv_level[l] = -1;
     // LDS layout: the two textures, the base level, then the pyramid from its coarsest level up, while they fit
+    MsGradDev mg = { d_kd, d_ks, -1, -1 };
     int used = 0;
     const long long kd_f = 3ll * kd_h * kd_w, ks_f = 3ll * ks_h * ks_w;
-    mg.lds_kd = mg.lds_ks = mg.lds_base = -1;
     if (kd_f <= GS_MS_TEX_LDS_FLOATS) { mg.lds_kd = used; used += (int)kd_f; }
     if (ks_f <= GS_MS_TEX_LDS_FLOATS) { mg.lds_ks = used; used += (int)ks_f; }
-    {
-        const long long cnt = 18ll * e.base_res * e.base_res;
-        if (e.base_res <= 32 && used + cnt <= GS_MS_LDS_FLOATS) { mg.lds_base = used; used += (int)cnt; }
-    }
-    for (int l = e.L - 1; l >= 0; --l) {
-        const long long cnt = 18ll * e.res[l] * e.res[l];
-        if (e.res[l] <= 32 && used + cnt <= GS_MS_LDS_FLOATS) { mg.lds_level[l] = used; used += (int)cnt; }
-    }
-    mg.lds_floats = used;
-    mg.stage_off = (used + 3) & ~3;
-    const size_t lds_bytes = (size_t)(mg.stage_off + (GS_MS_BLOCK / 64) * 640) * sizeof(float);
+    const size_t lds_bytes = env_lds_stage(env_lds_place(e, true, true, used, eg), GS_MS_BLOCK, eg);
     // persistent blocks, one flush each: as many as are resident at once -- ONE per compute unit (512 threads at 256 registers are the
     // 2 waves per SIMD a CU holds, whatever the LDS use)
     static int n_cu = 0;
@@ -561,7 +523,7 @@ extern "C" int gs_meshshade_bwd(int H, int W, const float* rast, const float* po
     const Tex2Dev tkd = { kd, kd_w, kd_h }, tks = { ks, ks_w, ks_h };
     GS_CHECK_HIP(hipFuncSetAttribute((const void*)meshshade_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(meshshade_bwd_kernel, dim3(blocks), dim3(GS_MS_BLOCK), lds_bytes, (hipStream_t)stream, P, rast, position, normal, uv,
-                       tkd, tks, cam_pos, e, cfg, d_color, d_position, d_normal, d_uv, mg);
+                       tkd, tks, cam_pos, e, cfg, d_color, d_position, d_normal, d_uv, mg, eg);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }

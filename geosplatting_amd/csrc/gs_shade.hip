@@ -43,15 +43,15 @@ shade_fwd_kernel(int N, const float* __restrict__ means, const float* __restrict
 // 160 KB LDS).  2 M Gaussians send ~13 M atomics at the 4 608 floats of the 16^2 level alone: in HBM/L2 that
 // serialises per address (5.5 ms per view measured); in LDS it is a ds_add_f32 and the block flushes its
 // copy once at the end.
-// Block size (512) and the largest LDS-privatised level (32^2) were run-time choices while they were being measured:
-// the round-1 shape -- 1024-thread blocks, one per CU, levels <= 32^2 in 92 KB of LDS -- caps the kernel at 128 VGPRs and it
-// SPILLS (264 bytes of scratch per lane, -Rpass-analysis): the recomputed forward then runs at a fifth of the forward
-// kernel's rate.  Smaller blocks lift the cap (256 registers at 2 waves per SIMD).  Measured at the bench workload (scripts/shade_ab.py):
-// 1024 threads / <= 32^2 in LDS 470 us (round 1); 512 / 32^2 389 us (default); 256 / 32^2 527 (4 waves per CU); 512 or 256 with only
+// Block size (512, GS_SHADE_BWD_BLOCK) and the largest LDS-privatised level (32^2) are fixed; history of how they were measured:
+// the round-1 shape -- 1024-thread blocks, one per CU, levels <= 32^2 in 92 KB of LDS -- capped the kernel at 128 VGPRs and it
+// SPILLED (264 bytes of scratch per lane, -Rpass-analysis): the recomputed forward then ran at a fifth of the forward
+// kernel's rate.  Smaller blocks lift the cap (256 registers at 2 waves per SIMD).  Measured at the bench workload:
+// 1024 threads / <= 32^2 in LDS 470 us (round 1); 512 / 32^2 389 us (kept); 256 / 32^2 527 (4 waves per CU); 512 or 256 with only
 // the 16^2 level in LDS 930-960 (the 32^2 level through memory-side atomics: 2 800 requests per cache line); no LDS copies 1 570.
 // Removal experiment at 512 / 32^2: 349 us without the LDS atomics, 333 without the global ones, 254 without either.
-template <bool PRIV, int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
+template <bool PRIV>
+__global__ void __launch_bounds__(GS_SHADE_BWD_BLOCK)
 shade_bwd_kernel(int N, const float* __restrict__ means, const float* __restrict__ normals,
                  const float* __restrict__ kd, const float* __restrict__ ks, const float* __restrict__ cam_pos,
                  float min_roughness, float max_metallic, int mode, EnvDev env, const float* __restrict__ v_colors,
@@ -64,107 +64,59 @@ shade_bwd_kernel(int N, const float* __restrict__ means, const float* __restrict
     // this block's XCD-private accumulator copy (device-scope fp32 atomics are resolved at the memory side of the
     // fabric -- a 32-byte write-through each, 0.6 GB per view here; XCD-local ones stay in the 4 MiB L2)
     float* const priv = PRIV ? eg.priv + (long long)gs_xcc_id() * eg.priv_stride : nullptr;
-    // wave-private commit staging behind the private texel copies (640 floats per wave, see wave_commit6_lds); -1 = permute form
-    float* const stage = eg.stage_off >= 0 ? s_grad + eg.stage_off + (threadIdx.x >> 6) * 640 : nullptr;
+    // wave-private commit staging behind the private texel copies (640 floats per wave, see wave_commit6_lds)
+    float* const stage = s_grad + eg.stage_off + (threadIdx.x >> 6) * 640;
     const float cp[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
     // wave-uniform trip count: every lane of a wave reaches the wave-wide scatter together
     const int n_iter = (N + (int)(gridDim.x * blockDim.x) - 1) / (int)(gridDim.x * blockDim.x);
     for (int it = 0; it < n_iter; ++it) {
         const int n = it * (int)(gridDim.x * blockDim.x) + blockIdx.x * blockDim.x + threadIdx.x;
-        const bool live = n < N;
         bool scatter = false;              // this lane has texel gradients to commit
         ShadeTmp t;
         float v_ls[3] = { 0, 0, 0 }, v_ld[3] = { 0, 0, 0 };
-        if (live) {
-        const float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
-        const float normal[3] = { normals[3 * (size_t)n], normals[3 * (size_t)n + 1], normals[3 * (size_t)n + 2] };
-        const float kdn[3] = { kd[3 * (size_t)n], kd[3 * (size_t)n + 1], kd[3 * (size_t)n + 2] };
-        const float2 ks2 = *reinterpret_cast<const float2*>(ks + 2 * (size_t)n);
-        const float ksn[2] = { ks2.x, ks2.y };
-        const float g[3] = { v_colors[3 * (size_t)n], v_colors[3 * (size_t)n + 1], v_colors[3 * (size_t)n + 2] };
-        if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) {
-            // Gaussian that reached no pixel (culled, hidden behind the opaque front layer, ...): every gradient
-            // of the shading is exactly zero -- skip the texture taps and the texel atomics
+        if (n < N) {
+            const float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
+            const float normal[3] = { normals[3 * (size_t)n], normals[3 * (size_t)n + 1], normals[3 * (size_t)n + 2] };
+            const float kdn[3] = { kd[3 * (size_t)n], kd[3 * (size_t)n + 1], kd[3 * (size_t)n + 2] };
+            const float2 ks2 = *reinterpret_cast<const float2*>(ks + 2 * (size_t)n);
+            const float ksn[2] = { ks2.x, ks2.y };
+            const float g[3] = { v_colors[3 * (size_t)n], v_colors[3 * (size_t)n + 1], v_colors[3 * (size_t)n + 2] };
+            if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) {
+                // Gaussian that reached no pixel (culled, hidden behind the opaque front layer, ...): every gradient
+                // of the shading is exactly zero -- skip the texture taps and the texel atomics
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (!accumulate) { v_means[3 * (size_t)n + k] = 0.0f; v_normals[3 * (size_t)n + k] = 0.0f; v_kd[3 * (size_t)n + k] = 0.0f; }
+                for (int k = 0; k < 3; ++k) {
+                    if (!accumulate) { v_means[3 * (size_t)n + k] = 0.0f; v_normals[3 * (size_t)n + k] = 0.0f; v_kd[3 * (size_t)n + k] = 0.0f; }
+                }
+                if (!accumulate) *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = make_float2(0.0f, 0.0f);
+            } else {
+                float color[3], o_mean[3], v_n[3], o_kd[3], o_ks[2];
+                shade_one<true>(mean, normal, kdn, ksn, cp, min_roughness, max_metallic, mode, env, color, t);
+                shade_one_bwd(t, normal, kdn, g, mode, min_roughness, max_metallic, v_ls, v_ld, o_kd, v_n, o_ks, o_mean);
+                scatter = true;
+                if (accumulate) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        v_means[3 * (size_t)n + k] += o_mean[k];
+                        v_normals[3 * (size_t)n + k] += v_n[k];
+                        v_kd[3 * (size_t)n + k] += o_kd[k];
+                    }
+                    float2 o = *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n);
+                    o.x += o_ks[0]; o.y += o_ks[1];
+                    *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = o;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        v_means[3 * (size_t)n + k] = o_mean[k];
+                        v_normals[3 * (size_t)n + k] = v_n[k];
+                        v_kd[3 * (size_t)n + k] = o_kd[k];
+                    }
+                    *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = make_float2(o_ks[0], o_ks[1]);
+                }
             }
-            if (!accumulate) *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = make_float2(0.0f, 0.0f);
-        } else {
-        float color[3];
-        shade_one<true>(mean, normal, kdn, ksn, cp, min_roughness, max_metallic, mode, env, color, t);
-        scatter = true;
-
-        float v_diff[3] = { 0, 0, 0 }, v_rf[3] = { 0, 0, 0 };
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (mode == GS_MODE_PBR)          { v_diff[c] = g[c]; v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
-            else if (mode == GS_MODE_DIFFUSE) { v_ld[c] = g[c] * t.diff[c]; v_diff[c] = g[c] * t.ld[c]; }
-            else                              { v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
         }
-        float v_A = 0.0f, v_B = 0.0f, v_metal = 0.0f, o_kd[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v_spec = v_rf[c] * t.fg[0];
-            v_A += v_rf[c] * t.spec[c];
-            v_B += v_rf[c];
-            o_kd[c] = v_spec * t.metal + v_diff[c] * (1.0f - t.metal);
-            v_metal += v_spec * (kdn[c] - 0.04f) - v_diff[c] * kdn[c];
-        }
-        const float v_ndv = v_A * t.dfg_du[0] + v_B * t.dfg_du[1];
-        float v_rough = v_A * t.dfg_dv[0] + v_B * t.dfg_dv[1];
-        float v_mip = 0.0f, v_refl[3] = { 0, 0, 0 }, v_n[3] = { 0, 0, 0 };
-        if (mode != GS_MODE_DIFFUSE) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                v_mip += v_ls[c] * t.ls.dmip[c];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) v_refl[k] += v_ls[c] * t.ls.dd[c * 3 + k];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) v_n[k] += v_ld[c] * t.ld_dd[c * 3 + k];
-        }
-        v_rough += v_mip * t.dmip_dr;
-        float v_d = 2.0f * (v_refl[0] * normal[0] + v_refl[1] * normal[1] + v_refl[2] * normal[2]);
-        float v_wo[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { v_n[k] += 2.0f * t.d * v_refl[k]; v_wo[k] = -v_refl[k]; }
-        if (t.d >= 1e-6f) v_d += v_ndv;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { v_n[k] += v_d * t.wo[k]; v_wo[k] += v_d * normal[k]; }
-        float o_mean[3] = { 0, 0, 0 };
-        if (!t.wo_const) {
-            const float dot = t.wo[0] * v_wo[0] + t.wo[1] * v_wo[1] + t.wo[2] * v_wo[2];
-            const float l = fmaxf(t.len, 1e-6f);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o_mean[k] = -((v_wo[k] - t.wo[k] * dot) / l);
-        }
-        if (accumulate) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                v_means[3 * (size_t)n + k] += o_mean[k];
-                v_normals[3 * (size_t)n + k] += v_n[k];
-                v_kd[3 * (size_t)n + k] += o_kd[k];
-            }
-            float2 o = *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n);
-            o.x += v_rough * (1.0f - min_roughness); o.y += v_metal * max_metallic;
-            *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = o;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                v_means[3 * (size_t)n + k] = o_mean[k];
-                v_normals[3 * (size_t)n + k] = v_n[k];
-                v_kd[3 * (size_t)n + k] = o_kd[k];
-            }
-            *reinterpret_cast<float2*>(v_ks + 2 * (size_t)n) = make_float2(v_rough * (1.0f - min_roughness), v_metal * max_metallic);
-        }
-
-        }   // non-zero upstream gradient
-        }   // live
         // ---- texel gradients: LDS-private copies for the small levels, row-pair atomics (cube_scatter_wave) for the rest
+        //      (env_scatter_wave, inline: through the helper this kernel measured 2-5 % slower, 360 against 350 us)
         if (mode != GS_MODE_DIFFUSE) {
             const int l0 = scatter ? t.ls.l0 : 0, l1 = scatter ? t.ls.l1 : -1;
             const float w0 = (l1 < 0) ? 1.0f : 1.0f - t.ls.f;
@@ -186,21 +138,7 @@ shade_bwd_kernel(int N, const float* __restrict__ means, const float* __restrict
     }
     // ---- flush the private copies
     __syncthreads();
-    if (eg.lds_base >= 0) {
-        const int cnt = 18 * env.base_res * env.base_res;
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const float v = s_grad[eg.lds_base + i];
-            if (v != 0.0f) gs_atomic_add(eg.base + i, v);
-        }
-    }
-    for (int l = 0; l < env.L; ++l) {
-        if (eg.lds_level[l] < 0) continue;
-        const int cnt = 18 * env.res[l] * env.res[l];
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const float v = s_grad[eg.lds_level[l] + i];
-            if (v != 0.0f) gs_atomic_add(eg.levels[l] + i, v);
-        }
-    }
+    env_lds_flush(s_grad, eg, env);
 }
 
 extern "C" int gs_shade_fwd(int N, const float* means, const float* normals, const float* kd, const float* ks,
@@ -231,7 +169,7 @@ extern "C" int gs_shade_bwd_plan_blocks(const GsEnv* env, int mode, int N, int* 
     if (env_to_dev(env, e) != 0 || mode < 0 || mode > 2 || N < 0) return 0;
     EnvGradDev eg;
     ShadeBwdPlan plan;
-    if (shade_bwd_plan(e, mode, N, nullptr, 0, eg, plan) != GS_OK) return 0;
+    if (shade_bwd_plan(e, mode, N, GS_SHADE_BWD_BLOCK, nullptr, 0, eg, plan) != GS_OK) return 0;
     if (block_threads) *block_threads = plan.block;
     return plan.blocks;
 }
@@ -245,29 +183,22 @@ extern "C" int gs_shade_bwd(int N, const float* means, const float* normals, con
     GS_CHECK_ARG(N >= 0 && mode >= 0 && mode <= 2, "bad N or mode");
     EnvDev e;
     GS_CHECK_ARG(env_to_dev(env, e) == 0, "bad GsEnv");
-    GS_CHECK_ARG(env_grad != nullptr, "env_grad must not be NULL");
     EnvGradDev eg;
-    eg.base = env_grad->base;
-    for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.levels[l] = l < e.L ? env_grad->levels[l] : nullptr;
-    if (mode == GS_MODE_DIFFUSE) GS_CHECK_ARG(eg.base != nullptr, "env_grad->base required in diffuse mode");
-    else for (int l = 0; l < e.L; ++l) GS_CHECK_ARG(eg.levels[l] != nullptr, "env_grad->levels[l] required");
+    { const int rc = env_grad_to_dev(__func__, env_grad, e, mode, eg); if (rc != GS_OK) return rc; }
     ShadeBwdPlan plan;
-    { const int rc = shade_bwd_plan(e, mode, N, ws, ws_bytes, eg, plan); if (rc != GS_OK) return rc; }
+    { const int rc = shade_bwd_plan(e, mode, N, GS_SHADE_BWD_BLOCK, ws, ws_bytes, eg, plan); if (rc != GS_OK) return rc; }
     if (N == 0) return GS_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int s_block = plan.block, blocks = plan.blocks;
-    const size_t lds_bytes = plan.lds_bytes, priv_floats = plan.priv_floats;
-    const bool use_priv = plan.use_priv;
-    if (use_priv) {
-        GS_CHECK_HIP(gs_zero_async(ws, priv_floats * sizeof(float) * GS_XCD_COPIES, s));
-#define GS_SHADE_LAUNCH(P, B)                                                                                                   \
-        do {                                                                                                                    \
-            GS_CHECK_HIP(hipFuncSetAttribute((const void*)shade_bwd_kernel<P, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-            hipLaunchKernelGGL((shade_bwd_kernel<P, B>), dim3(blocks), dim3(B), lds_bytes, s, N, means, normals, kd, ks, cam_pos,     \
-                               min_roughness, max_metallic, mode, e, v_colors, v_means, v_normals, v_kd, v_ks, eg, accumulate);   \
-            GS_CHECK_LAUNCH();                                                                                                  \
-        } while (0)
-        if (s_block == 1024) GS_SHADE_LAUNCH(true, 1024); else if (s_block == 768) GS_SHADE_LAUNCH(true, 768); else if (s_block == 512) GS_SHADE_LAUNCH(true, 512); else GS_SHADE_LAUNCH(true, 256);
+#define GS_SHADE_LAUNCH(P)                                                                                                      \
+    do {                                                                                                                        \
+        GS_CHECK_HIP(hipFuncSetAttribute((const void*)shade_bwd_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes)); \
+        hipLaunchKernelGGL((shade_bwd_kernel<P>), dim3(plan.blocks), dim3(GS_SHADE_BWD_BLOCK), plan.lds_bytes, s, N, means, normals, kd, ks, \
+                           cam_pos, min_roughness, max_metallic, mode, e, v_colors, v_means, v_normals, v_kd, v_ks, eg, accumulate); \
+        GS_CHECK_LAUNCH();                                                                                                      \
+    } while (0)
+    if (plan.use_priv) {
+        GS_CHECK_HIP(gs_zero_async(ws, plan.priv_floats * sizeof(float) * GS_XCD_COPIES, s));
+        GS_SHADE_LAUNCH(true);
         // fold the 8 copies into the caller's gradient buffers, level by level
         for (int l = -1; l < e.L; ++l) {
             const long long off = l < 0 ? eg.priv_base : eg.priv_level[l];
@@ -276,13 +207,13 @@ extern "C" int gs_shade_bwd(int N, const float* means, const float* normals, con
             float* dst = l < 0 ? eg.base : eg.levels[l];
             const long long n = 18ll * R * R;
             hipLaunchKernelGGL(priv_reduce_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, s, n,
-                               GS_XCD_COPIES, (const float*)ws + off, (long long)priv_floats, dst);
+                               GS_XCD_COPIES, (const float*)ws + off, (long long)plan.priv_floats, dst);
             GS_CHECK_LAUNCH();
         }
     } else {
-        if (s_block == 1024) GS_SHADE_LAUNCH(false, 1024); else if (s_block == 768) GS_SHADE_LAUNCH(false, 768); else if (s_block == 512) GS_SHADE_LAUNCH(false, 512); else GS_SHADE_LAUNCH(false, 256);
-#undef GS_SHADE_LAUNCH
+        GS_SHADE_LAUNCH(false);
     }
+#undef GS_SHADE_LAUNCH
     return GS_OK;
 }
 

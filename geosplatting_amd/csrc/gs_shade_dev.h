@@ -25,7 +25,7 @@ struct EnvGradDev {
     int lds_base;
     int lds_level[GS_MAX_LEVELS];
     int lds_floats;
-    int stage_off;                 // float offset of the per-wave commit staging (640 floats per wave) or -1
+    int stage_off;                 // float offset of the per-wave commit staging (640 floats per wave)
     // per-XCD private accumulators for the levels that do not fit LDS (XCD-local atomics, reduced afterwards):
     // copy x of level l lives at priv + x * priv_stride + priv_level[l] (floats); priv == nullptr -> device atomics
     float* priv;
@@ -174,6 +174,65 @@ __device__ void shade_one(const float* mean, const float* normal, const float* k
         else if (mode == GS_MODE_DIFFUSE) color[c] = t.ld[c] * t.diff[c];
         else                              color[c] = t.ls.out[c] * t.refl_c[c];
     }
+}
+
+// The chain rule behind shade_one<true> (shade_bwd_kernel, tail_bwd_kernel): colour cotangent g -> the texel cotangents v_ls / v_ld
+// (only the one the mode samples is written) and the parameter gradients o_kd, v_n, v_ks (scaled to the raw ks) and the
+// view-direction part of the mean's, o_mean.  One rounding per operation, in the order of oracle/gs_oracle_shade.c: the per-Gaussian
+// gradients are compared with the oracle bit for bit.
+__device__ __forceinline__ void shade_one_bwd(const ShadeTmp& t, const float* normal, const float* kd, const float* g, int mode,
+                                              float min_roughness, float max_metallic, float* v_ls, float* v_ld, float* o_kd, float* v_n,
+                                              float* v_ks, float* o_mean)
+{
+    float v_diff[3] = { 0, 0, 0 }, v_rf[3] = { 0, 0, 0 };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (mode == GS_MODE_PBR)          { v_diff[c] = g[c]; v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
+        else if (mode == GS_MODE_DIFFUSE) { v_ld[c] = g[c] * t.diff[c]; v_diff[c] = g[c] * t.ld[c]; }
+        else                              { v_ls[c] = g[c] * t.refl_c[c]; v_rf[c] = g[c] * t.ls.out[c]; }
+    }
+    float v_A = 0.0f, v_B = 0.0f, v_metal = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v_spec = v_rf[c] * t.fg[0];
+        v_A += v_rf[c] * t.spec[c];
+        v_B += v_rf[c];
+        o_kd[c] = v_spec * t.metal + v_diff[c] * (1.0f - t.metal);
+        v_metal += v_spec * (kd[c] - 0.04f) - v_diff[c] * kd[c];
+    }
+    const float v_ndv = v_A * t.dfg_du[0] + v_B * t.dfg_du[1];
+    float v_rough = v_A * t.dfg_dv[0] + v_B * t.dfg_dv[1];
+    float v_mip = 0.0f, v_refl[3] = { 0, 0, 0 };
+    v_n[0] = v_n[1] = v_n[2] = 0.0f;
+    if (mode != GS_MODE_DIFFUSE) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v_mip += v_ls[c] * t.ls.dmip[c];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v_refl[k] += v_ls[c] * t.ls.dd[c * 3 + k];
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v_n[k] += v_ld[c] * t.ld_dd[c * 3 + k];
+    }
+    v_rough += v_mip * t.dmip_dr;
+    float v_d = 2.0f * (v_refl[0] * normal[0] + v_refl[1] * normal[1] + v_refl[2] * normal[2]);
+    float v_wo[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v_n[k] += 2.0f * t.d * v_refl[k]; v_wo[k] = -v_refl[k]; }
+    if (t.d >= 1e-6f) v_d += v_ndv;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v_n[k] += v_d * t.wo[k]; v_wo[k] += v_d * normal[k]; }
+    o_mean[0] = o_mean[1] = o_mean[2] = 0.0f;
+    if (!t.wo_const) {
+        const float dot = t.wo[0] * v_wo[0] + t.wo[1] * v_wo[1] + t.wo[2] * v_wo[2];
+        const float l = fmaxf(t.len, 1e-6f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o_mean[k] = -((v_wo[k] - t.wo[k] * dot) / l);
+    }
+    v_ks[0] = v_rough * (1.0f - min_roughness); v_ks[1] = v_metal * max_metallic;
 }
 
 // ---- lean backward of one pair (round 4, tail_shade_pairs_kernel) -------------------------------------------------------------------
@@ -341,8 +400,53 @@ __device__ __forceinline__ void cube_scatter_lds(float* lds, const CubeFp& fp, c
     }
 }
 
+// ---- texel-gradient scatter of one cube level, wave-wide -------------------------------------------------------------------------------
+// Commit flavours of env_scatter_wave: where a level WITHOUT an LDS copy goes (glob = the caller's buffer, priv_off = the level's float
+// offset in the XCD-private copies or -1) and which wave commit of gs_cube.h takes it there.
+struct CommitDevice {              // device-scope atomics into the caller's buffer
+    __device__ __forceinline__ void operator()(float* glob, long long, const CubeFp& fp, const float* v, float w, bool on, float* stage) const
+    { cube_scatter_wave<false>(on ? glob : nullptr, fp, v, w, on, stage); }
+};
+struct CommitTagged {              // per lane: this XCD's copy where `priv` (may be null) holds the level, else the caller's buffer
+    float* priv;
+    __device__ __forceinline__ void operator()(float* glob, long long priv_off, const CubeFp& fp, const float* v, float w, bool on, float* stage) const
+    {
+        const bool loc = on && priv != nullptr && priv_off >= 0;
+        cube_scatter_wave_tagged(on ? (loc ? priv + priv_off : glob) : nullptr, loc, fp, v, w, on, stage);
+    }
+};
+
+// All 64 lanes of the wave call together.  A lane adds w * v at the footprint fp of pyramid level l (base: of the diffuse base level,
+// l = 0), or takes part with nothing to add (l < 0; fp and v may then be anything).  The level's LDS copy takes it if it has one,
+// else the wave commit.
+template <class Commit>
+__device__ __forceinline__ void env_scatter_wave(const EnvGradDev& eg, float* s_grad, float* stage, const Commit& commit, bool base, int l,
+                                                 const CubeFp& fp, const float* v, float w)
+{
+    const bool on = l >= 0;
+    const int ls = on ? l : 0;
+    const int lds_off = base ? eg.lds_base : eg.lds_level[ls];
+    const bool in_lds = on && lds_off >= 0;
+    if (in_lds) cube_scatter_lds(s_grad + lds_off, fp, v, w);
+    commit(base ? eg.base : eg.levels[ls], base ? eg.priv_base : eg.priv_level[ls], fp, v, w, on && !in_lds, stage);
+}
+
+// ---- flush of the block's private LDS copies: one global atomic per non-zero float (after the __syncthreads() that ends the scatter)
+__device__ __forceinline__ void lds_flush_array(const float* s, float* dst, int cnt)
+{
+    for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+        const float v = s[i];
+        if (v != 0.0f) gs_atomic_add(dst + i, v);
+    }
+}
+__device__ __forceinline__ void env_lds_flush(const float* s_grad, const EnvGradDev& eg, const EnvDev& env)
+{
+    if (eg.lds_base >= 0) lds_flush_array(s_grad + eg.lds_base, eg.base, 18 * env.base_res * env.base_res);
+    for (int l = 0; l < env.L; ++l)
+        if (eg.lds_level[l] >= 0) lds_flush_array(s_grad + eg.lds_level[l], eg.levels[l], 18 * env.res[l] * env.res[l]);
+}
+
 #define GS_XCD_COPIES 8
-static size_t lds_bytes_of(int floats) { return (size_t)floats * sizeof(float); }
 static size_t shade_bwd_priv_floats(const EnvDev& e, int mode, long long* level_off, long long* base_off)
 {
     long long off = 0;
@@ -383,33 +487,56 @@ priv_reduce_kernel(long long n, int copies, const float* __restrict__ priv, long
     }
 }
 
-// LDS / launch layout of a kernel that scatters texel gradients (shade_bwd_kernel, tail_bwd_kernel): which levels get a private
-// LDS copy, where the wave staging lives, how many persistent blocks.  `eg` must already hold the caller's gradient pointers.
-struct ShadeBwdPlan { int block; size_t lds_bytes; int blocks; bool use_priv; size_t priv_floats; };
-static inline int shade_bwd_plan(const EnvDev& e, int mode, int N, void* ws, size_t ws_bytes, EnvGradDev& eg, ShadeBwdPlan& plan,
-                                 bool force_stage = false, int force_block = 0)
+#define GS_SHADE_BWD_BLOCK 512     // threads of shade_bwd_kernel / tail_bwd_kernel (history: 256 / 768 / 1024 measured)
+
+// The caller's texel-gradient pointers; the mode decides which of them it must supply.  `fn`: the entry point, for the message.
+static inline int env_grad_to_dev(const char* fn, const GsEnvGrad* env_grad, const EnvDev& e, int mode, EnvGradDev& eg)
 {
-    // LDS layout: privatise every level of at most maxres^2 texels per face (and the diffuse base) within 128 KB
-    const int s_block = force_block > 0 ? force_block : 512;       // (256 / 768 / 1024-thread blocks and other LDS cut-offs: measured)
-    const int s_maxres = 32;
-    const int lds_budget_floats = 128 * 1024 / 4;
-    int used = 0;
+    if (env_grad == nullptr) { gs_set_error("%s: env_grad must not be NULL", fn); return GS_EINVAL; }
+    eg.base = env_grad->base;
+    for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.levels[l] = l < e.L ? env_grad->levels[l] : nullptr;
+    if (mode == GS_MODE_DIFFUSE) {
+        if (eg.base == nullptr) { gs_set_error("%s: env_grad->base required in diffuse mode", fn); return GS_EINVAL; }
+    } else {
+        for (int l = 0; l < e.L; ++l)
+            if (eg.levels[l] == nullptr) { gs_set_error("%s: env_grad->levels[l] required", fn); return GS_EINVAL; }
+    }
+    return GS_OK;
+}
+
+// Private LDS copies behind `used` floats that are already taken: the base level (with_base) and / or the pyramid from its coarsest
+// level up (with_levels), each of at most 32^2 texels per face and while it fits 128 KB.  Returns the floats used.
+// (History: with only the 16^2 level in LDS the shading backward took 930-960 us against 389)
+static inline int env_lds_place(const EnvDev& e, bool with_base, bool with_levels, int used, EnvGradDev& eg)
+{
+    const int maxres = 32, budget_floats = 128 * 1024 / 4;
     eg.lds_base = -1;
     for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.lds_level[l] = -1;
-    if (mode == GS_MODE_DIFFUSE) {
-        const int cnt = 18 * e.base_res * e.base_res;
-        if (e.base_res <= s_maxres && used + cnt <= lds_budget_floats) { eg.lds_base = used; used += cnt; }
-    } else {
-        for (int l = e.L - 1; l >= 0; --l) {
-            const int cnt = 18 * e.res[l] * e.res[l];
-            if (e.res[l] <= s_maxres && used + cnt <= lds_budget_floats) { eg.lds_level[l] = used; used += cnt; }
-        }
+    if (with_base && e.base_res <= maxres && used + 18 * e.base_res * e.base_res <= budget_floats) {
+        eg.lds_base = used; used += 18 * e.base_res * e.base_res;
     }
+    for (int l = e.L - 1; with_levels && l >= 0; --l) {
+        const int cnt = 18 * e.res[l] * e.res[l];
+        if (e.res[l] <= maxres && used + cnt <= budget_floats) { eg.lds_level[l] = used; used += cnt; }
+    }
+    return used;
+}
+
+// ... and behind them the commit staging of the block's waves (640 floats each); returns the block's dynamic LDS in bytes
+static inline size_t env_lds_stage(int used, int block, EnvGradDev& eg)
+{
     eg.lds_floats = used;
-    const bool staged = true;
-    (void)force_stage;
-    eg.stage_off = staged ? ((used + 3) & ~3) : -1;
-    const int stage_floats = staged ? (eg.stage_off - used) + (s_block / 64) * 640 : 0;
+    eg.stage_off = (used + 3) & ~3;
+    return (size_t)(eg.stage_off + (block / 64) * 640) * sizeof(float);
+}
+
+// LDS / launch layout of a kernel that scatters texel gradients (shade_bwd_kernel, tail_bwd_kernel): which levels get a private
+// LDS copy, where the wave staging lives, how many persistent blocks.  s_block: the threads of a block.  `eg` must already hold the caller's gradient pointers.
+struct ShadeBwdPlan { int block; size_t lds_bytes; int blocks; bool use_priv; size_t priv_floats; };
+static inline int shade_bwd_plan(const EnvDev& e, int mode, int N, int s_block, void* ws, size_t ws_bytes, EnvGradDev& eg, ShadeBwdPlan& plan)
+{
+    const int used = env_lds_place(e, mode == GS_MODE_DIFFUSE, mode != GS_MODE_DIFFUSE, 0, eg);
+    plan.lds_bytes = env_lds_stage(used, s_block, eg);
     // XCD-private accumulators for the big levels (optional workspace)
     const size_t priv_floats = shade_bwd_priv_floats(e, mode, eg.priv_level, &eg.priv_base);
     const bool use_priv = ws != nullptr && priv_floats > 0;
@@ -417,7 +544,6 @@ static inline int shade_bwd_plan(const EnvDev& e, int mode, int N, void* ws, siz
     eg.priv = use_priv ? (float*)ws : nullptr;
     eg.priv_stride = (long long)priv_floats;
     plan.block = s_block;
-    plan.lds_bytes = (size_t)(used + stage_floats) * sizeof(float);
     int blocks = gs_cdiv(N > 0 ? N : 1, s_block);
     // persistent blocks when LDS copies have to be flushed at the end (one flush per block): as many as are resident at once
     const int per_cu = used > 0 ? (int)fmin(8.0, fmax(1.0, floor(160.0 * 1024.0 / (double)(plan.lds_bytes + 1024)))) : 8;
