@@ -496,6 +496,74 @@ def specular_subset_bwd(R, sel, bounds, v_out_rgb, roughness, costheta_cutoff):
     return g
 
 
+# ---- float64 restatement of S5 with per-element error budgets (gs_oracle_splitsum.c, second half) ----
+# Every function returns float64 values and budgets in units of 2^-24 (tests/util.assert_within_budget).  Several maps or
+# cotangents may be stacked along the channel axis ([6,R,R,3k]): the pair weights do not depend on the content.
+def _f64_out(shape):
+    return np.empty(shape, np.float64), np.empty(shape, np.float64)
+
+
+def specular_fwd_budget(cubemap, bounds, roughness, costheta_cutoff):
+    """Normalised specular level in float64 over the float32 pair set `bounds` / `costheta_cutoff` decide: returns
+    (val [6,R,R,C], budget [6,R,R,C], doubt [6,R,R] bool).  budget = sum w k |c - val| / W + 8 sum w |c| / W with
+    k = 8 + 6 / d + the pixel area's conditioning per pair (derivation: gs_oracle_splitsum.c); a pair whose float64 cosine
+    lies within 4 * 2^-24 of the cutoff adds its whole effect (both decisions admissible) and marks its output in `doubt`.
+    An empty lobe gives val = NaN (0 / 0, as in the float32 operator) with budget 0."""
+    cubemap, bounds = _f32(cubemap), _f32(bounds)
+    R, Cn = cubemap.shape[1], cubemap.shape[3]
+    assert cubemap.shape == (6, R, R, Cn) and bounds.shape == (6, R, R, 24)
+    val, bud = _f64_out((6, R, R, Cn)); doubt = np.empty((6, R, R), np.uint8)
+    lib().gso_specular_cubemap_fwd_budget(int(R), int(Cn), _p(cubemap), _p(bounds), _fl(roughness), _fl(costheta_cutoff),
+                                          _p(val), _p(bud), _p(doubt))
+    return val, bud, doubt.astype(bool)
+
+
+def specular_bwd_budget(bounds, v_level, roughness, costheta_cutoff):
+    """Gradient of the NORMALISED specular level w.r.t. its source map in float64, g_i = sum_o w(o,i) v_o / W_o (v_level = the
+    cotangent of the normalised level, as as_splitsum_backward takes it): returns (g, budget, doubt [6,R,R] bool).
+    budget = sum_o |v_o| w / W_o (k(o,i) + mean_o k + 8); pairs in doubt as in specular_fwd_budget.  A texel no cotangent
+    reaches has g = 0 and budget 0.  Outputs with an empty lobe are skipped (use configurations without them)."""
+    bounds, v = _f32(bounds), _f32(v_level)
+    R, Cn = v.shape[1], v.shape[3]
+    assert v.shape == (6, R, R, Cn) and bounds.shape == (6, R, R, 24)
+    g, bud = _f64_out((6, R, R, Cn)); doubt = np.empty((6, R, R), np.uint8)
+    lib().gso_specular_cubemap_bwd_budget(int(R), int(Cn), _p(bounds), _p(v), _fl(roughness), _fl(costheta_cutoff),
+                                          _p(g), _p(bud), _p(doubt))
+    return g, bud, doubt.astype(bool)
+
+
+def diffuse_budget(src, backward=False):
+    """Diffuse irradiance map (backward=False) or its adjoint applied to a cotangent (backward=True) in float64: (val, budget)."""
+    src = _f32(src)
+    R, Cn = src.shape[1], src.shape[3]
+    val, bud = _f64_out((6, R, R, Cn))
+    lib().gso_diffuse_cubemap_budget(int(R), int(Cn), _p(src), int(bool(backward)), _p(val), _p(bud))
+    return val, bud
+
+
+def cubemap_mip_fwd_budget(cubemap):
+    """2x2 average in float64: (val, budget) [6,R/2,R/2,C]"""
+    cubemap = _f32(cubemap)
+    R, Cn = cubemap.shape[1], cubemap.shape[3]
+    val, bud = _f64_out((6, R // 2, R // 2, Cn))
+    lib().gso_cubemap_mip_fwd_budget(int(R), int(Cn), _p(cubemap), _p(val), _p(bud))
+    return val, bud
+
+
+def cubemap_mip_bwd_budget(v_out, b_in=None):
+    """_CubeMapMip.backward in float64 (the seam-aware bilinear lookup of 0.25 * v_out, not the adjoint of the average):
+    (val, budget) [6,2R,2R,3].  v_out may be float64 (a gradient from specular_bwd_budget); b_in, its budget, is carried through
+    the lookup's non-negative weights -- how a whole pyramid's backward chains its budgets."""
+    v = np.ascontiguousarray(v_out, np.float64)
+    R = v.shape[1]
+    assert v.shape == (6, R, R, 3)
+    b = None if b_in is None else np.ascontiguousarray(b_in, np.float64)
+    assert b is None or b.shape == v.shape
+    val, bud = _f64_out((6, 2 * R, 2 * R, 3))
+    lib().gso_cubemap_mip_bwd_budget(int(R), _p(v), _p(b), _p(val), _p(bud))
+    return val, bud
+
+
 def splitsum_roughness(L, min_roughness=0.08, max_roughness=0.5):
     """per-level prefilter roughness (rfstudio/graphics/_mesh/_texture.py:545-548)"""
     return [(i / (L - 2)) * (max_roughness - min_roughness) + min_roughness for i in range(L - 1)] + [1.0]

@@ -1212,3 +1212,166 @@ def mesh_degenerate():
     verts = np.concatenate((octa, rest)).astype(np.float32)
     faces = np.array(of + [[6, 7, 8], [9, 10, 11], [12, 13, 14], [12, 15, 16]], np.int64)
     return verts, faces, np.arange(faces.shape[0]) < 8
+
+
+# ----------------------------------------------------------------------------- split-sum prefilter against the float64 error budget
+# tests/test_prefilter_budget_cpu.py, tests/test_gpu_prefilter_budget.py.  Two constants by the rule written beside PROJ_BUDGET_KAPPA:
+# the smallest power of two that is at least 4 x the larger of (a) the float32 oracle against the float64 restatement on the CPU
+# (bar kappa / 2) and (b) the kernels on an MI355X.  The measurements are in the docstring of tests/test_gpu_prefilter_budget.py.
+PREFILTER_SPEC_KAPPA = 16.0        # specular operator, forward and backward, direct and tiled: (a) 2.83, (b) 1.04
+PREFILTER_LIN_KAPPA = 4.0          # diffuse map and mip links: (a) 0.73, (b) 0.82
+PREFILTER_DOUBT_CAP = 0.05         # share of texels that may own a pair whose float64 cosine lies within 4 * 2^-24 of the cutoff
+PREFILTER_SCENES = ("flat", "sun", "dark")
+PREFILTER_COTANGENTS = ("dense", "sparse", "spiked")
+
+
+def _cube_dirs(R):
+    """float64 unit directions [6,R,R,3] of the texel centres"""
+    g = 2.0 * ((np.arange(R) + 0.5) / R) - 1.0
+    gy, gx = np.meshgrid(g, g, indexing="ij")
+    d = np.stack([cube_face_point(s, gx, gy) for s in range(6)])
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def prefilter_sun_texels(R):
+    """the five texels of the 'sun' scene as (face, y, x): a 2x2 block across the edge of faces 0 and 4 (columns x = 0 and x = R - 1
+    are neighbours there) in rows 1 and 2, next to the cube corner (1, 1, 1); and one lone texel inside face 3, last column of one
+    tile and first row of the next for every tile size up to R / 2"""
+    return [(0, 1, 0), (0, 2, 0), (4, 1, R - 1), (4, 2, R - 1), (3, R // 2, R // 2 - 1)]
+
+
+def prefilter_scene(kind, R, seed=0):
+    """A [6,R,R,3] float32 environment map: 'flat' (rand + 0.05: every texel of one size), 'sun' (flat with prefilter_sun_texels
+    scaled by 1e4: the largest element says nothing about a dark texel), 'dark' (flat with face 5 and the octant x < 0, y < 0,
+    z > 0 exactly 0: outputs whose whole lobe is zero must be exactly 0).  Random content: no reflection of the cube maps a scene
+    onto itself.  Each scene asserts its own property."""
+    c = (np.random.RandomState(900 + seed).rand(6, R, R, 3) + 0.05).astype(np.float32)
+    if kind == "sun":
+        for s, y, x in prefilter_sun_texels(R):
+            c[s, y, x] *= np.float32(1e4)
+        assert c.max() / np.median(c) >= 1e4 and (c > 100).any(-1).sum() == 5
+    elif kind == "dark":
+        d = _cube_dirs(R)
+        octant = (d[..., 0] < 0) & (d[..., 1] < 0) & (d[..., 2] > 0)
+        c[octant] = 0.0; c[5] = 0.0
+        zero = (c == 0).all(-1)
+        assert zero[5].all() and zero[octant].all() and 0.25 < zero.mean() < 0.35 and (c[~zero] >= 0.05).all()
+    else:
+        assert kind == "flat", kind
+        assert c.max() / c.min() < 25
+    for flip in (lambda a: a[:, :, ::-1], lambda a: a[:, ::-1], lambda a: a.transpose(0, 2, 1, 3)):
+        assert not np.array_equal(flip(c), c)
+    return c
+
+
+def prefilter_sparse_texels(R):
+    """the non-zero texels of the 'sparse' cotangent: three face corners, both sides of a tile boundary in x and in y, both sides of
+    the seam of faces 0 and 4, one interior texel"""
+    h = R // 2
+    return [(0, 0, 0), (1, R - 1, R - 1), (2, 0, R - 1), (4, 5, h - 1), (4, 5, h), (5, h - 1, 3), (5, h, 3), (0, 3, 0), (4, 3, R - 1),
+            (3, 2, R - 3)]
+
+
+def prefilter_cotangent(kind, R, seed=0):
+    """A [6,R,R,3] float32 cotangent: 'dense' (rand - 0.5), 'sparse' (dense on prefilter_sparse_texels only: most gradients then
+    have budget 0 and must be exactly 0), 'spiked' (dense with three texels scaled by 1e4)"""
+    v = (np.random.RandomState(950 + seed).rand(6, R, R, 3) - 0.5).astype(np.float32)
+    if kind == "sparse":
+        keep = np.zeros((6, R, R), bool)
+        for s, y, x in prefilter_sparse_texels(R):
+            keep[s, y, x] = True
+        v[~keep] = 0.0
+        assert (v != 0).any(-1).sum() == 10
+    elif kind == "spiked":
+        for s, y, x in ((1, 2, R - 2), (2, R // 2, R // 2), (5, R - 1, 0)):
+            v[s, y, x] *= np.float32(1e4)
+        assert np.abs(v).max() / np.median(np.abs(v)) >= 1e4
+    else:
+        assert kind == "dense", kind
+    return v
+
+
+def assert_prefilter_budget(name, got, want, budget, kappa, nan_expected=False):
+    """assert_within_budget for a prefiltered level: texels the reference leaves NaN (an empty lobe: 0 / 0) must be NaN in `got`
+    too and are then left out; none may appear unless the configuration is known to have them.  Returns the worst ratio."""
+    got = np.asarray(got, np.float64); want = np.asarray(want, np.float64); budget = np.asarray(budget, np.float64)
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), (name, int(np.isnan(got).sum()), int(nan.sum()))
+    assert nan_expected or not nan.any(), (name, int(nan.sum()))
+    keep = ~nan
+    return assert_within_budget(name, got[keep], want[keep], budget[keep], kappa)
+
+
+_prefilter_refs = {}
+_prefilter_boxes = {}
+
+
+def prefilter_bounds(R, roughness):
+    """(cutoff cosine, the oracle's float32 lobe boxes [6,R,R,24]) of a level, computed once"""
+    import oracle
+    key = (int(R), float(roughness))
+    if key not in _prefilter_boxes:
+        ct = oracle.ndf_cutoff(roughness)
+        _prefilter_boxes[key] = (ct, oracle.specular_bounds(R, ct))
+    return _prefilter_boxes[key]
+
+
+def prefilter_reference(R, roughness):
+    """The float64 reference of one specular level, computed once per (R, roughness) and shared (never modified) by the CPU and
+    GPU budget tests: dict(ct, bounds, fwd={scene: (val, budget)}, fwd_doubt, bwd={cotangent: (g, budget)}, bwd_doubt,
+    has_nan).  The backward is left out where a lobe is empty (0 / 0 in the reference and in the kernels)."""
+    import oracle
+    key = (int(R), float(roughness))
+    if key not in _prefilter_refs:
+        ct, bounds = prefilter_bounds(R, roughness)
+        maps = np.concatenate([prefilter_scene(k, R) for k in PREFILTER_SCENES], -1)
+        val, bud, doubt = oracle.specular_fwd_budget(maps, bounds, roughness, ct)
+        ref = dict(ct=ct, bounds=bounds, fwd_doubt=doubt, has_nan=bool(np.isnan(val).any()),
+                   fwd={k: (val[..., 3 * j:3 * j + 3], bud[..., 3 * j:3 * j + 3]) for j, k in enumerate(PREFILTER_SCENES)})
+        if not ref["has_nan"]:
+            cots = np.concatenate([prefilter_cotangent(k, R) for k in PREFILTER_COTANGENTS], -1)
+            g, gb, gd = oracle.specular_bwd_budget(bounds, cots, roughness, ct)
+            ref["bwd"] = {k: (g[..., 3 * j:3 * j + 3], gb[..., 3 * j:3 * j + 3]) for j, k in enumerate(PREFILTER_COTANGENTS)}
+            ref["bwd_doubt"] = gd
+        _prefilter_refs[key] = ref
+    return _prefilter_refs[key]
+
+
+def prefilter_pyramid_roughness(n_levels, min_roughness=0.08, max_roughness=0.5):
+    return [(i / (n_levels - 2)) * (max_roughness - min_roughness) + min_roughness for i in range(n_levels - 1)] + [1.0]
+
+
+def prefilter_pyramid_forward_reference(mips):
+    """float64 reference of a pyramid's forward, CUT LOOSE per stage: `mips` are the float32 maps the implementation under test
+    itself produced ([map, mip 1, ...]); every stage is judged on the inputs it really read, so no error is carried from one
+    stage to the next.  Returns (mip_refs [(val, budget) for mips[1:]], base (val, budget), levels [(val, budget)])."""
+    import oracle
+    roughs = prefilter_pyramid_roughness(len(mips))
+    mip_refs = [oracle.cubemap_mip_fwd_budget(m) for m in mips[:-1]]
+    base = oracle.diffuse_budget(mips[-1])
+    levels = []
+    for m, r in zip(mips, roughs):
+        ct, bounds = prefilter_bounds(m.shape[1], r)
+        levels.append(oracle.specular_fwd_budget(m, bounds, r, ct)[:2])
+    return mip_refs, base, levels
+
+
+def prefilter_pyramid_backward_reference(v_base, v_levels):
+    """float64 reference of a pyramid's backward, with the budgets PROPAGATED (the implementation does not expose the gradients
+    of the mips): the last level's gradient is specular + diffuse, every other one specular + the mip link of the level below,
+    whose budget is carried through the link's non-negative weights; each accumulation adds one rounding of the sum.
+    Returns (g, budget) of the map."""
+    import oracle
+    roughs = prefilter_pyramid_roughness(len(v_levels))
+    parts = []
+    for v, r in zip(v_levels, roughs):
+        ct, bounds = prefilter_bounds(v.shape[1], r)
+        parts.append(oracle.specular_bwd_budget(bounds, v, r, ct)[:2])
+    d, db = oracle.diffuse_budget(v_base, backward=True)
+    g = parts[-1][0] + d
+    b = parts[-1][1] + db + np.abs(g)
+    for i in range(len(v_levels) - 1, 0, -1):
+        m, mb = oracle.cubemap_mip_bwd_budget(g, b)
+        g = parts[i - 1][0] + m
+        b = parts[i - 1][1] + mb + np.abs(g)
+    return g, b
