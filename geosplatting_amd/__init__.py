@@ -43,10 +43,15 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == optix_env_shade, TextureLatLng.compute_pdf_ and RenderableAttrs.splat_mc without the denoiser
                                              (rfstudio/graphics/_mesh/_optix/ops.py, _texture.py:287-305, rfstudio/model/geosplat.py:134-244):
                                              Monte-Carlo shading of a lat-long light with MIS and inline shadow rays on a MeshBVH
+  denoise.bilateral_denoiser, RenderableAttrs.splat_mc_deferred
+                                          == bilateral_denoiser (rfstudio/graphics/_mesh/_optix/ops.py:107-140, c_src/denoising.cu) with
+                                             1..8 channels, and RenderableAttrs.splat_mc_deferred (rfstudio/model/geosplat.py:247-376):
+                                             the 14-channel G-buffer, per-pixel env_shade, the filter, the residual light
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
 from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, sphere_cameras, view_matrix  # noqa: F401
+from .denoise import bilateral_denoiser, filter_radius  # noqa: F401
 from .envshade import LatLngEnvMap, env_shade, make_perms  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401

@@ -68,6 +68,7 @@ SYMBOLS = [
     "gs_tex2d_fwd", "gs_tex2d_bwd", "gs_meshshade_fwd", "gs_meshshade_bwd",
     "gs_bvh_bytes", "gs_bvh_ws_bytes", "gs_bvh_build", "gs_ray_occluded", "gs_ray_closest",
     "gs_envshade_fwd", "gs_envshade_bwd",
+    "gs_denoise_tiled_fits", "gs_denoise_fwd", "gs_denoise_bwd",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -168,6 +169,9 @@ def lib() -> C.CDLL:
                     C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
         l.gs_envshade_fwd.argtypes = env_head + [C.c_void_p] * 7
         l.gs_envshade_bwd.argtypes = env_head + [C.c_int] + [C.c_void_p] * 8
+        l.gs_denoise_tiled_fits.argtypes = [C.c_int, C.c_double]
+        l.gs_denoise_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_double, C.c_int] + [C.c_void_p] * 3
+        l.gs_denoise_bwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_double, C.c_int] + [C.c_void_p] * 4
         _lib = l
     return _lib
 

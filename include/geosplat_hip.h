@@ -1046,6 +1046,30 @@ int gs_envshade_bwd(int64_t P, const float* mask, const float* ro, const float* 
                     int merge_rounds, const float* diff_grad, const float* spec_grad, float* gb_pos_grad, float* gb_normal_grad,
                     float* gb_kd_grad, float* gb_ks_grad, float* light_grad, void* stream);
 
+/* ------------------------------------------------------------------ bilateral denoiser of the Monte-Carlo estimates ------------- */
+/* What the reference's stages 2 and 3 get from bilateral_denoiser (rfstudio/graphics/_mesh/_optix: ops.py:107-140,
+ * c_src/denoising.cu); a restatement of the semantics.  csrc/gs_denoise.hip; tests/denoise_ref.py states the same in float64.
+ *
+ * col [B,H,W,C] with 1 <= C <= 8 (the reference: 3), nrm [B,H,W,3], zdz [B,H,W,zdz_channels] with 1 or 2 channels: z = channel 0, dz = the
+ *   last channel (one channel: dz = z), all fp32.  R = 2 ceil(2.5 sigma) + 1 <= 127 and v = sigma^2, sigma a finite positive double.
+ * For a centre p and every tap q = p + (fx, fy), |fx|, |fy| <= R, inside the image, fy outer and fx inner:
+ *   w = exp(-(fx^2 + fy^2) / (2 v)) * clamp(nrm[q] . nrm[p], 1e-4, 1)^128 * exp(-|z[q] - z[p]| / max(dz[p] sqrt(fx^2 + fy^2), 1e-4))
+ * gs_denoise_fwd  wsum[p] = max(sum_q w, 1e-4) and out[p] = sum_q w col[q] / wsum[p] -- the reference's four-channel output and the
+ *   division its wrapper applies.  out [B,H,W,C] and wsum [B,H,W] are overwritten.
+ * gs_denoise_bwd  col_grad[p] = sum_q w(q<-p) out_grad[q] / wsum[q], with w(q<-p) the weight q gave the tap p: the forward's weight
+ *   with dz[q] in the depth denominator.  The gradient reaches col only.  col_grad [B,H,W,C] is overwritten.
+ * Both are gathers without atomics: the same inputs give the same bits, a C-channel call gives the bits of calls on its channel slices,
+ *   and the two forms agree bit for bit.  tiled: 1 stages the window halo in LDS (GS_EINVAL when it does not fit), 0 reads the taps
+ *   from global memory, -1 picks (the tiled form where gs_denoise_tiled_fits, except for H < 8).  gs_denoise_tiled_fits is 1 when the
+ *   halo of this C and sigma fits, for both directions alike; it touches no device.
+ * Both return GS_EINVAL before touching the device for B, H or W below 1, C outside 1..8, zdz_channels not 1 or 2, sigma not finite and
+ *   positive or with R > 127, B or H / 8 above 65535, an unknown form, or a null pointer. */
+int gs_denoise_tiled_fits(int C, double sigma);
+int gs_denoise_fwd(int B, int H, int W, int C, int zdz_channels, const float* col, const float* nrm, const float* zdz, double sigma,
+                   int tiled, float* out, float* wsum, void* stream);
+int gs_denoise_bwd(int B, int H, int W, int C, int zdz_channels, const float* nrm, const float* zdz, double sigma, int tiled,
+                   const float* wsum, const float* out_grad, float* col_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
