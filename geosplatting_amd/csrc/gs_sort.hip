@@ -3,10 +3,15 @@
 // (tile_id << 32) | float_bits(depth), payload = packed Gaussian index, stable ascending radix sort, so that equal keys
 // keep their emission order (= ascending packed index); that order fixes the composited order bit-exactly.
 //
-// Two entry points, both on the radix machinery below (no vendor sort library on the path):
+// Three entry points (no vendor sort library on any path):
+//   gs_isect_bin_front : what the engine uses.  The front kernel has counted the intersections per tile, so every tile's segment of
+//                   the output is known before anything is sorted: the intersections are scattered, in packed order, straight into
+//                   their tile's segment, and one workgroup per tile sorts its segment on chip by (depth key, packed index) -- a
+//                   bitonic network in LDS (gs_segsort_dev.h), no pass over the whole list.  See the block above the function.
+//                   Without the per-tile counts (more than 8 192 tiles) it falls back to the radix machinery below.
 //   gs_isect_sort : the upstream call shape -- sorts already emitted (isect_ids, flatten_ids) pairs, six 8-bit passes
 //                   over the 32 + tile_bits significant key bits (kept for callers that hold emitted keys);
-//   gs_isect_bin  : what rasterization() and the engine use.  The 44-bit key of an intersection is (tile, depth of
+//   gs_isect_bin  : what rasterization() uses.  The 44-bit key of an intersection is (tile, depth of
 //                   its Gaussian): the depth half is a property of the V Gaussians, not of the I = 2.1 V intersections,
 //                   so it is sorted ONCE on the Gaussians (4 passes over 8-byte (depth, index) items, V-sized), the
 //                   intersections are then EMITTED in depth order as 8-byte (tile, index) items, and two stable passes
@@ -20,6 +25,7 @@
 // per digit bit, the rank inside the wave is a popcount, and one lane per digit group advances the wave's running
 // counter in LDS -- no sorting network, no atomics.
 #include "gs_common.h"
+#include "gs_segsort_dev.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -397,36 +403,31 @@ extern "C" int gs_isect_bin_tiles_cap(int V_cap, const float* means2d, const int
                           nullptr, flatten_ids_sorted, ws, ws_bytes, stream, tile_ids_sorted);
 }
 
-// ---- gs_isect_bin_front: binning of the engine's fused front (round 4) ---------------------------------------------------------
+// ---- gs_isect_bin_front: binning of the engine's fused front ---------------------------------------------------------------------
 // Same result as gs_isect_bin_tiles_cap + gs_isect_offsets_tiles_cap -- `flatten_ids` in (tile, depth bits, packed index) order and the
-// per-tile offsets, bit for bit -- from what gs_front_fwd leaves behind, with fewer and smaller passes:
-//   * the depth key is 24 bits wide when the engine knows the view's depth range (key = depth bits - key_base, checked by the front
-//     kernel): THREE V-sized passes instead of four;
-//   * the tile rectangles come packed from the front kernel (no tile_rect_kernel);
-//   * the emission finds its own write positions with an in-launch chained scan over its blocks (ticket order, 8-byte {flag, value}
-//     granules as in project_fwd_kernel): no block-sum pass, no scan launch;
-//   * the front kernel has already counted the intersections per TILE (LDS histogram per block of 512 index-adjacent Gaussians): the
-//     tile offsets are the exclusive scan of those 2 500 counters, clamped to the capacity -- no I-sized offsets pass, and the last
-//     tile pass writes 4 bytes per intersection (flatten id) instead of 8.  (More than 8 192 tiles: the tile ids are kept and the
-//     offsets come from them.)
-// 18 launches (setup, 3 x 3 depth passes, emission, offset scan, 2 x 3 tile passes) against 25.
-// Round 6, built, bit-identical, measured and removed (`git show 3d98652:geosplatting_amd/csrc/gs_sort.hip`): every pass as ONE kernel
-// -- ticketed blocks publish {flag | count} rows, offsets from a two-level look-back over <= 31 block rows + the group totals, items held
-// in registers meanwhile, global digit histograms from one read of the keys / from the tile counters, the tile rectangle carried through
-// the depth passes as 12-byte items so that the emission reads in order (48 instead of 84 us) -- 9 launches instead of 18.  A fused pass
-// took 36 us (depth) / 53 us (tiles) alone against 8 + 6 + 16 / 8 + 6 + 18 for the three kernels it replaces: with every block resident
-// and publishing at the same moment the look-back is ~10 dependent global round trips, where a kernel boundary costs 1.5 us; 281 against
-// 252 us per view alone, 640 against 649 views/s inside the step (608 with 32 loads in flight and 21 KB blocks).
+// per-tile offsets, bit for bit -- from what gs_front_fwd leaves behind: depth keys (24 bits wide when the engine knows the view's
+// depth range, key = depth bits - key_base, checked by the front kernel), packed tile rectangles, and the intersections counted per TILE.
+//
+// Tile first (tile_counts given, <= BF_HIST_MAX tiles: the engine's path).  The counters fix every tile's segment of the output before
+// anything is sorted, so no pass over the whole list is needed:
+//   setup    bin_setup_kernel           clears the per-tile cursors and the class counters; capacity check
+//   offsets  tile_offsets_scan_kernel   exclusive scan of the counters, clamped to the capacity; files the tiles by segment length
+//   scatter  bin_scatter_kernel         packed slots in order -> {key, slot} items into their tile's segment, any order inside it
+//   sort     seg_sort_kernel x 4        one workgroup per tile sorts its segment by (key, slot) on chip and writes the slots
+// 7 launches, I * 8 bytes of scratch.  The items are written once and read once (about 27 MB each way for the bench view's 3.4 M
+// intersections, next to 24 MB of keys and rectangles in and 14 MB of ids out); the radix path moved ~0.6 GB for the same list.  No
+// kernel waits for another workgroup, every clear is a kernel, nothing is read back: capturable as it stands.
+//
+// Radix (no tile_counts, or more tiles than a block's LDS holds): key_bits / 8 V-sized depth passes, the emission in depth order with
+// its in-launch chained scan, two or three stable passes over the tile bits that keep the tile ids, and the offsets from those.
+// Round 6, built, bit-identical, measured and removed (`git show 3d98652:geosplatting_amd/csrc/gs_sort.hip`): every radix pass as ONE
+// kernel -- ticketed blocks publish {flag | count} rows, offsets from a two-level look-back -- 9 launches instead of 18, 281 against
+// 252 us per view alone, 640 against 649 views/s inside the step: the look-back cost more than the kernel boundaries it removed.
 struct KeyIn {                                                     // (depth key, packed index) straight from the key array
     const unsigned* keys;
     __device__ __forceinline__ uint2 load(int64_t i) const { return make_uint2(keys[i], (unsigned)i); }
 };
-struct FinalFlat {
-    int32_t* flatten_ids;
-    __device__ __forceinline__ void store(int64_t i, const uint2& it) const { flatten_ids[i] = (int32_t)it.y; }
-};
-
-#define BF_HIST_MAX 8192                     // tiles whose counters fit a block's LDS histogram (32 KB)
+#define BF_HIST_MAX 8192                     // tiles whose counters fit a block's LDS (32 KB): the front kernel's histogram, the scatter's cursors
 
 __global__ void __launch_bounds__(256)
 bin_setup_kernel(unsigned* __restrict__ state, int n_state_words,
@@ -548,15 +549,52 @@ emit_chained_kernel(GsCount vc, const uint2* __restrict__ order, const uint2* __
     }
 }
 
+// ---- tile-first binning (the engine's path up to BF_HIST_MAX tiles) ----------------------------------------------------------------
+// LDS classes of the segment sort: a segment of up to SEG_CAP<c> items is sorted in the LDS of one workgroup (class 0 -- seven in ten of
+// the bench scene's segments -- in 16.9 KB, under the 22.5 KB RS_ITEMS was tuned to); longer segments are sorted in place in the item
+// buffer by one workgroup each (class SEG_CLASSES, "general": any length up to I).  The capacities are powers of two: the LDS then
+// holds the whole padded network and no index of it is ever checked (gs_segsort_dev.h).  A thread holds 2^SEG_GMAX items.
+#define SEG_CLASSES 3
+#define SEG_CAP0 2048
+#define SEG_CAP1 4096
+#define SEG_CAP2 16384
+#define SEG_GMAX 4                           // (8 items per thread: +7 % on the three sort launches, 32: +25 %, 164 VGPRs)
+#define SEG_THREADS(cap) ((cap) >> SEG_GMAX > 1024 ? 1024 : ((cap) >> SEG_GMAX))
+#define SEG_BINS 64                          // half-octave length bins per class (lengths < 2^31: 62 used)
+static size_t seg_lds_bytes(int cap) { return (size_t)(cap + (cap >> 5) + 1) * sizeof(u64); }
+
+extern "C" int gs_isect_bin_front_classes(int* caps, int max)
+{
+    const int c[SEG_CLASSES] = { SEG_CAP0, SEG_CAP1, SEG_CAP2 };
+    for (int i = 0; i < SEG_CLASSES && i < max; ++i) if (caps) caps[i] = c[i];
+    return SEG_CLASSES;
+}
+
+// Work lists of the segment sort, filled by the offsets scan: lists[c * n_tiles ..] = the non-empty tiles of class c, longest first to
+// the half octave (struct BwdOrder of gs_raster.hip files the backward's tiles the same way), count[c] = how many.
+struct SegLists { unsigned* count; int32_t* lists; };
+
+__device__ __forceinline__ int seg_class(unsigned len) { return len <= SEG_CAP0 ? 0 : (len <= SEG_CAP1 ? 1 : (len <= SEG_CAP2 ? 2 : 3)); }
+__device__ __forceinline__ int seg_bin(unsigned len)                 // len >= 1: 2 * floor(log2) + the next bit, reversed (longest first)
+{
+    const int l2 = 31 - __clz((int)len);
+    const int half = l2 > 0 ? (int)((len >> (l2 - 1)) & 1u) : 0;
+    return SEG_BINS - 1 - (2 * l2 + half);
+}
+
 // offsets[t] = min(exclusive prefix of the tile counts, n) by one workgroup: the tile offsets of a view.  (The clamp only ever acts
-// on a view that overflowed its capacity: its list is truncated in emission order, the offsets then are not those of the truncated
-// list -- memory-safe, wrong image, reported, as the capacity protocol says.)
+// on a view that overflowed its capacity: its list is truncated, the offsets then are not those of the truncated
+// list -- memory-safe, wrong image, reported, as the capacity protocol says.)  With `sl` the same workgroup files every non-empty tile
+// by the length of its (clamped) segment: the lengths of a class sum to <= n, which bounds the grid of that class on the host.
 __global__ void __launch_bounds__(1024)
-tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, GsCount nc, int32_t* __restrict__ offsets)
+tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, GsCount nc, int32_t* __restrict__ offsets, SegLists sl)
 {
     __shared__ unsigned wsum[16];
+    __shared__ unsigned s_bin[(SEG_CLASSES + 1) * SEG_BINS];
     const unsigned n = (unsigned)gs_count(nc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (sl.count && threadIdx.x < (SEG_CLASSES + 1) * SEG_BINS) s_bin[threadIdx.x] = 0u;
+    __syncthreads();
     unsigned carry = 0u;
     for (int i0 = 0; i0 < n_tiles; i0 += 1024) {
         const int i = i0 + threadIdx.x;
@@ -567,9 +605,138 @@ tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, 
         __syncthreads();
         unsigned before = 0u, all = 0u;
         for (int w = 0; w < 16; ++w) { if (w < wave) before += wsum[w]; all += wsum[w]; }
-        if (i < n_tiles) { const unsigned o = carry + before + incl - v; offsets[i] = (int32_t)(o < n ? o : n); }
+        if (i < n_tiles) {
+            const unsigned o = carry + before + incl - v;
+            const unsigned beg = o < n ? o : n, end = o + v < n ? o + v : n;
+            offsets[i] = (int32_t)beg;
+            if (sl.count && end > beg) atomicAdd(&s_bin[seg_class(end - beg) * SEG_BINS + seg_bin(end - beg)], 1u);
+        }
         carry += all;
         __syncthreads();
+    }
+    if (!sl.count) return;
+    // wave c scans the bins of class c (64 bins = one wave): start of every bin inside the class list, and the class total
+    if (wave <= SEG_CLASSES) {
+        const unsigned v = s_bin[wave * SEG_BINS + lane];
+        const unsigned incl = gs_wave_incl_scan(v);
+        s_bin[wave * SEG_BINS + lane] = incl - v;
+        if (lane == 63) sl.count[wave] = incl;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_tiles; i += 1024) {                      // (offsets[] of this workgroup's own stores: same thread, same index)
+        const unsigned beg = (unsigned)offsets[i];
+        unsigned end = n;
+        if (i + 1 < n_tiles) end = (unsigned)__hip_atomic_load(&offsets[i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (end > beg) {
+            const int c = seg_class(end - beg);
+            const unsigned pos = atomicAdd(&s_bin[c * SEG_BINS + seg_bin(end - beg)], 1u);
+            sl.lists[(size_t)c * n_tiles + pos] = i;
+        }
+    }
+}
+
+#define SC_THREADS 512
+#define SC_PER 8                             // packed slots per thread
+#define SC_TILE (SC_THREADS * SC_PER)
+
+// Scatter in slot order: a block owns SC_TILE consecutive packed slots, reads their keys and rectangles coalesced, counts its items per
+// tile in LDS, reserves a range on every touched tile's cursor with ONE returning atomic, and ranks its items inside the range with LDS
+// atomics -- the same LDS word first counts, then holds the next free position of the tile.  An item is the 64-bit composite the segment
+// sort orders by: key << 31 | slot (slot < 2^31), with bit 62 set for 24-bit keys (item_bias: every item is then the bit pattern of a
+// normal positive double, see gs_seg_cx).  The order inside a segment is arbitrary.  Nobody waits for anybody.
+// The kernel's time follows the number of (block, touched tile) reservations, not the bytes: alone on the bench view 256 x 4 slots take
+// 89 us, 256 x 8 81, 256 x 16 60, 512 x 8 50, 1024 x 8 46 (there too: scanning only the touched range of tile ids,
+// and handing neighbouring chunks to one XCD, which both cost more than they saved).
+__global__ void __launch_bounds__(SC_THREADS)
+bin_scatter_kernel(GsCount vc, const unsigned* __restrict__ keys, const uint2* __restrict__ rects, unsigned key_mask, u64 item_bias, int tile_w, int tile_h,
+                   const int32_t* __restrict__ offsets, unsigned* __restrict__ cursor, u64* __restrict__ items, unsigned item_cap)
+{
+    extern __shared__ unsigned s_pos[];                          // [n_tiles]
+    const int V = (int)gs_count(vc);
+    const int n_tiles = tile_w * tile_h;
+    const int s0 = (int)blockIdx.x * SC_TILE + (int)threadIdx.x;
+    if ((long long)blockIdx.x * SC_TILE >= V) return;
+    for (int t = threadIdx.x; t < n_tiles; t += SC_THREADS) s_pos[t] = 0u;
+    unsigned key[SC_PER]; uint2 q[SC_PER];
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {
+        const int v = s0 + k * SC_THREADS;
+        const int vv = v < V ? v : V - 1;                        // (a load under a branch would drain the loads in flight)
+        key[k] = keys[vv];
+        q[k] = rects[vv];
+        if (v >= V) q[k] = make_uint2(0u, 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {                           // rectangles clipped to the grid once: nothing below indexes outside s_pos
+        int x1 = (int)(q[k].y & 0xffffu), y1 = (int)(q[k].y >> 16);
+        x1 = x1 < tile_w ? x1 : tile_w; y1 = y1 < tile_h ? y1 : tile_h;
+        q[k].y = (unsigned)x1 | ((unsigned)y1 << 16);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {
+        const int x0 = (int)(q[k].x & 0xffffu), y0 = (int)(q[k].x >> 16), x1 = (int)(q[k].y & 0xffffu), y1 = (int)(q[k].y >> 16);
+        for (int i = y0; i < y1; ++i)
+            for (int j = x0; j < x1; ++j) atomicAdd(&s_pos[i * tile_w + j], 1u);
+    }
+    __syncthreads();
+    for (int t0 = threadIdx.x; t0 < n_tiles; t0 += 4 * SC_THREADS) {       // four reservations in flight per thread
+        unsigned c[4], o[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = t0 + u * SC_THREADS;
+            c[u] = t < n_tiles ? s_pos[t] : 0u;
+            o[u] = c[u] ? (unsigned)offsets[t] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) b[u] = c[u] ? atomicAdd(&cursor[t0 + u * SC_THREADS], c[u]) : 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (c[u]) s_pos[t0 + u * SC_THREADS] = o[u] + b[u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {
+        const int x0 = (int)(q[k].x & 0xffffu), y0 = (int)(q[k].x >> 16), x1 = (int)(q[k].y & 0xffffu), y1 = (int)(q[k].y >> 16);
+        const u64 item = item_bias | ((u64)(key[k] & key_mask) << 31) | (u64)(unsigned)(s0 + k * SC_THREADS);
+        for (int i = y0; i < y1; ++i)
+            for (int j = x0; j < x1; ++j) {
+                const unsigned pos = atomicAdd(&s_pos[i * tile_w + j], 1u);
+                if (pos < item_cap) items[pos] = item;           // (capacity protocol: an overflowing view is reported, not written)
+            }
+    }
+}
+
+// Segment sort: workgroup b of a class sorts the segment of tile lists[b] by its items (key, then slot) -- the order of the stable radix sort,
+// ties included, whatever order the scatter left -- and writes the slots.  LDS classes load the segment once, pad it to its power of two
+// and sort it there; the general class runs the same network, guarded, in place on its own range of the item buffer (one CU: its
+// stores and loads meet in that CU's cache, a workgroup barrier orders them).  A slot is clamped to the view's count: after an overflow
+// the tail of the item buffer was never written, and the ids must stay valid rows for whoever gathers by them.
+template <int THREADS, bool GLOBAL, bool F64>
+__global__ void __launch_bounds__(THREADS)
+seg_sort_kernel(const int32_t* __restrict__ list, const unsigned* __restrict__ list_count, int n_tiles, const int32_t* __restrict__ offsets,
+                GsCount ic, GsCount vc, u64* items, int32_t* __restrict__ flat)
+{
+    extern __shared__ u64 s_seg[];
+    if (blockIdx.x >= *list_count) return;
+    const int t = list[blockIdx.x];
+    const int n_all = (int)gs_count(ic);
+    const int beg = offsets[t], end = t + 1 < n_tiles ? offsets[t + 1] : n_all;
+    const int n = end - beg;
+    if (n <= 0) return;
+    const long long V = gs_count(vc);
+    const unsigned vmax = V > 0 ? (unsigned)(V - 1) : 0u;
+    const int tid = threadIdx.x;
+    int P = 1 << SEG_GMAX;
+    while (P < n) P <<= 1;
+    u64* buf = GLOBAL ? items + beg : s_seg;
+    if (!GLOBAL) {
+        for (int i = tid; i < P; i += THREADS) s_seg[gs_seg_phys<true>(i)] = i < n ? items[beg + i] : gs_seg_inf<F64>();
+        __syncthreads();
+    }
+    GS_SEG_SORT_BODY(SEG_GMAX, !GLOBAL, F64, GLOBAL, buf, n, P, tid, THREADS, __syncthreads());
+    for (int i = tid; i < n; i += THREADS) {
+        const unsigned slot = (unsigned)buf[gs_seg_phys<!GLOBAL>(i)] & 0x7fffffffu;
+        flat[beg + i] = (int32_t)(slot < vmax ? slot : vmax);
     }
 }
 
@@ -594,11 +761,71 @@ bin_offsets_tiles_kernel(GsCount nc, const int32_t* __restrict__ tiles, int n_ti
 }
 
 
+// scratch of the two paths.  Tile first: the per-tile cursors + the class counters, the class lists, the items.
+static size_t tf_state_words(int n_tiles) { return (size_t)n_tiles + SEG_CLASSES + 1; }
+static size_t tf_ws_bytes(int64_t n_isects, int n_tiles)
+{
+    return align256(tf_state_words(n_tiles) * 4) + align256((size_t)(SEG_CLASSES + 1) * n_tiles * 4) + align256((size_t)n_isects * 8) + 256;
+}
+static size_t bf_radix_ws_bytes(size_t v, size_t n)
+{
+    return table_bytes((int64_t)(v > n ? v : n)) + 2 * align256(v * 8) + 2 * align256(n * 8) + bf_state_bytes((int)v) + align256(n * 4) + 256;
+}
+
+// What gs_isect_bin_front needs for these sizes when it is given tile_counts (it always needs that much; a caller that passes no
+// tile_counts for a grid of <= BF_HIST_MAX tiles takes the radix path and is told if its scratch is too small for it).
 extern "C" size_t gs_isect_bin_front_ws_bytes(int V, int64_t n_isects, int tile_w, int tile_h)
 {
     const size_t v = V > 0 ? (size_t)V : 1, n = n_isects > 0 ? (size_t)n_isects : 1;
-    const size_t tb = table_bytes((int64_t)(v > n ? v : n));
-    return tb + 2 * align256(v * 8) + 2 * align256(n * 8) + bf_state_bytes((int)v) + align256(n * 4) + 256;   // (tile ids: only without tile_counts)
+    const int64_t n_tiles = (int64_t)tile_w * tile_h;
+    if (n_tiles > 0 && n_tiles <= BF_HIST_MAX) return tf_ws_bytes((int64_t)n, (int)n_tiles);
+    return bf_radix_ws_bytes(v, n);
+}
+
+static int bin_front_tile_first(int V, const uint32_t* depth_keys, const uint32_t* tile_rects, const uint32_t* tile_counts,
+                                const int64_t* counts_dev, int64_t n_isects, int key_bits, int tile_w, int tile_h, int32_t* flatten_ids_sorted,
+                                int32_t* isect_offsets, void* ws, int64_t* status_dev, hipStream_t s)
+{
+    const int n_tiles = tile_w * tile_h;
+    const GsCount vc{ (long long)V, (const long long*)counts_dev }, ic{ (long long)n_isects, counts_dev ? (const long long*)counts_dev + 1 : nullptr };
+    char* p = (char*)ws;
+    unsigned* cursor = (unsigned*)p;                                        // [n_tiles], then the class counters
+    unsigned* class_count = cursor + n_tiles; p += align256(tf_state_words(n_tiles) * 4);
+    int32_t* lists = (int32_t*)p; p += align256((size_t)(SEG_CLASSES + 1) * n_tiles * 4);
+    u64* items = (u64*)p;
+    const int n_state_words = (int)tf_state_words(n_tiles);
+    hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(n_state_words, 256) < 64 ? gs_cdiv(n_state_words, 256) : 64), dim3(256), 0, s, cursor,
+                       n_state_words, (const long long*)counts_dev, (long long)V, (long long)n_isects, (long long*)status_dev);
+    GS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(tile_offsets_scan_kernel, dim3(1), dim3(1024), 0, s, n_tiles, (const unsigned*)tile_counts, ic, isect_offsets,
+                       SegLists{ class_count, lists });
+    GS_CHECK_LAUNCH();
+    const bool f64 = key_bits == 24;                                       // 24 + 31 bits under the bias bit: the double-precision compare-exchange
+    hipLaunchKernelGGL(bin_scatter_kernel, dim3(gs_cdiv(V, SC_TILE)), dim3(SC_THREADS), (size_t)n_tiles * 4, s, vc,
+                       (const unsigned*)depth_keys, (const uint2*)tile_rects, f64 ? 0xffffffu : 0xffffffffu, f64 ? (1ull << 62) : 0ull, tile_w, tile_h,
+                       (const int32_t*)isect_offsets, cursor, items, (unsigned)n_isects);
+    GS_CHECK_LAUNCH();
+    // a class holds segments longer than the class below takes, and the (clamped) segments sum to <= n_isects: that bounds its grid
+    GS_CHECK_HIP(hipFuncSetAttribute((const void*)seg_sort_kernel<SEG_THREADS(SEG_CAP2), false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds_bytes(SEG_CAP2)));
+    GS_CHECK_HIP(hipFuncSetAttribute((const void*)seg_sort_kernel<SEG_THREADS(SEG_CAP2), false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds_bytes(SEG_CAP2)));
+    const int caps[SEG_CLASSES + 1] = { 0, SEG_CAP0, SEG_CAP1, SEG_CAP2 };
+    for (int c = 0; c <= SEG_CLASSES; ++c) {
+        const int64_t most = n_isects / (caps[c] + 1);
+        const int grid = (int)(most < n_tiles ? most : n_tiles);
+        if (grid == 0) continue;
+        const int32_t* list = lists + (size_t)c * n_tiles;
+#define SEG_LAUNCH1(T, G, F, LDS) hipLaunchKernelGGL((seg_sort_kernel<T, G, F>), dim3(grid), dim3(T), LDS, s, list, (const unsigned*)(class_count + c), n_tiles, \
+                                                     (const int32_t*)isect_offsets, ic, vc, items, flatten_ids_sorted)
+#define SEG_LAUNCH(T, G, LDS) do { if (f64) SEG_LAUNCH1(T, G, true, LDS); else SEG_LAUNCH1(T, G, false, LDS); } while (0)
+        if (c == 0) SEG_LAUNCH(SEG_THREADS(SEG_CAP0), false, seg_lds_bytes(SEG_CAP0));
+        else if (c == 1) SEG_LAUNCH(SEG_THREADS(SEG_CAP1), false, seg_lds_bytes(SEG_CAP1));
+        else if (c == 2) SEG_LAUNCH(SEG_THREADS(SEG_CAP2), false, seg_lds_bytes(SEG_CAP2));
+        else SEG_LAUNCH(1024, true, 0);
+#undef SEG_LAUNCH
+#undef SEG_LAUNCH1
+        GS_CHECK_LAUNCH();
+    }
+    return GS_OK;
 }
 
 extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const uint32_t* tile_rects, const uint32_t* tile_counts,
@@ -615,9 +842,14 @@ extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const u
     const int n_tiles = tile_w * tile_h;
     if (V == 0 || n_isects == 0) { GS_CHECK_HIP(gs_zero_async(isect_offsets, sizeof(int32_t) * (size_t)n_tiles, s)); return GS_OK; }
     GS_CHECK_ARG(depth_keys != nullptr && tile_rects != nullptr && flatten_ids_sorted != nullptr && ws != nullptr, "null argument");
-    if (ws_bytes < gs_isect_bin_front_ws_bytes(V, n_isects, tile_w, tile_h)) { gs_set_error("gs_isect_bin_front: workspace too small"); return GS_ENOSPC; }
+    if (tile_counts != nullptr && n_tiles <= BF_HIST_MAX) {
+        if (ws_bytes < tf_ws_bytes(n_isects, n_tiles)) { gs_set_error("gs_isect_bin_front: workspace too small"); return GS_ENOSPC; }
+        return bin_front_tile_first(V, depth_keys, tile_rects, tile_counts, counts_dev, n_isects, key_bits, tile_w, tile_h, flatten_ids_sorted,
+                                    isect_offsets, ws, status_dev, s);
+    }
+    // radix path: the offsets come from the sorted tile ids
+    if (ws_bytes < bf_radix_ws_bytes((size_t)V, (size_t)n_isects)) { gs_set_error("gs_isect_bin_front: workspace too small for the radix path (no tile_counts)"); return GS_ENOSPC; }
     const GsCount vc{ (long long)V, (const long long*)counts_dev }, ic{ (long long)n_isects, counts_dev ? (const long long*)counts_dev + 1 : nullptr };
-    const bool hist = tile_counts != nullptr && n_tiles <= BF_HIST_MAX;     // otherwise the offsets come from the sorted tile ids
     char* p = (char*)ws;
     unsigned* table = (unsigned*)p; p += table_bytes((int64_t)V > n_isects ? (int64_t)V : n_isects);
     uint2* da = (uint2*)p; p += align256((size_t)V * 8);
@@ -625,10 +857,10 @@ extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const u
     uint2* ia = (uint2*)p; p += align256((size_t)n_isects * 8);
     uint2* ib = (uint2*)p; p += align256((size_t)n_isects * 8);
     unsigned* state = (unsigned*)p; p += bf_state_bytes(V);
-    int32_t* tile_ids = hist ? nullptr : (int32_t*)p;
+    int32_t* tile_ids = (int32_t*)p;
     const int eblocks = (V + EM_TILE - 1) / EM_TILE;
     const int n_state_words = (int)(bf_state_bytes(V) / 4);
-    // 0. clear the emission's look-back state and the tile counters; capacity check
+    // 0. clear the emission's look-back state; capacity check
     hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(n_state_words, 256) < 64 ? gs_cdiv(n_state_words, 256) : 64),
                        dim3(256), 0, s, state, n_state_words, (const long long*)counts_dev,
                        (long long)V_cap, (long long)n_isects_cap, (long long*)status_dev);
@@ -646,16 +878,12 @@ extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const u
         if (rc != GS_OK) return rc;
         order = db;
     }
-    // 2. emission in depth order (chained scan inside the launch) + per-tile counts
+    // 2. emission in depth order (chained scan inside the launch)
     unsigned* ctrl = state; u64* desc = (u64*)((char*)state + 16);
     hipLaunchKernelGGL(emit_chained_kernel, dim3(eblocks), dim3(EM_THREADS), 0, s, vc, order, (const uint2*)tile_rects, ctrl, desc,
                        eblocks + 1, tile_w, ia, (unsigned)n_isects, (long long*)status_dev);
     GS_CHECK_LAUNCH();
-    if (hist) {
-        hipLaunchKernelGGL(tile_offsets_scan_kernel, dim3(1), dim3(1024), 0, s, n_tiles, (const unsigned*)tile_counts, ic, isect_offsets);
-        GS_CHECK_LAUNCH();
-    }
-    // 3. stable split by tile id: npass digits of `width` bits, the last one writes the sorted flatten ids
+    // 3. stable split by tile id: npass digits of `width` bits, the last one writes the sorted tile ids and flatten ids
     int tb = 0;
     while ((1 << tb) < n_tiles) ++tb;
     if (tb < 1) tb = 1;
@@ -664,19 +892,15 @@ extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const u
     for (int pass = 0; pass < npass; ++pass) {
         const int shift = pass * width;
         const int nbits = (tb - shift) < width ? (tb - shift) : width;
-        if (pass == npass - 1 && hist)
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, FinalFlat{ flatten_ids_sorted }, nbits, table, s);
-        else if (pass == npass - 1)
+        if (pass == npass - 1)
             rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, FinalTiles{ tile_ids, flatten_ids_sorted }, nbits, table, s);
         else
             rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, U2Out{ dst }, nbits, table, s);
         if (rc != GS_OK) return rc;
         uint2* t = src; src = dst; dst = t;
     }
-    if (!hist) {
-        hipLaunchKernelGGL(bin_offsets_tiles_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, ic, tile_ids, n_tiles, isect_offsets);
-        GS_CHECK_LAUNCH();
-    }
+    hipLaunchKernelGGL(bin_offsets_tiles_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, ic, tile_ids, n_tiles, isect_offsets);
+    GS_CHECK_LAUNCH();
     return GS_OK;
 }
 

@@ -588,8 +588,15 @@ int gs_front_fwd(int N, const float* means, const float* quats, const float* sca
                  int tight_tiles, int64_t* counts4, int64_t* status4, void* ws, size_t ws_bytes, void* stream);
 /* Binning from gs_front_fwd's outputs: flatten_ids_sorted in (tile, depth, packed index) order and the tile offsets, bit-identical
  * to gs_isect_bin_tiles_cap + gs_isect_offsets_tiles_cap.  counts_dev == NULL: V_cap / n_isects_cap are the exact counts; otherwise
- * the capacity protocol of gs_isect_bin_cap (status_dev int64[4]).  key_bits as passed to gs_front_fwd. */
+ * the capacity protocol of gs_isect_bin_cap (status_dev int64[4]).  key_bits as passed to gs_front_fwd.
+ * With tile_counts and at most 8 192 tiles the binning is tile first (scatter into the tiles' segments, one workgroup sorts each
+ * segment on chip; I * 8 bytes of scratch); gs_isect_bin_front_ws_bytes returns that size for such a grid.  Otherwise (no
+ * tile_counts, or a larger grid) it runs radix passes: for a larger grid gs_isect_bin_front_ws_bytes covers them; a caller that
+ * withholds tile_counts on a small grid gets GS_ENOSPC unless its scratch is as large as the radix passes need.
+ * gs_isect_bin_front_classes: the segment lengths up to which a segment is sorted in LDS, ascending (longer ones are sorted in
+ * place in global memory); fills at most `max` entries of caps, returns how many classes there are. */
 size_t gs_isect_bin_front_ws_bytes(int V, int64_t n_isects, int tile_w, int tile_h);
+int gs_isect_bin_front_classes(int* caps, int max);
 int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const uint32_t* tile_rects, const uint32_t* tile_counts,
                        const int64_t* counts_dev, int64_t n_isects_cap, int key_bits, int tile_w, int tile_h, int32_t* flatten_ids_sorted,
                        int32_t* isect_offsets, void* ws, size_t ws_bytes, int64_t* status_dev, void* stream);
