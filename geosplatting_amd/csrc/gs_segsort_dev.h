@@ -140,3 +140,72 @@ GS_SEGSORT_FN void gs_seg_group_n(int g, gs_u64* buf, int n, int P, int a, bool 
             }                                                                                                \
         }                                                                                                    \
     } while (0)
+
+// Hybrid: the same network for a segment of ANY length n held in a global range g[0, n), by one workgroup of NT threads with an LDS
+// buffer of one chunk, C = 2^LGC words (gs_seg_phys<true>(C) + 1 words of LDS).  P = the power of two >= n.
+//   n <= C   load, pad to P, sort in LDS, emit.
+//   n >  C   the merges k <= C stay inside the aligned chunks: every chunk that begins below n is loaded (indices >= n padded with
+//            infinities), sorted in LDS, unguarded, and stored back.  A merge k = 2^lgk > C then runs its stages of stride bits
+//            lgk-1 .. LGC as guarded register groups directly on g (the flip leads, up to GMAX stages per round trip), and its last
+//            LGC stages (half-cleaners of stride C/2 .. 1, chunk-local again) per chunk in LDS: load, the groups, store.
+//            The chunk pass of the last merge emits from LDS instead of storing back.
+// The comparators are exactly those of GS_SEG_SORT_BODY for the same P, in the same stage order, so the result is the same word for
+// word; a word behind n is neither loaded nor stored.  bar() separates the groups and the loads / stores of a chunk from them (a
+// workgroup barrier on the device: every call sits in control flow that depends on n, LGC and GMAX alone).  emit(i, word) receives
+// every sorted word once, i in [0, n).
+template <int GMAX, int LGC, int NT, bool F64, class Barrier, class Emit>
+GS_SEGSORT_FN void gs_seg_hybrid(gs_u64* lds, gs_u64* g, int n, int tid, Barrier bar, Emit emit)
+{
+    static_assert(LGC > GMAX, "a chunk holds more than one group");
+    constexpr int C = 1 << LGC;
+    if (n <= C) {
+        int P = 1 << GMAX;
+        while (P < n) P <<= 1;
+        for (int i = tid; i < P; i += NT) lds[gs_seg_phys<true>(i)] = i < n ? g[i] : gs_seg_inf<F64>();
+        bar();
+        GS_SEG_SORT_BODY(GMAX, true, F64, false, lds, n, P, tid, NT, bar());
+        for (int i = tid; i < n; i += NT) emit(i, lds[gs_seg_phys<true>(i)]);
+        return;
+    }
+    int lgP = LGC + 1;
+    while ((1ll << lgP) < (long long)n) ++lgP;
+    // merges k <= C, chunk by chunk (a short last chunk takes the network of its own power of two: the merges above it meet nothing
+    // but infinities in their upper halves and a sorted lower half, so none of their comparators would move a word)
+    for (int cb = 0; cb < n; cb += C) {
+        const int nl = n - cb < C ? n - cb : C;
+        int Pl = 1 << GMAX;
+        while (Pl < nl) Pl <<= 1;
+        for (int i = tid; i < Pl; i += NT) lds[gs_seg_phys<true>(i)] = i < nl ? g[cb + i] : gs_seg_inf<F64>();
+        bar();
+        GS_SEG_SORT_BODY(GMAX, true, F64, false, lds, nl, Pl, tid, NT, bar());
+        for (int i = tid; i < nl; i += NT) g[cb + i] = lds[gs_seg_phys<true>(i)];
+        bar();
+    }
+    const int P = 1 << lgP;
+    for (int lgk = LGC + 1; lgk <= lgP; ++lgk) {
+        int rem = lgk;
+        bool flip = true;
+        while (rem > LGC) {                                      // global stages, stride bits rem-1 .. rem-gg
+            const int gg = flip ? ((rem - LGC - 1) % GMAX) + 1 : GMAX;
+            gs_seg_group_n<GMAX, false, F64, true>(gg, g, n, P, rem - gg, flip, tid, NT);
+            bar();
+            rem -= gg;
+            flip = false;
+        }
+        const bool last = lgk == lgP;
+        for (int cb = 0; cb < n; cb += C) {                      // stride bits LGC-1 .. 0
+            const int nl = n - cb < C ? n - cb : C;
+            for (int i = tid; i < C; i += NT) lds[gs_seg_phys<true>(i)] = i < nl ? g[cb + i] : gs_seg_inf<F64>();
+            bar();
+            for (int r = LGC; r > 0;) {
+                const int gg = ((r - 1) % GMAX) + 1;
+                gs_seg_group_n<GMAX, true, F64, false>(gg, lds, nl, C, r - gg, false, tid, NT);
+                bar();
+                r -= gg;
+            }
+            if (last) { for (int i = tid; i < nl; i += NT) emit(cb + i, lds[gs_seg_phys<true>(i)]); }
+            else      { for (int i = tid; i < nl; i += NT) g[cb + i] = lds[gs_seg_phys<true>(i)]; }
+            bar();
+        }
+    }
+}

@@ -410,11 +410,12 @@ extern "C" int gs_isect_bin_tiles_cap(int V_cap, const float* means2d, const int
 //
 // Tile first (tile_counts given, <= BF_HIST_MAX tiles: the engine's path).  The counters fix every tile's segment of the output before
 // anything is sorted, so no pass over the whole list is needed:
-//   setup    bin_setup_kernel           clears the per-tile cursors and the class counters; capacity check
-//   offsets  tile_offsets_scan_kernel   exclusive scan of the counters, clamped to the capacity; files the tiles by segment length
+//   offsets  tile_offsets_scan_kernel   exclusive scan of the counters, clamped to the capacity; files the tiles by segment length;
+//                                       clears the per-tile cursors; capacity check
 //   scatter  bin_scatter_kernel         packed slots in order -> {key, slot} items into their tile's segment, any order inside it
-//   sort     seg_sort_kernel x 4        one workgroup per tile sorts its segment by (key, slot) on chip and writes the slots
-// 7 launches, I * 8 bytes of scratch.  The items are written once and read once (about 27 MB each way for the bench view's 3.4 M
+//   sort     seg_sort_kernel,           one workgroup per tile sorts its segment by (key, slot) and writes the slots: up to 2 048 items
+//            seg_sort_large_kernel      and up to 8 192 in LDS, longer ones chunk by chunk in LDS with the wide stages in place
+// 4 launches, I * 8 bytes of scratch.  The items are written once and read once (about 27 MB each way for the bench view's 3.4 M
 // intersections, next to 24 MB of keys and rectangles in and 14 MB of ids out); the radix path moved ~0.6 GB for the same list.  No
 // kernel waits for another workgroup, every clear is a kernel, nothing is read back: capturable as it stands.
 //
@@ -550,31 +551,39 @@ emit_chained_kernel(GsCount vc, const uint2* __restrict__ order, const uint2* __
 }
 
 // ---- tile-first binning (the engine's path up to BF_HIST_MAX tiles) ----------------------------------------------------------------
-// LDS classes of the segment sort: a segment of up to SEG_CAP<c> items is sorted in the LDS of one workgroup (class 0 -- seven in ten of
-// the bench scene's segments -- in 16.9 KB, under the 22.5 KB RS_ITEMS was tuned to); longer segments are sorted in place in the item
-// buffer by one workgroup each (class SEG_CLASSES, "general": any length up to I).  The capacities are powers of two: the LDS then
-// holds the whole padded network and no index of it is ever checked (gs_segsort_dev.h).  A thread holds 2^SEG_GMAX items.
-#define SEG_CLASSES 3
+// Two classes of the segment sort, one launch each.  Small: a segment of up to SEG_CAP0 items is sorted in the LDS of one 128-thread
+// workgroup (seven in ten of the bench scene's segments, in 16.9 KB, under the 22.5 KB RS_ITEMS was tuned to).  Large: every longer
+// segment goes to one 512-thread workgroup with the LDS of one chunk of SEG_CHUNK items (66 KB: two of them, or one beside two
+// compositor workgroups, share a CU -- no workgroup needs an empty CU); up to SEG_CHUNK items it is sorted there as in the small
+// class, a longer one by the hybrid schedule of gs_segsort_dev.h -- the same network, its wide stages in place on the segment's range
+// of the item buffer, the rest chunk by chunk in LDS.  The capacities are powers of two: the LDS then holds a whole padded network
+// and no index of it is ever checked.  A thread holds 2^SEG_GMAX items.
+#define SEG_CLASSES 2
 #define SEG_CAP0 2048
-#define SEG_CAP1 4096
-#define SEG_CAP2 16384
+#define SEG_LG_CHUNK 13                      // (the large class: 512 threads x 8 192 items; 256 x 4 096 measured: DESIGN.md section 6)
+#define SEG_CHUNK (1 << SEG_LG_CHUNK)
 #define SEG_GMAX 4                           // (8 items per thread: +7 % on the three sort launches, 32: +25 %, 164 VGPRs)
-#define SEG_THREADS(cap) ((cap) >> SEG_GMAX > 1024 ? 1024 : ((cap) >> SEG_GMAX))
+#define SEG_THREADS(cap) ((cap) >> SEG_GMAX)
 #define SEG_BINS 64                          // half-octave length bins per class (lengths < 2^31: 62 used)
 static size_t seg_lds_bytes(int cap) { return (size_t)(cap + (cap >> 5) + 1) * sizeof(u64); }
 
 extern "C" int gs_isect_bin_front_classes(int* caps, int max)
 {
-    const int c[SEG_CLASSES] = { SEG_CAP0, SEG_CAP1, SEG_CAP2 };
-    for (int i = 0; i < SEG_CLASSES && i < max; ++i) if (caps) caps[i] = c[i];
-    return SEG_CLASSES;
+    const int c[2] = { SEG_CAP0, SEG_CHUNK };                   // the lengths at which the path changes
+    for (int i = 0; i < 2 && i < max; ++i) if (caps) caps[i] = c[i];
+    return 2;
 }
 
 // Work lists of the segment sort, filled by the offsets scan: lists[c * n_tiles ..] = the non-empty tiles of class c, longest first to
-// the half octave (struct BwdOrder of gs_raster.hip files the backward's tiles the same way), count[c] = how many.
-struct SegLists { unsigned* count; int32_t* lists; };
+// the half octave (struct BwdOrder of gs_raster.hip files the backward's tiles the same way), count[c] = how many.  The scan also does
+// what bin_setup_kernel does for the radix path: it clears the scatter's per-tile cursors and checks the view against its capacity.
+struct SegLists {
+    unsigned* count; int32_t* lists;
+    unsigned* cursor;                        // [n_tiles], cleared
+    const long long* counts; long long v_cap, i_cap; long long* status;          // capacity protocol, as bin_setup_kernel
+};
 
-__device__ __forceinline__ int seg_class(unsigned len) { return len <= SEG_CAP0 ? 0 : (len <= SEG_CAP1 ? 1 : (len <= SEG_CAP2 ? 2 : 3)); }
+__device__ __forceinline__ int seg_class(unsigned len) { return len <= SEG_CAP0 ? 0 : 1; }
 __device__ __forceinline__ int seg_bin(unsigned len)                 // len >= 1: 2 * floor(log2) + the next bit, reversed (longest first)
 {
     const int l2 = 31 - __clz((int)len);
@@ -585,15 +594,24 @@ __device__ __forceinline__ int seg_bin(unsigned len)                 // len >= 1
 // offsets[t] = min(exclusive prefix of the tile counts, n) by one workgroup: the tile offsets of a view.  (The clamp only ever acts
 // on a view that overflowed its capacity: its list is truncated, the offsets then are not those of the truncated
 // list -- memory-safe, wrong image, reported, as the capacity protocol says.)  With `sl` the same workgroup files every non-empty tile
-// by the length of its (clamped) segment: the lengths of a class sum to <= n, which bounds the grid of that class on the host.
+// by the length of its (clamped) segment: the lengths of a class sum to <= n, which bounds the grid of that class on the host.  It
+// walks every tile anyway, so it also clears the scatter's cursors, and its first thread does the capacity check.
 __global__ void __launch_bounds__(1024)
 tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, GsCount nc, int32_t* __restrict__ offsets, SegLists sl)
 {
     __shared__ unsigned wsum[16];
-    __shared__ unsigned s_bin[(SEG_CLASSES + 1) * SEG_BINS];
+    __shared__ unsigned s_bin[SEG_CLASSES * SEG_BINS];
     const unsigned n = (unsigned)gs_count(nc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (sl.count && threadIdx.x < (SEG_CLASSES + 1) * SEG_BINS) s_bin[threadIdx.x] = 0u;
+    if (sl.count && threadIdx.x < SEG_CLASSES * SEG_BINS) s_bin[threadIdx.x] = 0u;
+    if (sl.count && threadIdx.x == 0 && sl.counts != nullptr && sl.status != nullptr) {     // capacity protocol, as capacity_check_kernel
+        const long long V = sl.counts[0], I = sl.counts[1];
+        if (V > sl.v_cap || I > sl.i_cap) {
+            sl.status[0] = GS_ENOSPC;
+            if (I > sl.status[1]) sl.status[1] = I;
+            if (V > sl.status[2]) sl.status[2] = V;
+        }
+    }
     __syncthreads();
     unsigned carry = 0u;
     for (int i0 = 0; i0 < n_tiles; i0 += 1024) {
@@ -609,6 +627,7 @@ tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, 
             const unsigned o = carry + before + incl - v;
             const unsigned beg = o < n ? o : n, end = o + v < n ? o + v : n;
             offsets[i] = (int32_t)beg;
+            if (sl.count) sl.cursor[i] = 0u;
             if (sl.count && end > beg) atomicAdd(&s_bin[seg_class(end - beg) * SEG_BINS + seg_bin(end - beg)], 1u);
         }
         carry += all;
@@ -616,7 +635,7 @@ tile_offsets_scan_kernel(int n_tiles, const unsigned* __restrict__ tile_counts, 
     }
     if (!sl.count) return;
     // wave c scans the bins of class c (64 bins = one wave): start of every bin inside the class list, and the class total
-    if (wave <= SEG_CLASSES) {
+    if (wave < SEG_CLASSES) {
         const unsigned v = s_bin[wave * SEG_BINS + lane];
         const unsigned incl = gs_wave_incl_scan(v);
         s_bin[wave * SEG_BINS + lane] = incl - v;
@@ -707,11 +726,12 @@ bin_scatter_kernel(GsCount vc, const unsigned* __restrict__ keys, const uint2* _
 }
 
 // Segment sort: workgroup b of a class sorts the segment of tile lists[b] by its items (key, then slot) -- the order of the stable radix sort,
-// ties included, whatever order the scatter left -- and writes the slots.  LDS classes load the segment once, pad it to its power of two
-// and sort it there; the general class runs the same network, guarded, in place on its own range of the item buffer (one CU: its
-// stores and loads meet in that CU's cache, a workgroup barrier orders them).  A slot is clamped to the view's count: after an overflow
-// the tail of the item buffer was never written, and the ids must stay valid rows for whoever gathers by them.
-template <int THREADS, bool GLOBAL, bool F64>
+// ties included, whatever order the scatter left -- and writes the slots.  The small class loads the segment once, pads it to its power
+// of two and sorts it in LDS; the large class does the same up to one chunk and runs the hybrid schedule on a longer segment (its wide
+// stages in place on the segment's own range of the item buffer: one CU, its stores and loads meet in that CU's cache, a workgroup
+// barrier orders them).  A slot is clamped to the view's count: after an overflow the tail of the item buffer was never written, and
+// the ids must stay valid rows for whoever gathers by them.
+template <int THREADS, bool F64>
 __global__ void __launch_bounds__(THREADS)
 seg_sort_kernel(const int32_t* __restrict__ list, const unsigned* __restrict__ list_count, int n_tiles, const int32_t* __restrict__ offsets,
                 GsCount ic, GsCount vc, u64* items, int32_t* __restrict__ flat)
@@ -728,16 +748,34 @@ seg_sort_kernel(const int32_t* __restrict__ list, const unsigned* __restrict__ l
     const int tid = threadIdx.x;
     int P = 1 << SEG_GMAX;
     while (P < n) P <<= 1;
-    u64* buf = GLOBAL ? items + beg : s_seg;
-    if (!GLOBAL) {
-        for (int i = tid; i < P; i += THREADS) s_seg[gs_seg_phys<true>(i)] = i < n ? items[beg + i] : gs_seg_inf<F64>();
-        __syncthreads();
-    }
-    GS_SEG_SORT_BODY(SEG_GMAX, !GLOBAL, F64, GLOBAL, buf, n, P, tid, THREADS, __syncthreads());
+    for (int i = tid; i < P; i += THREADS) s_seg[gs_seg_phys<true>(i)] = i < n ? items[beg + i] : gs_seg_inf<F64>();
+    __syncthreads();
+    GS_SEG_SORT_BODY(SEG_GMAX, true, F64, false, s_seg, n, P, tid, THREADS, __syncthreads());
     for (int i = tid; i < n; i += THREADS) {
-        const unsigned slot = (unsigned)buf[gs_seg_phys<!GLOBAL>(i)] & 0x7fffffffu;
+        const unsigned slot = (unsigned)s_seg[gs_seg_phys<true>(i)] & 0x7fffffffu;
         flat[beg + i] = (int32_t)(slot < vmax ? slot : vmax);
     }
+}
+
+template <int THREADS, int LG_CHUNK, bool F64>
+__global__ void __launch_bounds__(THREADS)
+seg_sort_large_kernel(const int32_t* __restrict__ list, const unsigned* __restrict__ list_count, int n_tiles, const int32_t* __restrict__ offsets,
+                      GsCount ic, GsCount vc, u64* items, int32_t* __restrict__ flat)
+{
+    __shared__ u64 s_seg[(1 << LG_CHUNK) + (1 << (LG_CHUNK - 5)) + 1];          // (static: 66 KB need no per-launch opt-in on the host)
+    if (blockIdx.x >= *list_count) return;
+    const int t = list[blockIdx.x];
+    const int n_all = (int)gs_count(ic);
+    const int beg = offsets[t], end = t + 1 < n_tiles ? offsets[t + 1] : n_all;
+    const int n = end - beg;                                     // (uniform across the workgroup: so is every barrier of the schedule)
+    if (n <= 0) return;
+    const long long V = gs_count(vc);
+    const unsigned vmax = V > 0 ? (unsigned)(V - 1) : 0u;
+    gs_seg_hybrid<SEG_GMAX, LG_CHUNK, THREADS, F64>(s_seg, items + beg, n, (int)threadIdx.x, [] { __syncthreads(); },
+        [=](int i, u64 w) {
+            const unsigned slot = (unsigned)w & 0x7fffffffu;
+            flat[beg + i] = (int32_t)(slot < vmax ? slot : vmax);
+        });
 }
 
 // offsets[t] = first sorted position whose tile id >= t (the > 8 192-tile path; same as isect_offsets_tiles_kernel of gs_project.hip)
@@ -762,10 +800,10 @@ bin_offsets_tiles_kernel(GsCount nc, const int32_t* __restrict__ tiles, int n_ti
 
 
 // scratch of the two paths.  Tile first: the per-tile cursors + the class counters, the class lists, the items.
-static size_t tf_state_words(int n_tiles) { return (size_t)n_tiles + SEG_CLASSES + 1; }
+static size_t tf_state_words(int n_tiles) { return (size_t)n_tiles + SEG_CLASSES; }
 static size_t tf_ws_bytes(int64_t n_isects, int n_tiles)
 {
-    return align256(tf_state_words(n_tiles) * 4) + align256((size_t)(SEG_CLASSES + 1) * n_tiles * 4) + align256((size_t)n_isects * 8) + 256;
+    return align256(tf_state_words(n_tiles) * 4) + align256((size_t)SEG_CLASSES * n_tiles * 4) + align256((size_t)n_isects * 8) + 256;
 }
 static size_t bf_radix_ws_bytes(size_t v, size_t n)
 {
@@ -791,14 +829,10 @@ static int bin_front_tile_first(int V, const uint32_t* depth_keys, const uint32_
     char* p = (char*)ws;
     unsigned* cursor = (unsigned*)p;                                        // [n_tiles], then the class counters
     unsigned* class_count = cursor + n_tiles; p += align256(tf_state_words(n_tiles) * 4);
-    int32_t* lists = (int32_t*)p; p += align256((size_t)(SEG_CLASSES + 1) * n_tiles * 4);
+    int32_t* lists = (int32_t*)p; p += align256((size_t)SEG_CLASSES * n_tiles * 4);
     u64* items = (u64*)p;
-    const int n_state_words = (int)tf_state_words(n_tiles);
-    hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(n_state_words, 256) < 64 ? gs_cdiv(n_state_words, 256) : 64), dim3(256), 0, s, cursor,
-                       n_state_words, (const long long*)counts_dev, (long long)V, (long long)n_isects, (long long*)status_dev);
-    GS_CHECK_LAUNCH();
     hipLaunchKernelGGL(tile_offsets_scan_kernel, dim3(1), dim3(1024), 0, s, n_tiles, (const unsigned*)tile_counts, ic, isect_offsets,
-                       SegLists{ class_count, lists });
+                       SegLists{ class_count, lists, cursor, (const long long*)counts_dev, (long long)V, (long long)n_isects, (long long*)status_dev });
     GS_CHECK_LAUNCH();
     const bool f64 = key_bits == 24;                                       // 24 + 31 bits under the bias bit: the double-precision compare-exchange
     hipLaunchKernelGGL(bin_scatter_kernel, dim3(gs_cdiv(V, SC_TILE)), dim3(SC_THREADS), (size_t)n_tiles * 4, s, vc,
@@ -806,23 +840,22 @@ static int bin_front_tile_first(int V, const uint32_t* depth_keys, const uint32_
                        (const int32_t*)isect_offsets, cursor, items, (unsigned)n_isects);
     GS_CHECK_LAUNCH();
     // a class holds segments longer than the class below takes, and the (clamped) segments sum to <= n_isects: that bounds its grid
-    GS_CHECK_HIP(hipFuncSetAttribute((const void*)seg_sort_kernel<SEG_THREADS(SEG_CAP2), false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds_bytes(SEG_CAP2)));
-    GS_CHECK_HIP(hipFuncSetAttribute((const void*)seg_sort_kernel<SEG_THREADS(SEG_CAP2), false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds_bytes(SEG_CAP2)));
-    const int caps[SEG_CLASSES + 1] = { 0, SEG_CAP0, SEG_CAP1, SEG_CAP2 };
-    for (int c = 0; c <= SEG_CLASSES; ++c) {
+    const int caps[SEG_CLASSES] = { 0, SEG_CAP0 };
+    for (int c = 0; c < SEG_CLASSES; ++c) {
         const int64_t most = n_isects / (caps[c] + 1);
         const int grid = (int)(most < n_tiles ? most : n_tiles);
         if (grid == 0) continue;
         const int32_t* list = lists + (size_t)c * n_tiles;
-#define SEG_LAUNCH1(T, G, F, LDS) hipLaunchKernelGGL((seg_sort_kernel<T, G, F>), dim3(grid), dim3(T), LDS, s, list, (const unsigned*)(class_count + c), n_tiles, \
-                                                     (const int32_t*)isect_offsets, ic, vc, items, flatten_ids_sorted)
-#define SEG_LAUNCH(T, G, LDS) do { if (f64) SEG_LAUNCH1(T, G, true, LDS); else SEG_LAUNCH1(T, G, false, LDS); } while (0)
-        if (c == 0) SEG_LAUNCH(SEG_THREADS(SEG_CAP0), false, seg_lds_bytes(SEG_CAP0));
-        else if (c == 1) SEG_LAUNCH(SEG_THREADS(SEG_CAP1), false, seg_lds_bytes(SEG_CAP1));
-        else if (c == 2) SEG_LAUNCH(SEG_THREADS(SEG_CAP2), false, seg_lds_bytes(SEG_CAP2));
-        else SEG_LAUNCH(1024, true, 0);
+#define SEG_LAUNCH(KERNEL, T, LDS) hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(T), LDS, s, list, (const unsigned*)(class_count + c), n_tiles, \
+                                                      (const int32_t*)isect_offsets, ic, vc, items, flatten_ids_sorted)
+        if (c == 0) {
+            if (f64) SEG_LAUNCH((seg_sort_kernel<SEG_THREADS(SEG_CAP0), true>), SEG_THREADS(SEG_CAP0), seg_lds_bytes(SEG_CAP0));
+            else SEG_LAUNCH((seg_sort_kernel<SEG_THREADS(SEG_CAP0), false>), SEG_THREADS(SEG_CAP0), seg_lds_bytes(SEG_CAP0));
+        } else {
+            if (f64) SEG_LAUNCH((seg_sort_large_kernel<SEG_THREADS(SEG_CHUNK), SEG_LG_CHUNK, true>), SEG_THREADS(SEG_CHUNK), 0);
+            else SEG_LAUNCH((seg_sort_large_kernel<SEG_THREADS(SEG_CHUNK), SEG_LG_CHUNK, false>), SEG_THREADS(SEG_CHUNK), 0);
+        }
 #undef SEG_LAUNCH
-#undef SEG_LAUNCH1
         GS_CHECK_LAUNCH();
     }
     return GS_OK;

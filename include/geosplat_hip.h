@@ -593,8 +593,10 @@ int gs_front_fwd(int N, const float* means, const float* quats, const float* sca
  * segment on chip; I * 8 bytes of scratch); gs_isect_bin_front_ws_bytes returns that size for such a grid.  Otherwise (no
  * tile_counts, or a larger grid) it runs radix passes: for a larger grid gs_isect_bin_front_ws_bytes covers them; a caller that
  * withholds tile_counts on a small grid gets GS_ENOSPC unless its scratch is as large as the radix passes need.
- * gs_isect_bin_front_classes: the segment lengths up to which a segment is sorted in LDS, ascending (longer ones are sorted in
- * place in global memory); fills at most `max` entries of caps, returns how many classes there are. */
+ * gs_isect_bin_front_classes: the segment lengths at which the sort changes its path, ascending -- {2048, 8192}: up to the first a
+ * 128-thread workgroup sorts the segment in LDS, up to the second a 512-thread workgroup does, a longer one is sorted by a 512-thread
+ * workgroup in 8 192-item chunks in LDS with the wide stages of the network in place in global memory; fills at most `max` entries
+ * of caps, returns how many lengths there are. */
 size_t gs_isect_bin_front_ws_bytes(int V, int64_t n_isects, int tile_w, int tile_h);
 int gs_isect_bin_front_classes(int* caps, int max);
 int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const uint32_t* tile_rects, const uint32_t* tile_counts,
