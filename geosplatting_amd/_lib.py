@@ -2,17 +2,22 @@
 
 There is NO fallback: if the HIP library is missing the import of any op raises.  PyTorch is only used for
 device memory (``tensor.data_ptr()``) and the current HIP stream.
+
+The header is the one table of prototypes: ``lib()`` sets ``restype`` and ``argtypes`` of every ``gs_*`` symbol from it, so callers
+pass plain Python numbers and ``ptr(tensor)``; ctypes refuses a wrong argument count or kind before the call.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgeosplat_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "geosplat_hip.h")
 
 GS_MAX_LEVELS = 16
 
@@ -47,35 +52,57 @@ class GsEnvGrad(C.Structure):
     _fields_ = [("base", C.c_void_p), ("levels", C.c_void_p * GS_MAX_LEVELS)]
 
 
-# every symbol include/geosplat_hip.h declares (tests/test_abi.py checks the list against the header)
-SYMBOLS = [
-    "gs_last_error", "gs_version", "gs_project_ws_bytes", "gs_project_fwd", "gs_project_fwd_vis", "gs_project_fwd_vis_ex", "gs_isect_emit", "gs_sort_ws_bytes",
-    "gs_isect_sort", "gs_isect_bin_ws_bytes", "gs_isect_bin", "gs_isect_offsets", "gs_raster_ws_bytes", "gs_raster_fwd", "gs_raster_prepare", "gs_raster_prepare_vis", "gs_raster_composite", "gs_raster_grad_stride", "gs_raster_bwd", "gs_raster_bwd_acc", "gs_selftest_rcp", "gs_selftest_exp", "gs_selftest_cube_edges", "gs_isect_bin_cap", "gs_isect_offsets_cap", "gs_isect_bin_tiles_cap", "gs_isect_offsets_tiles_cap", "gs_raster_prepare_vis_cap", "gs_raster_composite_cap", "gs_raster_bwd_cap", "gs_raster_bwd_acc_cap", "gs_raster_composite_tone", "gs_raster_bwd_tone_acc", "gs_raster_log_ws_bytes", "gs_raster_composite_tone_log", "gs_raster_bwd_tone_log_acc", "gs_project_bwd_cap", "gs_project_bwd", "gs_project_bwd_ex", "gs_shade_fwd",
-    "gs_shade_bwd_ws_bytes", "gs_shade_bwd_plan_blocks", "gs_shade_bwd", "gs_tonemap_fwd", "gs_tonemap_bwd", "gs_tonemap_fwd3", "gs_tonemap_bwd3", "gs_cubemap_mip_fwd", "gs_cubemap_mip_chain_fwd", "gs_cube_sample_linear",
-    "gs_cubemap_mip_bwd", "gs_diffuse_cubemap_fwd", "gs_diffuse_cubemap_bwd", "gs_specular_bounds", "gs_specular_bounds_ws_bytes", "gs_specular_bounds_fast", "gs_cube_dir_table",
-    "gs_specular_cubemap_fwd", "gs_specular_cubemap_bwd", "gs_specular_tiles_count", "gs_specular_tiles_fill",
-    "gs_specular_tiles_check", "gs_specular_tiles_apply", "gs_specular_tiles_apply_multi", "gs_mgadapter_fwd", "gs_mgadapter_bwd", "gs_vertex_normals_fwd",
-    "gs_vertex_normals_bwd", "gs_photo_loss_ws_bytes", "gs_photo_loss", "gs_smooth_loss_ws_bytes", "gs_smooth_loss", "gs_hashgrid_fwd", "gs_hashgrid_bwd_ws_bytes", "gs_hashgrid_bwd", "gs_hashgrid_bwd_fixed_ws_bytes", "gs_hashgrid_bwd_fixed", "gs_mlp_wgrad_ws_bytes", "gs_mlp_wgrad",
-    "gs_flexicubes_ws_bytes", "gs_flexicubes_count", "gs_flexicubes_fwd", "gs_flexicubes_bwd", "gs_flexicubes_entropy_fwd",
-    "gs_flexicubes_entropy_bwd", "gs_front_ws_bytes", "gs_front_fwd", "gs_isect_bin_front_ws_bytes", "gs_isect_bin_front", "gs_isect_bin_front_classes", "gs_tail_bwd", "gs_tail_bwd_multi", "gs_tail_bwd_multi_parts", "gs_tail_priv_ws_bytes", "gs_tail_priv_reduce", "gs_smooth_gather", "gs_smooth_fold", "gs_activation_chain",
-    "gs_densify_stats", "gs_densify_ws_bytes", "gs_densify_plan", "gs_densify_fill",
-    "gs_surfel_project_ws_bytes", "gs_surfel_project_fwd", "gs_surfel_project_bwd", "gs_surfel_raster_fwd", "gs_surfel_grad_stride",
-    "gs_surfel_raster_bwd",
-    "gs_tsdf_integrate", "gs_tsdf_extract_ws_bytes", "gs_tsdf_extract_count", "gs_tsdf_extract_fill",
-    "gs_meshraster_ws_bytes", "gs_meshraster_fwd", "gs_meshraster_resolve", "gs_meshraster_bwd", "gs_mesh_interp_fwd",
-    "gs_mesh_interp_bwd",
-    "gs_mesh_topology_bytes", "gs_mesh_topology_build", "gs_meshaa_fwd", "gs_meshaa_bwd",
-    "gs_tex2d_fwd", "gs_tex2d_bwd", "gs_meshshade_fwd", "gs_meshshade_bwd",
-    "gs_bvh_bytes", "gs_bvh_ws_bytes", "gs_bvh_build", "gs_ray_occluded", "gs_ray_closest",
-    "gs_envshade_fwd", "gs_envshade_bwd",
-    "gs_denoise_tiled_fits", "gs_denoise_fwd", "gs_denoise_bwd",
-]
-
-_lib: Optional[C.CDLL] = None
-
-
 class GeoSplatHipError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_RETURNS = {**_SCALARS, "const char*": C.c_char_p}
+_PROTOTYPE = re.compile(r"(const\s+char\s*\*|\w+)\s*\b(gs_\w+)\s*\((.*)\)", re.S)
+
+
+def _ctype(where: str, decl: str):
+    """ctypes type of one parameter declaration ("const float* means", "size_t ws_bytes"): every pointer is a c_void_p."""
+    if "*" in decl and "(" not in decl:
+        return C.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if len(words) != 2 or words[0] not in _SCALARS:
+        raise GeoSplatHipError(f"{where}: parameter type of `{decl.strip()}` is not one the binding knows")
+    return _SCALARS[words[0]]
+
+
+def parse_header(path: str) -> dict:
+    """{name: (restype, argtypes)} of every gs_* prototype the header declares -- the header is the one table of the C ABI.  It is
+    plain C: comments, preprocessor lines, the extern "C" brace and the typedef struct blocks are dropped, every remaining statement
+    must be a prototype over the scalar types above and pointers."""
+    if not os.path.exists(path):
+        raise GeoSplatHipError(f"{path} not found: the binding takes every prototype from it (the package runs from a checkout)")
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\b.*?\}\s*\w+\s*;", "", text, flags=re.S)
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = stmt.strip()
+        if stmt in ("", "}"):
+            continue
+        m = _PROTOTYPE.fullmatch(stmt)
+        if m is None:
+            raise GeoSplatHipError(f"{path}: cannot read `{' '.join(stmt.split())[:80]}` as a gs_* prototype")
+        ret, name, params = m.groups()
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise GeoSplatHipError(f"{path}: {name}: return type `{ret}` is not one the binding knows")
+        params = params.strip()
+        protos[name] = (_RETURNS[ret], [] if params in ("", "void") else [_ctype(f"{path}: {name}", p) for p in params.split(",")])
+    return protos
+
+
+PROTOTYPES = parse_header(HEADER_PATH)
+SYMBOLS = list(PROTOTYPES)                 # every symbol include/geosplat_hip.h declares
+
+_lib: Optional[C.CDLL] = None
 
 
 def lib() -> C.CDLL:
@@ -87,91 +114,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m geosplatting_amd.build` "
                 "(hipcc --offload-arch=gfx950).  geosplatting_amd has no CPU / PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        l.gs_last_error.restype = C.c_char_p
-        l.gs_project_ws_bytes.restype = C.c_size_t
-        l.gs_project_ws_bytes.argtypes = [C.c_int]
-        l.gs_sort_ws_bytes.restype = C.c_size_t
-        l.gs_sort_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
-        l.gs_isect_bin_ws_bytes.restype = C.c_size_t
-        l.gs_isect_bin_ws_bytes.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
-        l.gs_shade_bwd_ws_bytes.restype = C.c_size_t
-        l.gs_shade_bwd_ws_bytes.argtypes = [C.c_void_p, C.c_int]
-        l.gs_shade_bwd_plan_blocks.restype = C.c_int
-        l.gs_shade_bwd_plan_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        l.gs_hashgrid_bwd_ws_bytes.restype = C.c_size_t
-        l.gs_hashgrid_bwd_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        l.gs_hashgrid_bwd_fixed_ws_bytes.restype = C.c_size_t
-        l.gs_hashgrid_bwd_fixed_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        l.gs_mlp_wgrad_ws_bytes.restype = C.c_size_t
-        l.gs_mlp_wgrad_ws_bytes.argtypes = [C.c_int64]
-        l.gs_flexicubes_ws_bytes.restype = C.c_size_t
-        l.gs_flexicubes_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        l.gs_photo_loss_ws_bytes.restype = C.c_size_t
-        l.gs_photo_loss_ws_bytes.argtypes = [C.c_int, C.c_int]
-        l.gs_smooth_loss_ws_bytes.restype = C.c_size_t
-        l.gs_smooth_loss_ws_bytes.argtypes = [C.c_int, C.c_int]
-        l.gs_specular_bounds_ws_bytes.restype = C.c_size_t
-        l.gs_specular_bounds_ws_bytes.argtypes = [C.c_int]
-        l.gs_front_ws_bytes.restype = C.c_size_t
-        l.gs_front_ws_bytes.argtypes = [C.c_int]
-        l.gs_isect_bin_front_ws_bytes.restype = C.c_size_t
-        l.gs_isect_bin_front_ws_bytes.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
-        l.gs_tail_priv_ws_bytes.restype = C.c_size_t
-        l.gs_tail_priv_ws_bytes.argtypes = [C.c_void_p, C.c_int]
-        l.gs_raster_log_ws_bytes.restype = C.c_size_t
-        l.gs_raster_log_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
-        l.gs_raster_ws_bytes.restype = C.c_size_t
-        l.gs_raster_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
-        l.gs_densify_ws_bytes.restype = C.c_size_t
-        l.gs_densify_ws_bytes.argtypes = [C.c_int64, C.c_int]
-        l.gs_surfel_project_ws_bytes.restype = C.c_size_t
-        l.gs_surfel_project_ws_bytes.argtypes = [C.c_int]
-        l.gs_tsdf_extract_ws_bytes.restype = C.c_size_t
-        l.gs_tsdf_extract_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        l.gs_tsdf_integrate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                        C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gs_tsdf_extract_count.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        l.gs_tsdf_extract_fill.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
-                                           C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gs_meshraster_ws_bytes.restype = C.c_size_t
-        l.gs_meshraster_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
-        mesh_head = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float]
-        l.gs_meshraster_fwd.argtypes = mesh_head + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        l.gs_meshraster_resolve.argtypes = mesh_head + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        l.gs_meshraster_bwd.argtypes = mesh_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gs_mesh_interp_fwd.argtypes = [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]
-        l.gs_mesh_interp_bwd.argtypes = [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gs_mesh_topology_bytes.restype = C.c_size_t
-        l.gs_mesh_topology_bytes.argtypes = [C.c_int64]
-        l.gs_mesh_topology_build.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        aa_head = mesh_head + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        l.gs_meshaa_fwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gs_meshaa_bwd.argtypes = aa_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        tex_head = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        l.gs_tex2d_fwd.argtypes = tex_head + [C.c_void_p, C.c_void_p]
-        l.gs_tex2d_bwd.argtypes = tex_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        shade_head = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
-        l.gs_meshshade_fwd.argtypes = shade_head + [C.c_void_p, C.c_void_p]
-        l.gs_meshshade_bwd.argtypes = shade_head + [C.c_void_p] * 8
-        l.gs_bvh_bytes.restype = C.c_size_t
-        l.gs_bvh_bytes.argtypes = [C.c_int64]
-        l.gs_bvh_ws_bytes.restype = C.c_size_t
-        l.gs_bvh_ws_bytes.argtypes = [C.c_int64]
-        l.gs_bvh_build.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        ray_head = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                    C.c_float, C.c_float]
-        l.gs_ray_occluded.argtypes = ray_head + [C.c_void_p, C.c_void_p]
-        l.gs_ray_closest.argtypes = ray_head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        env_head = ([C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
-                    C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
-        l.gs_envshade_fwd.argtypes = env_head + [C.c_void_p] * 7
-        l.gs_envshade_bwd.argtypes = env_head + [C.c_int] + [C.c_void_p] * 8
-        l.gs_denoise_tiled_fits.argtypes = [C.c_int, C.c_double]
-        l.gs_denoise_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_double, C.c_int] + [C.c_void_p] * 3
-        l.gs_denoise_bwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_double, C.c_int] + [C.c_void_p] * 4
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            try:
+                fn = getattr(l, name)
+            except AttributeError:
+                raise GeoSplatHipError(f"{LIB_PATH} does not export {name}, which {HEADER_PATH} declares: rebuild the library") from None
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 

@@ -446,7 +446,7 @@ class RenderStep:
         # final, so their all-reduce (RCCL on the communication stream) overlaps the prefilter backward
         if tail_job is None:
             with torch.cuda.stream(pstream if pstream is not None else main):
-                L.check(lib.gs_activation_chain(L.i64(N), L.ptr(g_scales_act), L.ptr(scales_act), L.ptr(g_opac_act), L.ptr(opac_act),
+                L.check(lib.gs_activation_chain(N, L.ptr(g_scales_act), L.ptr(scales_act), L.ptr(g_opac_act), L.ptr(opac_act),
                                                 L.ptr(b["scales"]), L.ptr(b["opacities"]), st()), "gs_activation_chain")
             if pstream is not None:
                 for t in (scales_act, opac_act):
@@ -530,7 +530,7 @@ class RenderStep:
             with torch.cuda.stream(pstream):
                 pstream.wait_event(ev_sh)                      # (v_means: the projection half adds to what the shading half stored)
                 F.tail_multi_stage(*args, accumulate=job["accumulate"], parts=2)
-                L.check(lib.gs_activation_chain(L.i64(n1 - n0), L.ptr(sl(g_scales_act)), L.ptr(sl(scales_act)), L.ptr(sl(g_opac_act)),
+                L.check(lib.gs_activation_chain(n1 - n0, L.ptr(sl(g_scales_act)), L.ptr(sl(scales_act)), L.ptr(sl(g_opac_act)),
                                                 L.ptr(sl(opac_act)), L.ptr(b["scales"][n0:n1]), L.ptr(b["opacities"][n0:n1]), L.stream()),
                         "gs_activation_chain")
                 if ctx.smooth_grads is not None:              # the smoothing scratch of these rows, behind this chunk's shading half

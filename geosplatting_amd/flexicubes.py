@@ -12,7 +12,6 @@ kernels use the closed-form index layout, `indices` is kept for interface compat
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, replace as _dc_replace
 from typing import Optional, Tuple
 
@@ -50,7 +49,7 @@ class _Extract(torch.autograd.Function):
             raise _lib.GeoSplatHipError("resolution out of range")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         counts = torch.empty(8, dtype=torch.int64, device=dev)
-        _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), C.c_size_t(ws_bytes), _lib.ptr(counts),
+        _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),
                                            _lib.stream()), "gs_flexicubes_count")
         N, Q, K, E, nq, _, _, _ = counts.tolist()                    # the reference syncs here too (:605, :651)
         if N <= 0:                                                        # the reference asserts here (:606)
@@ -59,9 +58,8 @@ class _Extract(torch.autograd.Function):
         L_dev = torch.empty(K, device=dev)
         eps = -1.0 if sdf_eps is None else float(sdf_eps)
         _lib.check(lib.gs_flexicubes_fwd(R0, R1, R2, _lib.ptr(v), _lib.ptr(s), _lib.ptr(a), _lib.ptr(b), _lib.ptr(g),
-                                         _lib.f32(weight_scale), _lib.f32(eps), _lib.ptr(ws), C.c_size_t(ws_bytes), _lib.i64(Q),
-                                         _lib.i64(nq), _lib.i64(K), _lib.ptr(out_v), _lib.ptr(faces), _lib.ptr(L_dev),
-                                         _lib.stream()), "gs_flexicubes_fwd")
+                                         weight_scale, eps, _lib.ptr(ws), ws_bytes, Q, nq, K, _lib.ptr(out_v), _lib.ptr(faces),
+                                         _lib.ptr(L_dev), _lib.stream()), "gs_flexicubes_fwd")
         ctx.save_for_backward(v, s, a, b, g, ws, out_v)
         ctx.meta = (res, weight_scale, eps, Q, nq, K, ws_bytes, sdf.shape,
                     None if alpha is None else alpha.shape, None if beta is None else beta.shape,
@@ -82,10 +80,10 @@ class _Extract(torch.autograd.Function):
         gg = None if g is None else torch.empty_like(g)
         scratch = torch.empty(Q, 3, device=dev)
         _lib.check(_lib.lib().gs_flexicubes_bwd(R0, R1, R2, _lib.ptr(v), _lib.ptr(s), _lib.ptr(a), _lib.ptr(b), _lib.ptr(g),
-                                                _lib.f32(weight_scale), _lib.f32(eps), _lib.ptr(ws), C.c_size_t(ws_bytes),
-                                                _lib.i64(Q), _lib.i64(nq), _lib.i64(K), _lib.ptr(out_v), _lib.ptr(v_out),
-                                                _lib.ptr(v_L), _lib.ptr(scratch), _lib.ptr(gv), _lib.ptr(gs), _lib.ptr(ga),
-                                                _lib.ptr(gb), _lib.ptr(gg), _lib.stream()), "gs_flexicubes_bwd")
+                                                weight_scale, eps, _lib.ptr(ws), ws_bytes, Q, nq, K, _lib.ptr(out_v),
+                                                _lib.ptr(v_out), _lib.ptr(v_L), _lib.ptr(scratch), _lib.ptr(gv),
+                                                _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gb), _lib.ptr(gg),
+                                                _lib.stream()), "gs_flexicubes_bwd")
         rs = lambda t, shp: None if t is None else t.reshape(shp)
         return gv, gs.reshape(s_shape), rs(ga, a_shape), rs(gb, b_shape), rs(gg, g_shape), None, None, None
 
@@ -102,9 +100,9 @@ class _Entropy(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
         counts = torch.empty(8, dtype=torch.int64, device=s.device)
         out = torch.empty(1, device=s.device)
-        _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), C.c_size_t(ws_bytes), _lib.ptr(counts),
+        _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),
                                            _lib.stream()), "gs_flexicubes_count")
-        _lib.check(lib.gs_flexicubes_entropy_fwd(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), C.c_size_t(ws_bytes), _lib.ptr(out),
+        _lib.check(lib.gs_flexicubes_entropy_fwd(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes, _lib.ptr(out),
                                                  _lib.stream()), "gs_flexicubes_entropy_fwd")
         ctx.save_for_backward(s, ws)
         ctx.meta = (res, ws_bytes, sdf.shape)
@@ -115,7 +113,7 @@ class _Entropy(torch.autograd.Function):
         s, ws = ctx.saved_tensors
         (R0, R1, R2), ws_bytes, shape = ctx.meta
         gs = torch.empty_like(s)
-        _lib.check(_lib.lib().gs_flexicubes_entropy_bwd(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), C.c_size_t(ws_bytes),
+        _lib.check(_lib.lib().gs_flexicubes_entropy_bwd(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes,
                                                         _lib.ptr(v_out.reshape(1).contiguous().float()), _lib.ptr(gs), 0,
                                                         _lib.stream()), "gs_flexicubes_entropy_bwd")
         return gs.reshape(shape), None

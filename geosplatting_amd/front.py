@@ -63,11 +63,11 @@ def front_stage(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
     fr.packed_index = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if want_packed_index else None
     ws_bytes = lib.gs_front_ws_bytes(N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    L.check(lib.gs_front_fwd(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(normals), L.ptr(kd), L.ptr(ks),
-                             L.ptr(viewmat), L.ptr(K), L.ptr(cam_pos), L.f32(min_roughness), L.f32(max_metallic), mode,
-                             C.byref(env_struct) if env_struct is not None else None, W, H, tile_size, L.f32(eps2d), L.f32(near), L.f32(far), L.f32(radius_clip),
-                             C.c_uint32(int(key_base) & 0xffffffff), int(key_bits), L.ptr(fr.vis), L.ptr(fr.keys), L.ptr(fr.rects),
-                             L.ptr(fr.tile_counts), L.ptr(fr.packed_index), 1 if tight_tiles else 0, L.ptr(fr.counts), L.ptr(status), L.ptr(ws), C.c_size_t(ws_bytes), L.stream()), "gs_front_fwd")
+    L.check(lib.gs_front_fwd(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(normals), L.ptr(kd), L.ptr(ks), L.ptr(viewmat),
+                             L.ptr(K), L.ptr(cam_pos), min_roughness, max_metallic, mode, C.byref(env_struct) if env_struct is not None else None, W,
+                             H, tile_size, eps2d, near, far, radius_clip, int(key_base) & 0xffffffff, int(key_bits), L.ptr(fr.vis), L.ptr(fr.keys),
+                             L.ptr(fr.rects), L.ptr(fr.tile_counts), L.ptr(fr.packed_index), 1 if tight_tiles else 0, L.ptr(fr.counts), L.ptr(status),
+                             L.ptr(ws), ws_bytes, L.stream()), "gs_front_fwd")
     fr.host_counts = pinned_counts4()
     fr.host_counts.copy_(fr.counts, non_blocking=True)        # 32 bytes, asynchronous
     fr.event = torch.cuda.Event()
@@ -128,21 +128,21 @@ def bin_stage(fr: Front, i_cap: Optional[int], status: Optional[Tensor], prepare
     else:
         flat = torch.empty(max(I, 1), dtype=torch.int32, device=dev)
         offsets = torch.empty(th * tw, dtype=torch.int32, device=dev)
-        bin_bytes = lib.gs_isect_bin_front_ws_bytes(V, L.i64(I), tw, th)
+        bin_bytes = lib.gs_isect_bin_front_ws_bytes(V, I, tw, th)
         bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
-        L.check(lib.gs_isect_bin_front(V, L.ptr(fr.keys), L.ptr(fr.rects), L.ptr(fr.tile_counts), L.ptr(counts), L.i64(I), fr.key_bits, tw, th,
-                                       L.ptr(flat), L.ptr(offsets), L.ptr(bin_ws), C.c_size_t(bin_bytes),
-                                       L.ptr(status) if counts is not None else None, st), "gs_isect_bin_front")
+        L.check(lib.gs_isect_bin_front(V, L.ptr(fr.keys), L.ptr(fr.rects), L.ptr(fr.tile_counts), L.ptr(counts), I, fr.key_bits, tw, th,
+                                       L.ptr(flat), L.ptr(offsets), L.ptr(bin_ws), bin_bytes, L.ptr(status) if counts is not None else None,
+                                       st), "gs_isect_bin_front")
     if not prepare:
         return dict(flatten_ids=flat, isect_offsets=offsets, counts=counts, keys=fr.keys, rects=fr.rects, tile_counts=fr.tile_counts), V, I
-    rws_bytes = lib.gs_raster_ws_bytes(L.i64(I), V, W, H, tile_size)
+    rws_bytes = lib.gs_raster_ws_bytes(I, V, W, H, tile_size)
     rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
     if counts is None:
-        L.check(lib.gs_raster_prepare_vis(W, H, tile_size, 3, V, L.ptr(fr.vis), L.i64(I), L.ptr(offsets), L.ptr(flat), L.ptr(rws),
-                                          C.c_size_t(rws_bytes), st), "gs_raster_prepare_vis")
+        L.check(lib.gs_raster_prepare_vis(W, H, tile_size, 3, V, L.ptr(fr.vis), I, L.ptr(offsets), L.ptr(flat), L.ptr(rws),
+                                          rws_bytes, st), "gs_raster_prepare_vis")
     else:
-        L.check(lib.gs_raster_prepare_vis_cap(W, H, tile_size, 3, V, L.ptr(fr.vis), L.i64(I), L.ptr(counts), L.ptr(offsets), L.ptr(flat),
-                                              L.ptr(rws), C.c_size_t(rws_bytes), st), "gs_raster_prepare_vis_cap")
+        L.check(lib.gs_raster_prepare_vis_cap(W, H, tile_size, 3, V, L.ptr(fr.vis), I, L.ptr(counts), L.ptr(offsets), L.ptr(flat),
+                                              L.ptr(rws), rws_bytes, st), "gs_raster_prepare_vis_cap")
     state = dict(vis_records=fr.vis, flatten_ids=flat, isect_offsets=offsets, raster_ws=rws, counts=counts, keys=fr.keys, rects=fr.rects,
                  tile_counts=fr.tile_counts, packed_index=fr.packed_index)
     return state, V, I
@@ -157,11 +157,10 @@ def tail_stage(V: int, counts: Optional[Tensor], means: Tensor, quats: Tensor, s
     `priv`: the zeroed scratch of `tail_priv_alloc` (XCD-private copies of the mid-sized levels; fold with `tail_priv_reduce`)."""
     lib = L.lib()
     L.check(lib.gs_tail_bwd(V, L.ptr(counts), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(normals), L.ptr(kd),
-                            L.ptr(ks), L.ptr(viewmat), L.ptr(K), L.ptr(cam_pos), L.f32(min_roughness), L.f32(max_metallic), mode,
-                            C.byref(env_struct), W, H, L.f32(eps2d), L.ptr(vis), L.ptr(v_packed), int(v_packed.shape[1]),
-                            L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opacities), L.ptr(g_normals), L.ptr(g_kd),
-                            L.ptr(g_ks), C.byref(env_grad_struct), L.ptr(priv), C.c_size_t(0 if priv is None else priv.numel()),
-                            L.stream()), "gs_tail_bwd")
+                            L.ptr(ks), L.ptr(viewmat), L.ptr(K), L.ptr(cam_pos), min_roughness, max_metallic, mode,
+                            C.byref(env_struct), W, H, eps2d, L.ptr(vis), L.ptr(v_packed), int(v_packed.shape[1]), L.ptr(g_means),
+                            L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opacities), L.ptr(g_normals), L.ptr(g_kd), L.ptr(g_ks),
+                            C.byref(env_grad_struct), L.ptr(priv), 0 if priv is None else priv.numel(), L.stream()), "gs_tail_bwd")
 
 
 def tail_priv_alloc(env_struct, mode: int, device) -> Optional[Tensor]:
@@ -172,7 +171,7 @@ def tail_priv_alloc(env_struct, mode: int, device) -> Optional[Tensor]:
 
 def tail_priv_reduce(env_struct, env_grad_struct, mode: int, priv: Optional[Tensor]) -> None:
     if priv is not None:
-        L.check(L.lib().gs_tail_priv_reduce(C.byref(env_struct), mode, L.ptr(priv), C.c_size_t(priv.numel()), C.byref(env_grad_struct),
+        L.check(L.lib().gs_tail_priv_reduce(C.byref(env_struct), mode, L.ptr(priv), priv.numel(), C.byref(env_grad_struct),
                                             L.stream()), "gs_tail_priv_reduce")
 
 
@@ -193,11 +192,11 @@ def tail_multi_stage(views, means: Tensor, quats: Tensor, scales: Tensor, opacit
         arr[i].W = int(W); arr[i].H = int(H)
         assert stride in (None, int(vp.shape[1]))
         stride = int(vp.shape[1])
-    L.check(lib.gs_tail_bwd_multi_parts(int(parts), means.shape[0], len(views), arr, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(normals),
-                                  L.ptr(kd), L.ptr(ks), L.f32(min_roughness), L.f32(max_metallic), mode, C.byref(env_struct), L.f32(eps2d),
-                                  stride, L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opacities), L.ptr(g_normals), L.ptr(g_kd),
-                                  L.ptr(g_ks), 1 if accumulate else 0, C.byref(env_grad_struct), L.ptr(priv),
-                                  C.c_size_t(0 if priv is None else priv.numel()), L.stream()), "gs_tail_bwd_multi_parts")
+    L.check(lib.gs_tail_bwd_multi_parts(int(parts), means.shape[0], len(views), arr, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities),
+                                        L.ptr(normals), L.ptr(kd), L.ptr(ks), min_roughness, max_metallic, mode, C.byref(env_struct), eps2d, stride,
+                                        L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opacities), L.ptr(g_normals), L.ptr(g_kd),
+                                        L.ptr(g_ks), 1 if accumulate else 0, C.byref(env_grad_struct), L.ptr(priv),
+                                        0 if priv is None else priv.numel(), L.stream()), "gs_tail_bwd_multi_parts")
 
 
 # ------------------------------------------------------------------------------------------------------------ both drivers
@@ -268,7 +267,7 @@ def texel_grads(env, flat: Optional[Tensor] = None):
 
 def log_ws(I: int, W: int, H: int, dev: torch.device) -> Tensor:
     """The compositor's cull log of one view (what composite_fwd leaves for composite_bwd), on the current stream."""
-    return torch.empty(L.lib().gs_raster_log_ws_bytes(L.i64(I), W, H, 16), dtype=torch.uint8, device=dev)
+    return torch.empty(L.lib().gs_raster_log_ws_bytes(I, W, H, 16), dtype=torch.uint8, device=dev)
 
 
 def composite_fwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Tensor, log: Tensor):
@@ -280,9 +279,9 @@ def composite_fwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Te
     render = torch.empty(H, W, 3, dtype=f32, device=dev); alphas = torch.empty(H, W, dtype=f32, device=dev)
     last_ids = torch.empty(H, W, dtype=torch.int32, device=dev); img = torch.empty(H, W, 4, dtype=f32, device=dev)
     rws = state["raster_ws"]
-    L.check(L.lib().gs_raster_composite_tone_log(W, H, 16, V, None, L.i64(I), L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
+    L.check(L.lib().gs_raster_composite_tone_log(W, H, 16, V, None, I, L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
                                                  L.ptr(render), L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(img),
-                                                 L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(log), C.c_size_t(log.numel()), L.stream()),
+                                                 L.ptr(rws), rws.numel(), L.ptr(log), log.numel(), L.stream()),
             "gs_raster_composite_tone_log")
     return img, render, alphas, last_ids
 
@@ -291,10 +290,10 @@ def composite_bwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Te
                   last_ids: Tensor, log: Tensor, v_img: Tensor, g_exp: Tensor) -> None:
     """A6 + S4 backward on the current stream: ADDS into the view's gradient records (state["v_packed"]) and into `g_exp`."""
     rws = state["raster_ws"]
-    L.check(L.lib().gs_raster_bwd_tone_log_acc(W, H, 16, V, None, L.i64(I), L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
+    L.check(L.lib().gs_raster_bwd_tone_log_acc(W, H, 16, V, None, I, L.ptr(state["counts"]), L.ptr(state["isect_offsets"]),
                                                L.ptr(render), L.ptr(alphas), L.ptr(last_ids), tone, L.ptr(exposure), L.ptr(v_img),
-                                               L.ptr(state["v_packed"]), L.ptr(g_exp), L.ptr(rws), C.c_size_t(rws.numel()), L.ptr(log),
-                                               C.c_size_t(log.numel()), L.stream()), "gs_raster_bwd_tone_log_acc")
+                                               L.ptr(state["v_packed"]), L.ptr(g_exp), L.ptr(rws), rws.numel(), L.ptr(log),
+                                               log.numel(), L.stream()), "gs_raster_bwd_tone_log_acc")
 
 
 def smooth_view(state, V: int, I: int, W: int, H: int, kd: Tensor, ks: Tensor, normals: Tensor, bg9: Tensor, gt: Optional[Tensor],
@@ -315,20 +314,20 @@ def smooth_view(state, V: int, I: int, W: int, H: int, kd: Tensor, ks: Tensor, n
     alphas = torch.empty(H, W, dtype=torch.float32, device=dev)
     last_ids = torch.empty(H, W, dtype=torch.int32, device=dev)
     if counts is None:
-        L.check(lib.gs_raster_composite(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(offsets), L.ptr(render), L.ptr(alphas),
-                                        L.ptr(last_ids), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_composite")
+        L.check(lib.gs_raster_composite(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), I, L.ptr(offsets), L.ptr(render), L.ptr(alphas),
+                                        L.ptr(last_ids), L.ptr(rws), rws.numel(), st), "gs_raster_composite")
     else:
-        L.check(lib.gs_raster_composite_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(counts), L.ptr(offsets), L.ptr(render),
-                                            L.ptr(alphas), L.ptr(last_ids), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_composite_cap")
+        L.check(lib.gs_raster_composite_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), I, L.ptr(counts), L.ptr(offsets), L.ptr(render),
+                                            L.ptr(alphas), L.ptr(last_ids), L.ptr(rws), rws.numel(), st), "gs_raster_composite_cap")
     from .loss import smooth_loss_and_grad
     _, v_img = smooth_loss_and_grad(render, gt, kinds, weights, out=loss)
     v9 = state["v_packed9"]
     if counts is None:
-        L.check(lib.gs_raster_bwd_acc(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(offsets), L.ptr(alphas), L.ptr(last_ids),
-                                      L.ptr(v_img), L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), C.c_size_t(rws.numel()), st), "gs_raster_bwd_acc")
+        L.check(lib.gs_raster_bwd_acc(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), I, L.ptr(offsets), L.ptr(alphas), L.ptr(last_ids), L.ptr(v_img),
+                                      L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), rws.numel(), st), "gs_raster_bwd_acc")
     else:
-        L.check(lib.gs_raster_bwd_acc_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), L.i64(I), L.ptr(counts), L.ptr(offsets), L.ptr(alphas),
-                                          L.ptr(last_ids), L.ptr(v_img), L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), C.c_size_t(rws.numel()),
+        L.check(lib.gs_raster_bwd_acc_cap(W, H, 16, 9, V, L.ptr(cols), L.ptr(bg9), I, L.ptr(counts), L.ptr(offsets), L.ptr(alphas),
+                                          L.ptr(last_ids), L.ptr(v_img), L.ptr(zero_alphas), L.ptr(v9), L.ptr(rws), rws.numel(),
                                           st), "gs_raster_bwd_acc_cap")
     vp = state["v_packed"]
     L.check(lib.gs_smooth_fold(V, L.ptr(counts), L.ptr(vis), L.ptr(v9), int(v9.shape[1]), L.ptr(vp), int(vp.shape[1]), L.ptr(g_kd),

@@ -13,7 +13,6 @@ statistics are gs_densify_stats.  No CPU path.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -223,7 +222,7 @@ class GaussianSet:
         lib, dev, n = _lib.lib(), self.device, len(self)
         if n == 0:
             return torch.empty(0, dtype=torch.int64, device=dev)
-        nbytes = lib.gs_densify_ws_bytes(_lib.i64(n), int(num_splits))
+        nbytes = lib.gs_densify_ws_bytes(n, int(num_splits))
         if nbytes == 0:
             raise _lib.GeoSplatHipError(f"densify: N={n} / num_splits={num_splits} outside the supported range")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -233,10 +232,10 @@ class GaussianSet:
         stats = (None, None) if mode == MODE_CULL else (self.xys_grad_norm.float().contiguous(), self.vis_counts.float().contiguous())
         if mode == MODE_DENSIFY and (stats[0].shape != (n,) or stats[1].shape != (n,)):
             raise _lib.GeoSplatHipError("densify: xys_grad_norm / vis_counts must be [N]")
-        _lib.check(lib.gs_densify_plan(_lib.i64(n), _lib.ptr(src["scales"]), _lib.ptr(opac), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
-                                       _lib.f32(half_extent), _lib.f32(grad_thresh), _lib.f32(size_thresh), _lib.f32(alpha_thresh),
-                                       _lib.f32(-1.0 if scale_thresh is None else scale_thresh), int(num_splits), mode, _lib.ptr(ws),
-                                       C.c_size_t(nbytes), _lib.ptr(totals), _lib.stream()), "gs_densify_plan")
+        _lib.check(lib.gs_densify_plan(n, _lib.ptr(src["scales"]), _lib.ptr(opac), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                                       half_extent, grad_thresh, size_thresh, alpha_thresh,
+                                       -1.0 if scale_thresh is None else scale_thresh, int(num_splits), mode, _lib.ptr(ws), nbytes,
+                                       _lib.ptr(totals), _lib.stream()), "gs_densify_plan")
         n_sel, n_split, n_dup, n_out = (int(v) for v in totals.tolist())        # the reference's own sync (nonzero / boolean indexing)
         self.last_totals = (n_sel, n_split, n_dup, n_out)
         if mode == MODE_DENSIFY:
@@ -264,8 +263,8 @@ class GaussianSet:
         table = (_lib.GsDensifyTensor * len(rows))()
         for k, (s, d, fpr, kind) in enumerate(rows):
             table[k].src, table[k].dst, table[k].floats_per_row, table[k].kind = s.data_ptr(), d.data_ptr(), fpr, kind
-        _lib.check(lib.gs_densify_fill(_lib.i64(n), int(num_splits), _lib.ptr(ws), C.c_size_t(nbytes), _lib.i64(n_sel), _lib.i64(n_split),
-                                       _lib.i64(n_dup), table, len(rows), _lib.ptr(src["quats"]), _lib.ptr(src["scales"]),
+        _lib.check(lib.gs_densify_fill(n, int(num_splits), _lib.ptr(ws), nbytes, n_sel, n_split, n_dup, table, len(rows),
+                                       _lib.ptr(src["quats"]), _lib.ptr(src["scales"]),
                                        _lib.ptr(randn) if (randn is not None and randn.numel()) else None, _lib.ptr(indices),
                                        _lib.stream()), "gs_densify_fill")
         rg = self.requires_grad
@@ -495,7 +494,7 @@ def densify_stats(gaussian_ids: Tensor, v_means2d: Tensor, xys_grad_norm: Tensor
     if grad.shape[0] != ids.shape[0] or xys_grad_norm.shape != vis_counts.shape or xys_grad_norm.dtype != torch.float32 or \
             vis_counts.dtype != torch.float32:
         raise _lib.GeoSplatHipError("densify_stats expects ids[V], v_means2d[V,2] and fp32 xys_grad_norm[N], vis_counts[N]")
-    _lib.check(_lib.lib().gs_densify_stats(int(ids.shape[0]), _lib.ptr(ids), _lib.ptr(grad), _lib.i64(xys_grad_norm.numel()),
+    _lib.check(_lib.lib().gs_densify_stats(int(ids.shape[0]), _lib.ptr(ids), _lib.ptr(grad), xys_grad_norm.numel(),
                                            _lib.ptr(xys_grad_norm), _lib.ptr(vis_counts), _lib.stream()), "gs_densify_stats")
 
 

@@ -27,9 +27,9 @@ def _photo_loss_raw(rgb: Tensor, alpha: Tensor, gt_rgba: Tensor, train_bg: Tenso
     nbytes = _lib.lib().gs_photo_loss_ws_bytes(W, H)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=rgb.device)
     _lib.check(_lib.lib().gs_photo_loss(W, H, _lib.ptr(rgb), _lib.ptr(alpha), _lib.ptr(gt_rgba), int(bool(gt_is_srgb)),
-                                        _lib.ptr(train_bg), _lib.ptr(mb), _lib.f32(ssim_lambda), _lib.f32(mask_weight),
-                                        _lib.f32(grad_scale), _lib.ptr(out), _lib.ptr(v_rgb), _lib.ptr(v_alpha),
-                                        _lib.ptr(ws), C.c_size_t(nbytes), _lib.stream()), "gs_photo_loss")
+                                        _lib.ptr(train_bg), _lib.ptr(mb), ssim_lambda, mask_weight, grad_scale,
+                                        _lib.ptr(out), _lib.ptr(v_rgb), _lib.ptr(v_alpha), _lib.ptr(ws), nbytes,
+                                        _lib.stream()), "gs_photo_loss")
     return out, v_rgb, v_alpha
 
 
@@ -133,5 +133,5 @@ def smooth_loss_and_grad(img: Tensor, gt_rgb: Optional[Tensor], kinds, weights, 
     k = (C.c_int * 3)(*[int(x) for x in kinds])
     w = (C.c_float * 3)(*[float(x) for x in weights])
     _lib.check(l.gs_smooth_loss(W, H, _lib.ptr(img), _lib.ptr(gt), k, w, _lib.ptr(out), _lib.ptr(v_img), _lib.ptr(ws),
-                                C.c_size_t(nbytes), _lib.stream()), "gs_smooth_loss")
+                                nbytes, _lib.stream()), "gs_smooth_loss")
     return out, v_img

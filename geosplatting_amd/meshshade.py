@@ -140,7 +140,7 @@ class _ShadePixels(torch.autograd.Function):
         color = torch.empty(H, W, 3, dtype=torch.float32, device=rast.device)
         e = _make_env(lut, TextureSplitSum(base, levels, env_min_r, env_max_r))
         L.check(L.lib().gs_meshshade_fwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
-                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, L.f32(min_visibility),
+                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
                                          int(bend), L.ptr(color), L.stream()), "gs_meshshade_fwd")
         ctx.save_for_backward(position, normal, uv, rast, kd, ks, cam_pos, lut, base, *levels)
         ctx.cfg = cfg
@@ -161,7 +161,7 @@ class _ShadePixels(torch.autograd.Function):
         for i, t in enumerate(d_levels):
             eg.levels[i] = t.data_ptr()
         L.check(L.lib().gs_meshshade_bwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
-                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, L.f32(min_visibility),
+                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
                                          int(bend), L.ptr(g), L.ptr(d_position), L.ptr(d_normal), L.ptr(d_uv), L.ptr(d_kd), L.ptr(d_ks),
                                          C.byref(eg), L.stream()), "gs_meshshade_bwd")
         return (d_position, d_normal, d_uv, None, d_kd, d_ks, None, None, d_base, None, *d_levels)

@@ -7,7 +7,6 @@ for gfx950) through the C-ABI in include/geosplat_hip.h -- there is no PyTorch o
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, Optional, Tuple
 
@@ -59,18 +58,18 @@ def _project_stage(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tens
     st = L.stream()
     if sh_degree is None and not classic:
         L.check(lib.gs_project_fwd_vis(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(colors), D,
-                                       L.ptr(viewmat), L.ptr(K), W, H, tile_size, L.f32(eps2d), L.f32(near), L.f32(far),
-                                       L.f32(radius_clip), L.ptr(gids), L.ptr(radii), L.ptr(means2d), L.ptr(depths),
-                                       L.ptr(conics), L.ptr(comps), L.ptr(opac_p), L.ptr(colors_p), L.ptr(tpg), L.ptr(cum),
-                                       None, L.ptr(vis), L.ptr(ws), C.c_size_t(ws_bytes), L.ptr(counts), st), "gs_project_fwd_vis")
+                                       L.ptr(viewmat), L.ptr(K), W, H, tile_size, eps2d, near, far, radius_clip, L.ptr(gids),
+                                       L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics), L.ptr(comps), L.ptr(opac_p),
+                                       L.ptr(colors_p), L.ptr(tpg), L.ptr(cum), None, L.ptr(vis), L.ptr(ws), ws_bytes,
+                                       L.ptr(counts), st), "gs_project_fwd_vis")
     else:
         sh = sh_degree is not None
         L.check(lib.gs_project_fwd_vis_ex(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), None if sh else L.ptr(colors),
                                           D, L.ptr(colors) if sh else None, colors.shape[1] if sh else 0, -1 if not sh else sh_degree,
-                                          GS_PROJ_CLASSIC if classic else 0, L.ptr(viewmat), L.ptr(K), W, H, tile_size, L.f32(eps2d),
-                                          L.f32(near), L.f32(far), L.f32(radius_clip), L.ptr(gids), L.ptr(radii), L.ptr(means2d),
-                                          L.ptr(depths), L.ptr(conics), L.ptr(comps), L.ptr(opac_p), L.ptr(colors_p), L.ptr(tpg),
-                                          L.ptr(cum), None, L.ptr(vis), L.ptr(ws), C.c_size_t(ws_bytes), L.ptr(counts), st),
+                                          GS_PROJ_CLASSIC if classic else 0, L.ptr(viewmat), L.ptr(K), W, H, tile_size, eps2d, near,
+                                          far, radius_clip, L.ptr(gids), L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics),
+                                          L.ptr(comps), L.ptr(opac_p), L.ptr(colors_p), L.ptr(tpg), L.ptr(cum), None, L.ptr(vis),
+                                          L.ptr(ws), ws_bytes, L.ptr(counts), st),
                 "gs_project_fwd_vis_ex")
     pr = _Projected()
     pr.host_counts = _pinned_pool.pop() if _pinned_pool else torch.empty(2, dtype=torch.int64).pin_memory()
@@ -113,17 +112,17 @@ def _bin_stage(pr: _Projected, depth_channel: bool = False):
         ids = torch.empty(I, dtype=torch.int64, device=dev); flat = torch.empty(I, dtype=i32, device=dev)
         L.check(lib.gs_isect_emit(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(cum), tile_size, tw, th,
                                   L.ptr(ids), L.ptr(flat), st), "gs_isect_emit")
-        sort_bytes = lib.gs_sort_ws_bytes(L.i64(I), tw, th)
+        sort_bytes = lib.gs_sort_ws_bytes(I, tw, th)
         sort_ws = torch.empty(max(sort_bytes, 1), dtype=torch.uint8, device=dev)
-        L.check(lib.gs_isect_sort(L.i64(I), L.ptr(ids), L.ptr(flat), L.ptr(ids_s), L.ptr(flat_s), tw, th, L.ptr(sort_ws),
-                                  C.c_size_t(sort_bytes), st), "gs_isect_sort")
+        L.check(lib.gs_isect_sort(I, L.ptr(ids), L.ptr(flat), L.ptr(ids_s), L.ptr(flat_s), tw, th, L.ptr(sort_ws),
+                                  sort_bytes, st), "gs_isect_sort")
     else:                                                                        # depth-major binning (csrc/gs_sort.hip)
-        bin_bytes = lib.gs_isect_bin_ws_bytes(V, L.i64(I), tw, th)
+        bin_bytes = lib.gs_isect_bin_ws_bytes(V, I, tw, th)
         bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
-        L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), L.i64(I), tile_size, tw, th,
-                                 L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), C.c_size_t(bin_bytes), st), "gs_isect_bin")
+        L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), I, tile_size, tw, th,
+                                 L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, st), "gs_isect_bin")
     offsets = torch.empty(th * tw, dtype=i32, device=dev)
-    L.check(lib.gs_isect_offsets(L.i64(I), L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets")
+    L.check(lib.gs_isect_offsets(I, L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets")
     state = dict(gaussian_ids_i32=gids, radii=radii, means2d=means2d, depths=depths, conics=conics,
                  compensations=comps, opacities=opac_p, colors=colors_p, tiles_per_gauss=tpg, isect_ids=ids_s,
                  flatten_ids=flat_s, isect_offsets=offsets)
@@ -136,18 +135,18 @@ def _prepare_stage(state, V: int, I: int, D: int, whs):
     """A5 preparation (per-visible records, sorted record stream, tile order) on the current stream."""
     lib = L.lib()
     W, H, tile_size = whs
-    rws_bytes = lib.gs_raster_ws_bytes(L.i64(I), V, W, H, tile_size)
+    rws_bytes = lib.gs_raster_ws_bytes(I, V, W, H, tile_size)
     rws = torch.empty(rws_bytes, dtype=torch.uint8, device=state["means2d"].device)   # written here, read by fwd AND bwd
     vis = state.get("vis_records")
     if vis is not None:
-        L.check(lib.gs_raster_prepare_vis(W, H, tile_size, D, V, L.ptr(vis), L.i64(I), L.ptr(state["isect_offsets"]),
-                                          L.ptr(state["flatten_ids"]), L.ptr(rws), C.c_size_t(rws_bytes), L.stream()),
+        L.check(lib.gs_raster_prepare_vis(W, H, tile_size, D, V, L.ptr(vis), I, L.ptr(state["isect_offsets"]),
+                                          L.ptr(state["flatten_ids"]), L.ptr(rws), rws_bytes, L.stream()),
                 "gs_raster_prepare_vis")
     else:
         L.check(lib.gs_raster_prepare(W, H, tile_size, D, V, L.ptr(state["means2d"]), L.ptr(state["conics"]),
-                                      L.ptr(state["opacities"]), L.ptr(state["colors"]), L.i64(I),
+                                      L.ptr(state["opacities"]), L.ptr(state["colors"]), I,
                                       L.ptr(state["isect_offsets"]), L.ptr(state["flatten_ids"]), L.ptr(rws),
-                                      C.c_size_t(rws_bytes), L.stream()), "gs_raster_prepare")
+                                      rws_bytes, L.stream()), "gs_raster_prepare")
     return dict({k: v for k, v in state.items() if k != "vis_records"}, raster_ws=rws)
 
 
@@ -162,9 +161,9 @@ def _composite_stage(state, V: int, I: int, D: int, whs, background: Optional[Te
     rws = state["raster_ws"]
     render = torch.empty(H, W, D, dtype=f32, device=dev); alphas = torch.empty(H, W, dtype=f32, device=dev)
     last_ids = torch.empty(H, W, dtype=i32, device=dev)
-    L.check(lib.gs_raster_composite(W, H, tile_size, D, V, L.ptr(state["colors"]), L.ptr(background), L.i64(I),
+    L.check(lib.gs_raster_composite(W, H, tile_size, D, V, L.ptr(state["colors"]), L.ptr(background), I,
                                     L.ptr(state["isect_offsets"]), L.ptr(render), L.ptr(alphas), L.ptr(last_ids),
-                                    L.ptr(rws), C.c_size_t(rws.numel()), L.stream()), "gs_raster_composite")
+                                    L.ptr(rws), rws.numel(), L.stream()), "gs_raster_composite")
     state = dict(state, last_ids=last_ids)
     return render, alphas, state, V, I
 
@@ -181,21 +180,21 @@ def _bin_stage_cap(pr: _Projected, I_cap: int, status: Tensor, want_ids: bool = 
     tw, th = (W + tile_size - 1) // tile_size, (H + tile_size - 1) // tile_size
     st = L.stream()
     flat_s = torch.empty(I_cap, dtype=torch.int32, device=dev)
-    bin_bytes = lib.gs_isect_bin_ws_bytes(N, L.i64(I_cap), tw, th)
+    bin_bytes = lib.gs_isect_bin_ws_bytes(N, I_cap, tw, th)
     bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
     offsets = torch.empty(th * tw, dtype=torch.int32, device=dev)
     if want_ids:
         ids_s = torch.empty(I_cap, dtype=torch.int64, device=dev)
-        L.check(lib.gs_isect_bin_cap(N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(counts), L.i64(I_cap), tile_size, tw, th,
-                                     L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), C.c_size_t(bin_bytes), L.ptr(status), st),
+        L.check(lib.gs_isect_bin_cap(N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(counts), I_cap, tile_size, tw, th,
+                                     L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, L.ptr(status), st),
                 "gs_isect_bin_cap")
-        L.check(lib.gs_isect_offsets_cap(L.i64(I_cap), L.ptr(counts), L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets_cap")
+        L.check(lib.gs_isect_offsets_cap(I_cap, L.ptr(counts), L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets_cap")
     else:                      # the caller only composites: int32 tile ids instead of the 64-bit keys (the `isect_ids` entry holds them)
         ids_s = torch.empty(I_cap, dtype=torch.int32, device=dev)
-        L.check(lib.gs_isect_bin_tiles_cap(N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(counts), L.i64(I_cap), tile_size, tw, th,
-                                           L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), C.c_size_t(bin_bytes), L.ptr(status), st),
+        L.check(lib.gs_isect_bin_tiles_cap(N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(counts), I_cap, tile_size, tw, th,
+                                           L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, L.ptr(status), st),
                 "gs_isect_bin_tiles_cap")
-        L.check(lib.gs_isect_offsets_tiles_cap(L.i64(I_cap), L.ptr(counts), L.ptr(ids_s), tw * th, L.ptr(offsets), st),
+        L.check(lib.gs_isect_offsets_tiles_cap(I_cap, L.ptr(counts), L.ptr(ids_s), tw * th, L.ptr(offsets), st),
                 "gs_isect_offsets_tiles_cap")
     state = dict(gaussian_ids_i32=gids, radii=radii, means2d=means2d, depths=depths, conics=conics, compensations=comps,
                  opacities=opac_p, colors=colors_p, tiles_per_gauss=tpg, isect_ids=ids_s, flatten_ids=flat_s,
@@ -206,11 +205,11 @@ def _bin_stage_cap(pr: _Projected, I_cap: int, status: Tensor, want_ids: bool = 
 def _prepare_stage_cap(state, V_cap: int, I_cap: int, D: int, whs):
     lib = L.lib()
     W, H, tile_size = whs
-    rws_bytes = lib.gs_raster_ws_bytes(L.i64(I_cap), V_cap, W, H, tile_size)
+    rws_bytes = lib.gs_raster_ws_bytes(I_cap, V_cap, W, H, tile_size)
     rws = torch.empty(rws_bytes, dtype=torch.uint8, device=state["means2d"].device)
-    L.check(lib.gs_raster_prepare_vis_cap(W, H, tile_size, D, V_cap, L.ptr(state["vis_records"]), L.i64(I_cap), L.ptr(state["counts"]),
-                                          L.ptr(state["isect_offsets"]), L.ptr(state["flatten_ids"]), L.ptr(rws),
-                                          C.c_size_t(rws_bytes), L.stream()), "gs_raster_prepare_vis_cap")
+    L.check(lib.gs_raster_prepare_vis_cap(W, H, tile_size, D, V_cap, L.ptr(state["vis_records"]), I_cap, L.ptr(state["counts"]),
+                                          L.ptr(state["isect_offsets"]), L.ptr(state["flatten_ids"]), L.ptr(rws), rws_bytes,
+                                          L.stream()), "gs_raster_prepare_vis_cap")
     return dict({k: v for k, v in state.items() if k != "vis_records"}, raster_ws=rws)
 
 
@@ -221,9 +220,9 @@ def _composite_stage_cap(state, V_cap: int, I_cap: int, D: int, whs, background:
     rws = state["raster_ws"]
     render = torch.empty(H, W, D, dtype=torch.float32, device=dev); alphas = torch.empty(H, W, dtype=torch.float32, device=dev)
     last_ids = torch.empty(H, W, dtype=torch.int32, device=dev)
-    L.check(lib.gs_raster_composite_cap(W, H, tile_size, D, V_cap, L.ptr(state["colors"]), L.ptr(background), L.i64(I_cap),
+    L.check(lib.gs_raster_composite_cap(W, H, tile_size, D, V_cap, L.ptr(state["colors"]), L.ptr(background), I_cap,
                                         L.ptr(state["counts"]), L.ptr(state["isect_offsets"]), L.ptr(render), L.ptr(alphas),
-                                        L.ptr(last_ids), L.ptr(rws), C.c_size_t(rws.numel()), L.stream()), "gs_raster_composite_cap")
+                                        L.ptr(last_ids), L.ptr(rws), rws.numel(), L.stream()), "gs_raster_composite_cap")
     return render, alphas, dict(state, last_ids=last_ids)
 
 
@@ -262,12 +261,12 @@ def _project_backward(saved, cfg, st, v_packed: Tensor):
     v_depths = v_packed[:, 6 + Dc].contiguous() if depth_channel else None   # grad of the appended depth channel
     if not sh and not classic:
         L.check(lib.gs_project_bwd(N, V, Dc, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
-                                   L.ptr(K), W, H, L.f32(eps2d), L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
+                                   L.ptr(K), W, H, eps2d, L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
                                    L.ptr(st["compensations"]), L.ptr(v_packed), stride, L.ptr(v_depths), L.ptr(g_means),
                                    L.ptr(g_quats), L.ptr(g_scales), L.ptr(g_opac), L.ptr(g_colors), 0, s), "gs_project_bwd")
     else:
         L.check(lib.gs_project_bwd_ex(N, V, Dc, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
-                                      L.ptr(K), W, H, L.f32(eps2d), L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
+                                      L.ptr(K), W, H, eps2d, L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
                                       L.ptr(st["compensations"]), L.ptr(v_packed), stride, L.ptr(v_depths),
                                       L.ptr(colors) if sh else None, colors.shape[1] if sh else 0, sh_degree if sh else -1,
                                       GS_PROJ_CLASSIC if classic else 0, L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales),
@@ -286,9 +285,9 @@ def _raster_backward(W: int, H: int, tile_size: int, D: int, V: int, I: int, st,
     stride = lib.gs_raster_grad_stride(D)
     v_packed = torch.empty(V, stride, dtype=f32, device=dev)
     rws = st["raster_ws"]
-    L.check(lib.gs_raster_bwd(W, H, tile_size, D, V, L.ptr(st["colors"]), L.ptr(background), L.i64(I),
-                              L.ptr(st["isect_offsets"]), L.ptr(alphas), L.ptr(st["last_ids"]), L.ptr(v_render),
-                              L.ptr(v_alphas), L.ptr(v_packed), L.ptr(rws), C.c_size_t(rws.numel()), L.stream()), "gs_raster_bwd")
+    L.check(lib.gs_raster_bwd(W, H, tile_size, D, V, L.ptr(st["colors"]), L.ptr(background), I, L.ptr(st["isect_offsets"]),
+                              L.ptr(alphas), L.ptr(st["last_ids"]), L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_packed), L.ptr(rws),
+                              rws.numel(), L.stream()), "gs_raster_bwd")
     return v_packed
 
 

@@ -46,7 +46,7 @@ def specular_bounds(res: int, roughness: float, cutoff: float, device: torch.dev
         # (gs_specular_bounds is the kernel shaped like the reference's SpecularBoundsKernel, 0.2 s at 512^2; tests compare the two)
         nbytes = L.lib().gs_specular_bounds_ws_bytes(res)
         ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-        L.check(L.lib().gs_specular_bounds_fast(res, L.f32(ct), L.ptr(dir_table(res, device)), L.ptr(b), L.ptr(ws), C.c_size_t(nbytes),
+        L.check(L.lib().gs_specular_bounds_fast(res, ct, L.ptr(dir_table(res, device)), L.ptr(b), L.ptr(ws), nbytes,
                                                 L.stream()), "gs_specular_bounds_fast")
         _bounds_cache[key] = (ct, b)
     return _bounds_cache[key]
@@ -106,8 +106,8 @@ def _build_direction(res: int, roughness: float, ct: float, bounds: Tensor, tabl
     cnt = torch.zeros(nt * ns, dtype=torch.int32, device=dev)
     ext = torch.zeros(nt * ns, 4, dtype=torch.int32, device=dev)
     pairs = torch.zeros(1, dtype=torch.int64, device=dev)
-    L.check(lib.gs_specular_tiles_count(res, L.f32(roughness), L.f32(ct), backward, margin, bw, nb, L.ptr(bounds), L.ptr(table),
-                                        L.ptr(tiles), nt, L.ptr(cnt), L.ptr(ext), L.ptr(pairs), L.stream()), "gs_specular_tiles_count")
+    L.check(lib.gs_specular_tiles_count(res, roughness, ct, backward, margin, bw, nb, L.ptr(bounds), L.ptr(table), L.ptr(tiles), nt,
+                                        L.ptr(cnt), L.ptr(ext), L.ptr(pairs), L.stream()), "gs_specular_tiles_count")
     cnt_pad = ((cnt.long() + (_ROW_PAD - 1)) // _ROW_PAD) * _ROW_PAD
     csum = torch.cumsum(cnt_pad, 0)
     row_begin = (csum - cnt_pad).contiguous()
@@ -130,8 +130,8 @@ def _build_direction(res: int, roughness: float, ct: float, bounds: Tensor, tabl
     lds_bytes = int((rh * pitch).max().item()) * 16
     desc = torch.zeros(max(total, 2 * _ROW_PAD), dtype=torch.int32, device=dev)
     weights = torch.zeros(max(total, 2 * _ROW_PAD) * 64, dtype=torch.float32, device=dev)
-    L.check(lib.gs_specular_tiles_fill(res, L.f32(roughness), L.f32(ct), backward, margin, bw, nb, L.ptr(bounds), L.ptr(table),
-                                       L.ptr(tiles), nt, L.ptr(row_begin), L.ptr(seg), L.ptr(desc), L.ptr(weights), L.stream()),
+    L.check(lib.gs_specular_tiles_fill(res, roughness, ct, backward, margin, bw, nb, L.ptr(bounds), L.ptr(table), L.ptr(tiles),
+                                       nt, L.ptr(row_begin), L.ptr(seg), L.ptr(desc), L.ptr(weights), L.stream()),
             "gs_specular_tiles_fill")
     rows_per_tile = cnt_pad.view(nt, ns).sum(-1)
     return {"cnt": cnt_pad.int().view(nt, ns).contiguous(), "row_begin": row_begin.view(nt, ns).contiguous(), "seg": seg, "desc": desc,
@@ -151,8 +151,8 @@ def _weight_sums(res: int, roughness: float, cutoff: float, device: torch.device
         ct, bounds = specular_bounds(res, roughness, cutoff, device)
         ones = torch.ones(6, res, res, 3, dtype=torch.float32, device=device)
         raw = torch.empty(6, res, res, 4, dtype=torch.float32, device=device)
-        L.check(L.lib().gs_specular_cubemap_fwd(res, L.ptr(ones), L.ptr(bounds), L.ptr(dir_table(res, device)), L.f32(roughness),
-                                                L.f32(ct), L.ptr(raw), L.stream()), "gs_specular_cubemap_fwd")
+        L.check(L.lib().gs_specular_cubemap_fwd(res, L.ptr(ones), L.ptr(bounds), L.ptr(dir_table(res, device)), roughness, ct,
+                                                L.ptr(raw), L.stream()), "gs_specular_cubemap_fwd")
         _wsum_cache[key] = raw[..., 3].contiguous()
     return _wsum_cache[key]
 
@@ -233,7 +233,7 @@ def _tiles_apply(entry: Dict, direction: str, src: Tensor, dst: Tensor, tile_beg
                                             entry["nb"], L.ptr(src), L.ptr(entry["inv_wsum"] if bwd else entry["area4"]),
                                             L.ptr(entry["area4"]) if bwd else None, L.ptr(entry["bounds"]), L.ptr(o["tiles"]),
                                             L.ptr(o["seg"]), L.ptr(o["row_begin"]), L.ptr(o["cnt"]), L.ptr(d["desc"]), L.ptr(d["weights"]),
-                                            L.ptr(dst), tile_begin, te, C.c_size_t(d["lds_bytes"]), L.stream()), "gs_specular_tiles_apply")
+                                            L.ptr(dst), tile_begin, te, d["lds_bytes"], L.stream()), "gs_specular_tiles_apply")
 
 
 MERGED_APPLY = True               # False (tests): _tiles_apply_multi launches the levels one by one
@@ -347,8 +347,8 @@ class _SpecularCubemap(torch.autograd.Function):
         R = cubemap.shape[1]
         raw = torch.empty(6, R, R, 4, dtype=torch.float32, device=cubemap.device)
         table = dir_table(R, cubemap.device)
-        L.check(L.lib().gs_specular_cubemap_fwd(R, L.ptr(cubemap), L.ptr(bounds), L.ptr(table), L.f32(roughness),
-                                                L.f32(costheta_cutoff), L.ptr(raw), L.stream()),
+        L.check(L.lib().gs_specular_cubemap_fwd(R, L.ptr(cubemap), L.ptr(bounds), L.ptr(table), roughness,
+                                                costheta_cutoff, L.ptr(raw), L.stream()),
                 "gs_specular_cubemap_fwd")
         wsum = raw[..., 3:]
         ctx.save_for_backward(bounds, wsum)
@@ -362,8 +362,8 @@ class _SpecularCubemap(torch.autograd.Function):
         v = (dout / wsum).contiguous()             # wsum does not depend on the cubemap
         g = torch.empty_like(v)
         table = dir_table(v.shape[1], v.device)
-        L.check(L.lib().gs_specular_cubemap_bwd(v.shape[1], L.ptr(bounds), L.ptr(table), L.ptr(v), L.f32(roughness), L.f32(ct),
-                                                L.ptr(g), 0, L.stream()), "gs_specular_cubemap_bwd")
+        L.check(L.lib().gs_specular_cubemap_bwd(v.shape[1], L.ptr(bounds), L.ptr(table), L.ptr(v), roughness, ct, L.ptr(g), 0,
+                                                L.stream()), "gs_specular_cubemap_bwd")
         return g, None, None, None
 
 
@@ -548,8 +548,8 @@ def as_splitsum_backward(g_base: Tensor, g_levels: List[Tensor], *, cutoff: floa
             ct, bounds = specular_bounds(res, rough, cutoff, gl.device)
             v = (gl / _weight_sums(res, rough, cutoff, gl.device).unsqueeze(-1)).contiguous()
             g_mips[i] = first if (i == 0 and first is not None) else torch.empty_like(v)
-            L.check(L.lib().gs_specular_cubemap_bwd(res, L.ptr(bounds), L.ptr(dir_table(res, gl.device)), L.ptr(v), L.f32(rough),
-                                                    L.f32(ct), L.ptr(g_mips[i]), 0, L.stream()), "gs_specular_cubemap_bwd")
+            L.check(L.lib().gs_specular_cubemap_bwd(res, L.ptr(bounds), L.ptr(dir_table(res, gl.device)), L.ptr(v), rough, ct,
+                                                    L.ptr(g_mips[i]), 0, L.stream()), "gs_specular_cubemap_bwd")
     if out is not None and g_mips[0] is not out:
         out.copy_(g_mips[0]); g_mips[0] = out
     return _mip_chain_backward(g_mips, g_base)

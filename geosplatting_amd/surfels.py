@@ -57,10 +57,10 @@ def _project_bin(means, quats, scales, opacities, colors, viewmat, K, W, H, tile
     st = L.stream()
     L.check(lib.gs_surfel_project_fwd(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), None if sh else L.ptr(colors), Dc,
                                       L.ptr(colors) if sh else None, colors.shape[1] if sh else 0, sh_degree if sh else -1,
-                                      1 if depth_channel else 0, L.ptr(viewmat), L.ptr(K), W, H, tile_size, L.f32(near), L.f32(far),
-                                      L.f32(radius_clip), L.ptr(gids), L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(rt),
-                                      L.ptr(normals), L.ptr(opac_p), L.ptr(colors_p), L.ptr(tpg), L.ptr(ws), C.c_size_t(ws_bytes),
-                                      L.ptr(counts), st), "gs_surfel_project_fwd")
+                                      1 if depth_channel else 0, L.ptr(viewmat), L.ptr(K), W, H, tile_size, near, far, radius_clip,
+                                      L.ptr(gids), L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(rt), L.ptr(normals),
+                                      L.ptr(opac_p), L.ptr(colors_p), L.ptr(tpg), L.ptr(ws), ws_bytes, L.ptr(counts),
+                                      st), "gs_surfel_project_fwd")
     V, I = (int(x) for x in counts.tolist())                 # the one host sync of the forward, where upstream has its own
     if V < 0 or V > N or I < 0 or I >= 2 ** 31:
         raise L.GeoSplatHipError(f"bad intersection count V={V} I={I}")
@@ -68,12 +68,12 @@ def _project_bin(means, quats, scales, opacities, colors, viewmat, K, W, H, tile
     opac_p, colors_p, tpg = opac_p[:V], colors_p[:V], tpg[:V]
     tw, th = (W + tile_size - 1) // tile_size, (H + tile_size - 1) // tile_size
     ids_s = torch.empty(I, dtype=torch.int64, device=dev); flat_s = torch.empty(I, dtype=i32, device=dev)
-    bin_bytes = lib.gs_isect_bin_ws_bytes(V, L.i64(I), tw, th)
+    bin_bytes = lib.gs_isect_bin_ws_bytes(V, I, tw, th)
     bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
-    L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), L.i64(I), tile_size, tw, th, L.ptr(ids_s),
-                             L.ptr(flat_s), L.ptr(bin_ws), C.c_size_t(bin_bytes), st), "gs_isect_bin")
+    L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), I, tile_size, tw, th, L.ptr(ids_s),
+                             L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, st), "gs_isect_bin")
     offsets = torch.empty(th * tw, dtype=i32, device=dev)
-    L.check(lib.gs_isect_offsets(L.i64(I), L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets")
+    L.check(lib.gs_isect_offsets(I, L.ptr(ids_s), tw * th, L.ptr(offsets), st), "gs_isect_offsets")
     return dict(gaussian_ids_i32=gids, radii=radii, means2d=means2d, depths=depths, ray_transforms=rt, normals=normals,
                 opacities=opac_p, colors=colors_p, tiles_per_gauss=tpg, isect_ids=ids_s, flatten_ids=flat_s, isect_offsets=offsets,
                 V=V, I=I, C=Cn, Dc=Dc)
@@ -133,7 +133,7 @@ def _raster_fwd(st, background, W, H, tile_size, depth_channel, distloss):
     final_D = torch.empty(H, W, dtype=f32, device=dev) if distloss else None
     L.check(lib.gs_surfel_raster_fwd(W, H, tile_size, Cn, 1 if depth_channel else 0, 1 if distloss else 0, V,
                                      L.ptr(st["ray_transforms"]), L.ptr(st["means2d"]), L.ptr(st["opacities"]), L.ptr(st["colors"]),
-                                     L.ptr(st["normals"]), L.ptr(background), L.i64(I), L.ptr(st["isect_offsets"]),
+                                     L.ptr(st["normals"]), L.ptr(background), I, L.ptr(st["isect_offsets"]),
                                      L.ptr(st["flatten_ids"]), L.ptr(render), L.ptr(alphas), L.ptr(normals), L.ptr(distort),
                                      L.ptr(median), L.ptr(last_ids), L.ptr(final_T), L.ptr(final_D), L.stream()),
             "gs_surfel_raster_fwd")
@@ -151,7 +151,7 @@ def _raster_bwd(st, background, W, H, tile_size, depth_channel, distloss, last_i
     v_densify = torch.empty(V, 2, dtype=f32, device=dev)
     L.check(lib.gs_surfel_raster_bwd(W, H, tile_size, Cn, 1 if depth_channel else 0, 1 if distloss else 0, V, L.ptr(st["ray_transforms"]),
                                      L.ptr(st["means2d"]), L.ptr(st["opacities"]), L.ptr(st["colors"]), L.ptr(st["normals"]),
-                                     L.ptr(st["depths"]), L.ptr(background), L.i64(I), L.ptr(st["isect_offsets"]), L.ptr(st["flatten_ids"]),
+                                     L.ptr(st["depths"]), L.ptr(background), I, L.ptr(st["isect_offsets"]), L.ptr(st["flatten_ids"]),
                                      L.ptr(last_ids), L.ptr(final_T), L.ptr(final_D), L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_normals),
                                      L.ptr(v_distort), L.ptr(v_packed), L.ptr(v_densify), L.stream()),
             "gs_surfel_raster_bwd")
