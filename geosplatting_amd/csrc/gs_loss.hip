@@ -17,6 +17,12 @@
 //           dL/dx = G*(dmu) + 2x G*(dExx) + y G*(dExy) + L1 term;  v_rgb = dL/dx, v_alpha = -bg . dL/dx + mask term;
 //   finalize: one block sums the partials in a fixed order in double (deterministic).
 // HBM-bound: ~28 B/px read + 36 B/px map write (pass 1), 36+28 B/px read + 16 B/px write (pass 2).
+// Conditioning: the variances are formed as E[xx] - mu^2 and compared with c2 = 9e-4.  On an opaque, bright, smooth render
+// (mu^2 ~ 0.8, variance <= 1e-5: a nearly converged view) the difference keeps a few float32 roundings of 0.8, which no float32
+// evaluation of this formula survives: tests/test_gpu_loss_budget.py, tier B, measures per gradient element 0.01 ... 1.2 times
+// "1e-4 of the sum of absolute contributions" for this kernel and 1.0 ... 1.5 times for torch's float32 evaluation on the CPU
+// (loss value: 5e-5 ... 5e-4 against 6e-4 ... 2e-3 relative).  A pivoted form (accumulate x - c, y - c around a per-image
+// constant) would remove the cancellation; it is NOT built: a change of formulation with its own benchmark question.
 #include "gs_common.h"
 
 #define LT 16

@@ -37,7 +37,10 @@ def test_loss_golden():
 @pytest.mark.parametrize("H,W,srgb,mask_loss", [(40, 56, True, True), (67, 33, False, True), (128, 128, True, False),
                                                  (11, 11, True, True)])
 def test_loss_value_and_gradient_vs_float64(H, W, srgb, mask_loss):
-    """tolerance (north star): 1e-4 relative on the value and on the gradient (relative to its max)"""
+    """1e-4 relative on the value and on the gradient in max-norm (relative to its largest element), on textured, noisy inputs with
+    local variances of 1e-2 and more.  It is no property of a float32 evaluation of the formula on a smooth, bright, opaque render,
+    where E[xx] - mu^2 cancels against c2: there torch's own float32 evaluation misses it by two orders of magnitude.  The per-element
+    bound, the shapes at the tile edges and that regime are in tests/test_gpu_loss_budget.py."""
     from geosplatting_amd.loss import photo_loss
     rgb, alpha, gt, bg = _case(H, W, H * 1000 + W, srgb)
     rc = rgb.cuda().requires_grad_(True); ac = alpha.cuda().requires_grad_(True)

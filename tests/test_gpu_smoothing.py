@@ -67,6 +67,60 @@ def test_smooth_loss_kernel_matches_torch(cuda, H, W):
         assert abs(float(acc) - 1.0 - got) <= 1e-6 * max(1.0, got)
 
 
+def _abs_scale(img, gt, kinds, weights):
+    """per element of d(sum)/d(img): the float64 sum of the absolute stencil contributions -- edge-aware: the reference's backward with
+    the absolute Sobel cotangents |sign(S(r))| exp(-|S(gt)|) w / (3 H W) through the absolute stencil weights (replicate padding as in
+    the forward); TV: gscale (|up| + |dn|) + gscale_x (|lf| + |rt|) with the forward differences around the element"""
+    from geosplatting_amd.loss import SMOOTH_EDGE, SMOOTH_TV
+    from geosplatting_amd.stage1 import spatial_gradient
+    H, W = img.shape[0], img.shape[1]
+    S = torch.zeros_like(img)
+    kx = torch.tensor([[1.0, 0.0, 1.0], [2.0, 0.0, 2.0], [1.0, 0.0, 1.0]], dtype=img.dtype) / 8.0
+    k_abs = torch.stack((kx, kx.t()))[:, None]
+    for i, (k, w) in enumerate(zip(kinds, weights)):
+        r = img[..., 3 * i: 3 * i + 3]
+        if k == SMOOTH_EDGE:
+            cot = (spatial_gradient(r) != 0).double() * (-spatial_gradient(gt).abs()).exp() * (w / (3.0 * H * W))      # [3,2,H,W]
+            z = torch.zeros(3, 1, H, W, dtype=img.dtype, requires_grad=True)
+            y = torch.nn.functional.conv2d(torch.nn.functional.pad(z, (1, 1, 1, 1), mode="replicate"), k_abs)
+            (y * cot).sum().backward()
+            S[..., 3 * i: 3 * i + 3] = z.grad[:, 0].permute(1, 2, 0)
+        elif k == SMOOTH_TV:
+            dy, dx = (r[1:] - r[:-1]).abs(), (r[:, 1:] - r[:, :-1]).abs()
+            s = torch.zeros_like(r)
+            gy, gx = 2.0 * w / (3.0 * (H - 1) * W), 2.0 * w / (3.0 * H * (W - 1))
+            s[:-1] += gy * dy; s[1:] += gy * dy                     # |dn| of the upper pixel, |up| of the lower one
+            s[:, :-1] += gx * dx; s[:, 1:] += gx * dx
+            S[..., 3 * i: 3 * i + 3] = s
+    return S
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (2, 17), (3, 3), (16, 16), (17, 17), (17, 33)])
+def test_smooth_loss_kernel_per_element(cuda, H, W):
+    """the smallest images the entry accepts and images whose replicate-padded halo clamps on both sides inside one tile: every
+    gradient element within 1e-5 of the float64 sum of the absolute stencil contributions to it (not of the image's largest
+    gradient), exact zeros where the reference has exact zeros"""
+    from geosplatting_amd.loss import SMOOTH_EDGE as E, SMOOTH_NONE as N, SMOOTH_TV as T, smooth_loss_and_grad
+    g = torch.Generator().manual_seed(H * 1000 + W)
+    img = _quantised((H, W, 9), g)
+    gt = _quantised((H, W, 3), g, flat_value=0.25)
+    cases = [((E, E, E), (0.0, 0.7, 0.3)), ((E, E, E), (1.5, 0.0, 0.3)), ((E, E, E), (1.5, 0.7, 0.0)),
+             ((T, T, N), (2.0, 1.0, 0.0)), ((T, T, E), (2.0, 1.0, 0.4))]
+    for kinds, weights in cases:
+        kinds = tuple(k if w > 0 else N for k, w in zip(kinds, weights))
+        want, want_g = _reference(img, gt, kinds, weights)
+        S = _abs_scale(img, gt, kinds, weights)
+        assert (want_g.abs() <= S * (1 + 1e-12)).all()
+        out, v = smooth_loss_and_grad(img.float().to(cuda), gt.float().to(cuda) if E in kinds else None, kinds, weights)
+        got_g = v.double().cpu()
+        assert abs(float(out) - want) <= 1e-5 * abs(want), (kinds, weights, float(out), want)
+        err = (got_g - want_g).abs()
+        frac = torch.where(S > 0, err / S.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+        print(f"\n  {H}x{W} {kinds} {weights}: largest fraction of 1e-5 S {float(frac.max()) / 1e-5:.4f}; exact zeros {int((want_g == 0).sum())}")
+        assert float(frac.max()) <= 1e-5, (kinds, weights, float(frac.max()))
+        assert (got_g[want_g == 0] == 0).all(), (kinds, weights)
+
+
 def _step_scene(dev):
     import geosplatting_amd.synthetic as syn
     from geosplatting_amd.cameras import orbit_cameras
