@@ -47,11 +47,19 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == bilateral_denoiser (rfstudio/graphics/_mesh/_optix/ops.py:107-140, c_src/denoising.cu) with
                                              1..8 channels, and RenderableAttrs.splat_mc_deferred (rfstudio/model/geosplat.py:247-376):
                                              the 14-channel G-buffer, per-pixel env_shade, the filter, the residual light
+  envmap.EnvCubeMap / cube_to_latlng / latlng_to_cube / sample_cubemap / render_background / blend_background / load_hdr /
+  save_hdr / relight_sequence, LatLngEnvMap.as_cubemap / visualize, the frame methods of both maps
+                                          == TextureCubeMap.as_latlng / sample / render / visualize, TextureLatLng.as_cubemap and the
+                                             frame transforms z_up_to_y_up_ / y_up_to_z_up_ / rotateX_ / rotateY_ / rotateZ_
+                                             (rfstudio/graphics/_mesh/_texture.py:307-503): a stage-1 cube map becomes the stage-2
+                                             lat-long light and back, and the relighting loop of tests/model/test_geosplat_defer.py:303-334
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
 from .cameras import Camera, intrinsic_matrix, lookat_c2w, orbit_cameras, sphere_cameras, view_matrix  # noqa: F401
 from .denoise import bilateral_denoiser, filter_radius  # noqa: F401
+from .envmap import (EnvCubeMap, blend_background, cube_to_latlng, latlng_to_cube, load_hdr, relight_sequence,  # noqa: F401
+                     render_background, sample_cubemap, save_hdr)
 from .envshade import LatLngEnvMap, env_shade, make_perms  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401

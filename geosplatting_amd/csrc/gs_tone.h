@@ -29,3 +29,11 @@ __device__ __forceinline__ float tone_grad(int mode, float rgb)
     }
     return 1.0f;
 }
+
+// rgb2srgb of PBRImages (rfstudio/graphics/_images.py:165-182): the same piecewise curve the photometric loss applies for its sRGB
+// metric (gs_loss.hip: linear_to_srgb), here for the environment background (gs_envmap.hip).
+__device__ __forceinline__ float tone_rgb2srgb(float c)
+{
+#pragma clang fp contract(off)
+    return c <= 0.0031308f ? c * 12.92f : powf(fmaxf(c, 0.0031308f), 1.0f / 2.4f) * 1.055f - 0.055f;
+}

@@ -14,20 +14,93 @@ from torch import Tensor
 from . import _lib
 from .raytrace import MeshBVH
 
-__all__ = ["LatLngEnvMap", "make_perms", "env_shade", "BSDF_NAMES"]
+__all__ = ["LatLngEnvMap", "make_perms", "env_shade", "BSDF_NAMES", "require_baked"]
 
 BSDF_NAMES = ("pbr", "diffuse", "white")            # the order is the kernel's encoding
 
 
-class LatLngEnvMap:
-    """A lat-long radiance map ``data`` [H,W,3] with the sampling tables of ``TextureLatLng``: after ``compute_pdf_()``,
-    ``pdf`` is [H,W,3] = stack(pdf, rows, cols) and the shader takes ``pdf[..., 0]``, ``pdf[:, 0, 1]`` and ``pdf[..., 2]``."""
+# The frame changes of TextureCubeMap / TextureLatLng (rfstudio/graphics/_mesh/_texture.py:307-357): the reference's matrices, composed
+# as ``new @ old``.  `EnvCubeMap` (envmap.py) shares them.
+def frame_z_up_to_y_up() -> Tensor:
+    return torch.tensor([[0.0, -1.0, 0.0], [0.0, 0.0, 1.0], [-1.0, 0.0, 0.0]])
 
-    def __init__(self, data: Tensor):
+
+def frame_y_up_to_z_up() -> Tensor:
+    return torch.tensor([[0.0, 0.0, -1.0], [-1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+
+
+def frame_rotation(axis: str, rad: float) -> Tensor:
+    """Rotation by ``rad`` about 'x', 'y' or 'z' in float32, as get_rotation_from_axis_angle builds it (Rodrigues):
+    cos I + (1 - cos) a a^T + sin [a]x."""
+    x, y, z = (1.0 if k == "xyz".index(axis) else 0.0 for k in range(3))
+    a = torch.tensor([x, y, z])
+    cos, sin = torch.tensor(float(rad)).cos(), torch.tensor(float(rad)).sin()
+    skew = torch.tensor([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+    return cos * torch.eye(3) + (1 - cos) * (a[:, None] @ a[None, :]) + sin * skew
+
+
+def compose_transform(new: Tensor, old: Optional[Tensor]) -> Tensor:
+    """``new @ old`` (the reference's order: the latest frame change is applied last), on old's device"""
+    if old is None:
+        return new
+    return new.to(old.device) @ old
+
+
+class _FrameMethods:
+    """the frame methods of TextureCubeMap / TextureLatLng, in place on ``self.transform``"""
+    transform: Optional[Tensor]
+
+    def _compose(self, new: Tensor):
+        self.transform = compose_transform(new.to(self.data.device), self.transform)
+        return self
+
+    def z_up_to_y_up_(self):
+        return self._compose(frame_z_up_to_y_up())
+
+    def y_up_to_z_up_(self):
+        return self._compose(frame_y_up_to_z_up())
+
+    def rotateX_(self, rad: float):
+        return self._compose(frame_rotation("x", rad))
+
+    def rotateY_(self, rad: float):
+        return self._compose(frame_rotation("y", rad))
+
+    def rotateZ_(self, rad: float):
+        return self._compose(frame_rotation("z", rad))
+
+
+class LatLngEnvMap(_FrameMethods):
+    """A lat-long radiance map ``data`` [H,W,3] with the sampling tables of ``TextureLatLng``: after ``compute_pdf_()``,
+    ``pdf`` is [H,W,3] = stack(pdf, rows, cols) and the shader takes ``pdf[..., 0]``, ``pdf[:, 0, 1]`` and ``pdf[..., 2]``.
+    ``transform`` [3,3] (default None) is the frame the texels are stored in, changed by the frame methods; the shaders take a map
+    without one: bake it with ``as_cubemap(...).as_latlng(..., apply_transform=True)``."""
+
+    def __init__(self, data: Tensor, transform: Optional[Tensor] = None):
         if data.ndim != 3 or data.shape[-1] != 3 or data.shape[0] < 2 or data.shape[1] < 2:
             raise ValueError(f"data must be [H,W,3] with H, W >= 2, got {tuple(data.shape)}")
+        if transform is not None and tuple(transform.shape) != (3, 3):
+            raise ValueError(f"transform must be [3,3], got {tuple(transform.shape)}")
         self.data = data
         self.pdf: Optional[Tensor] = None
+        self.transform = transform
+
+    def clone(self) -> "LatLngEnvMap":
+        out = LatLngEnvMap(self.data.clone(), None if self.transform is None else self.transform.clone())
+        out.pdf = None if self.pdf is None else self.pdf.clone()
+        return out
+
+    def as_cubemap(self, resolution: int):
+        """TextureLatLng.as_cubemap -> `EnvCubeMap` [6,R,R,3]; the transform is carried over.  Differentiable in ``data``."""
+        from .envmap import EnvCubeMap, latlng_to_cube
+        return EnvCubeMap(latlng_to_cube(self.data, resolution), transform=self.transform)
+
+    def visualize(self) -> Tensor:
+        """The light as a lat-long picture in the world frame: ``data`` itself without a transform, otherwise resampled through a
+        cube map of max(W, H)^2 faces with the transform applied, as the reference does."""
+        if self.transform is None:
+            return self.data
+        return self.as_cubemap(max(self.width, self.height)).visualize(width=self.width, height=self.height)
 
     @property
     def height(self) -> int:
@@ -60,6 +133,13 @@ class LatLngEnvMap:
         if self.pdf is None:
             self.compute_pdf_()
         return self.pdf[..., 0], self.pdf[:, 0, 1], self.pdf[..., 2]
+
+
+def require_baked(envmap, who: str) -> None:
+    """The shaders look a lat-long map up in its own frame (the reference asserts ``envmap.transform is None``)"""
+    if getattr(envmap, "transform", None) is not None:
+        raise ValueError(f"{who} needs a lat-long map without a transform: bake it with "
+                         "as_cubemap(...).as_latlng(..., apply_transform=True)")
 
 
 def make_perms(n_samples_x: int, device, tables: int = 32768, generator: Optional[torch.Generator] = None) -> Tensor:
@@ -141,12 +221,14 @@ def _rows3(name: str, t: Tensor, P: Optional[int], last: int = 3) -> Tensor:
 
 
 def env_shade(bvh: MeshBVH, mask: Tensor, ro: Tensor, gb_pos: Tensor, gb_normal: Tensor, gb_view_pos: Tensor, gb_kd: Tensor,
-              gb_ks: Tensor, light: Tensor, pdf: Tensor, rows: Tensor, cols: Tensor, BSDF: str = "pbr", n_samples_x: int = 8,
+              gb_ks: Tensor, light, pdf: Optional[Tensor] = None, rows: Optional[Tensor] = None, cols: Optional[Tensor] = None,
+              BSDF: str = "pbr", n_samples_x: int = 8,
               rnd_seed: Optional[int] = None, shadow_scale: float = 1.0, *, perms: Optional[Tensor] = None,
               return_samples: bool = False, lanes_per_point: int = 0, merge_rounds: int = -1):
     """``optix_env_shade`` on a `MeshBVH` -> (diff, spec, resi): the diffuse and specular irradiance sums [..,3] and the shadowed
     share of both [..,2], zero where ``mask <= 0``, in the shape family of the inputs ([1,1,N,.] as the reference passes them, or flat
-    [N,.]).  ``light`` [H,W,3] with its tables ``pdf`` [H,W], ``rows`` [H], ``cols`` [H,W] (`LatLngEnvMap.tables`); ``gb_ks`` is
+    [N,.]).  ``light`` [H,W,3] with its tables ``pdf`` [H,W], ``rows`` [H], ``cols`` [H,W] (`LatLngEnvMap.tables`), or a `LatLngEnvMap`
+    alone (its data and tables; ValueError while it carries a transform); ``gb_ks`` is
     (occlusion factor, roughness, metallic); ``BSDF`` is 'pbr', 'diffuse' or 'white'.
 
     Differentiable in gb_pos, gb_normal, gb_kd, gb_ks and light; ``resi`` carries no gradient.  The forward is deterministic for a
@@ -159,6 +241,13 @@ def env_shade(bvh: MeshBVH, mask: Tensor, ro: Tensor, gb_pos: Tensor, gb_normal:
     the kernel's arrangement; they change the order of sums only (scripts/envshade_bench.py measures them)."""
     if BSDF not in BSDF_NAMES:
         raise ValueError(f"BSDF must be one of {BSDF_NAMES}, got {BSDF!r}")
+    if isinstance(light, LatLngEnvMap):
+        require_baked(light, "env_shade")
+        if pdf is None and rows is None and cols is None:
+            pdf, rows, cols = light.tables()
+        light = light.data
+    if pdf is None or rows is None or cols is None:
+        raise ValueError("env_shade needs pdf, rows and cols with a light tensor (LatLngEnvMap.tables), or a LatLngEnvMap as light")
     _lib.require_cuda(mask, ro, gb_pos, gb_normal, gb_view_pos, gb_kd, gb_ks, light, pdf, rows, cols, perms)
     if not isinstance(bvh, MeshBVH):
         raise TypeError(f"bvh must be a MeshBVH, got {type(bvh).__name__}")

@@ -31,6 +31,9 @@
  *        = the pybind entry points diffuse_cubemap_fwd/bwd, specular_bounds, specular_cubemap_fwd/bwd
  *          (rfstudio/graphics/_mesh/_splitsum/c_src/torch_bindings.cpp:265-271) and _CubeMapMip
  *          (rfstudio/graphics/_mesh/_texture.py:199-226)
+ *   gs_env_cube_to_latlng_fwd/_bwd, gs_env_latlng_to_cube_fwd/_bwd, gs_cube_sample_linear_bwd, gs_env_background_fwd
+ *        = TextureCubeMap.as_latlng / sample / render and TextureLatLng.as_cubemap (rfstudio/graphics/_mesh/_texture.py:359-377,
+ *          :411-465)
  */
 #ifndef GEOSPLAT_HIP_H
 #define GEOSPLAT_HIP_H
@@ -1078,6 +1081,40 @@ int gs_denoise_fwd(int B, int H, int W, int C, int zdz_channels, const float* co
                    int tiled, float* out, float* wsum, void* stream);
 int gs_denoise_bwd(int B, int H, int W, int C, int zdz_channels, const float* nrm, const float* zdz, double sigma, int tiled,
                    const float* wsum, const float* out_grad, float* col_grad, void* stream);
+
+/* ------------------------------------------------------------------ environment resampling, relighting background ------------- */
+/* What the reference gets from TextureCubeMap.as_latlng / visualize / sample / render and TextureLatLng.as_cubemap
+ * (rfstudio/graphics/_mesh/_texture.py:359-377, :411-465); a restatement of the semantics.  csrc/gs_envmap.hip; tests/envmap_ref.py
+ * states the same in float64.
+ *
+ * cube [6,R,R,3] with 1 <= R <= 4096, latlng [H,W,3] with H, W >= 2 (row 0 is the +y pole: rows run y-DOWN), all fp32.
+ * Cube lookups are the seam-aware bilinear lookup of gs_cube_sample_linear (csrc/gs_cube.h: edge taps re-projected onto the
+ * neighbouring face, the missing corner tap the mean of the other three, zeros for a zero or non-finite direction; the length of the
+ * direction does not matter).  The lat-long lookup is gs_tex2d_fwd's with GS_TEX_WRAP: texel centres at u W - 0.5, wrapped in both axes.
+ * transform: DEVICE pointer to 9 floats, row-major [3,3], or NULL for the identity.  linspace(a, b, n)[k] = a + k (b - a) / (n - 1).
+ *
+ * gs_env_cube_to_latlng_fwd   out[i,j] = cube(T d), d = (sin t sin p, cos t, -sin t cos p) with t = pi linspace(1/H, 1 - 1/H, H)[i]
+ *                             (the reference's end points, not the row centres) and p = pi linspace(-1 + 1/W, 1 - 1/W, W)[j].
+ * gs_env_cube_to_latlng_bwd   d_cube [6,R,R,3] ADDED to (caller zeroes): the texel gradient of the above for d_out [H,W,3].
+ * gs_env_latlng_to_cube_fwd   out[s,y,x] = latlng(tu, tv) with g = linspace(-1 + 1/R, 1 - 1/R, R), v = normalize(face point of
+ *                             (s, g[x], g[y])), tu = atan2(v0, -v2) / (2 pi) + 0.5, tv = acos(clamp(v1, -1, 1)) / pi.
+ * gs_env_latlng_to_cube_bwd   d_latlng [H,W,3] ADDED to (caller zeroes): the texel gradient of the above for d_out [6,R,R,3].
+ * gs_cube_sample_linear_bwd   d_tex [6,R,R,3] ADDED to (caller zeroes): the texel gradient of gs_cube_sample_linear for d_out [n,3]
+ *                             (scale as in the forward).  No gradient reaches the directions.
+ * gs_env_background_fwd       out[i,j] = cube(T Rc ((0.5 - cx + j) / fx, -(0.5 - cy + i) / fy, -1)) for the [H,W] pixels of a camera;
+ *                             c2w: DEVICE pointer to 12 floats, row-major [3,4], OpenGL convention, Rc its rotation.  srgb != 0 applies
+ *                             rgb2srgb (c <= 0.0031308 ? 12.92 c : 1.055 c^(1/2.4) - 0.055) per channel, srgb == 0 leaves radiance.
+ * One thread per output element, directions in registers.  The forwards are gathers: the same inputs give the same bits.  The
+ * backwards recompute the footprint and use float atomics (sums in arrival order).  All return GS_EINVAL before touching the device
+ * for R outside 1..4096, H or W below 2 (the background: below 1), H W above 2^28, zero or non-finite intrinsics, or a null required
+ * pointer.  n == 0 is a no-op. */
+int gs_env_cube_to_latlng_fwd(int R, int H, int W, const float* cube, const float* transform, float* out, void* stream);
+int gs_env_cube_to_latlng_bwd(int R, int H, int W, const float* transform, const float* d_out, float* d_cube, void* stream);
+int gs_env_latlng_to_cube_fwd(int H, int W, int R, const float* latlng, float* out, void* stream);
+int gs_env_latlng_to_cube_bwd(int H, int W, int R, const float* d_out, float* d_latlng, void* stream);
+int gs_cube_sample_linear_bwd(int64_t n, int R, const float* dirs, float scale, const float* d_out, float* d_tex, void* stream);
+int gs_env_background_fwd(int R, int H, int W, const float* cube, float fx, float fy, float cx, float cy, const float* c2w,
+                          const float* transform, int srgb, float* out, void* stream);
 
 #ifdef __cplusplus
 }
