@@ -752,7 +752,7 @@ int gs_surfel_project_fwd(int N, const float* means, const float* quats, const f
                           int32_t* tiles_per_gauss, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
 
 /* The exact derivative of the above (radii are not differentiable).  The incoming gradients are rows of `stride` floats per visible
- * Gaussian (the columns of gs_surfel_raster_bwd's v_packed, or separate arrays with their own row length): v_ray_transforms (9),
+ * Gaussian (the columns of gs_surfel_raster_bwd's v_packed, or separate arrays that all have this one row length): v_ray_transforms (9),
  * v_means2d (2), v_depths (1, nullable), v_normals (3), v_opacities (1), v_colors (Dc).  Outputs [N, .], zero for invisible Gaussians:
  * g_means, g_quats, g_scales (third column 0), g_opacities and g_colors [N,Dc] or, with sh_degree >= 0, g_sh [N,sh_K,3]. */
 int gs_surfel_project_bwd(int N, int V, int Dc, const float* means, const float* quats, const float* scales,

@@ -93,6 +93,15 @@ BUDGET_KAPPA = 16.0          # one constant for every kernel and scene: 4.8 x th
 # correct implementation stays near or below 1 whatever the compiler does; the compositor's budget is not of that kind (its worst
 # ratio is 3.31), and sharing its 16 would leave 30 x headroom here.
 PROJ_BUDGET_KAPPA = 4.0
+# The surfel projection and the SH colours (tests/test_gpu_surfel_project_budget.py, reference and budgets in
+# tests/surfel_project_ref.py), by the same rule -- the smallest power of two that is at least 4 x the larger of (a) the float32
+# restatement against float64 on the CPU (tests/test_surfel_project_cpu.py, bar kappa / 2) and (b) the kernels on an MI355X:
+# SURFEL_PROJ_KAPPA (projection forward and backward): (a) 0.70 (ray_transforms / depths; gradients 0.55), (b) 0.85 (ray_transforms of
+# the 131 372-row compaction scene; gradients 0.64).  SH_KAPPA (SH colours and coefficient gradients): (a) 0.996, (b) 0.996 -- a
+# degree-0 colour is two roundings and a rounded literal against a bound of exactly those.  The scene builders of
+# tests/surfel_project_ref.py redraw every Gaussian with a decision margin below 2 * max(kappa) bounds.
+SURFEL_PROJ_KAPPA = 4.0
+SH_KAPPA = 4.0
 
 
 # The surfel compositor backward (tests/test_gpu_surfel_budget.py) is measured against the per-pair restatement of tests/surfel_ref.py
