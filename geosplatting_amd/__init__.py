@@ -53,6 +53,11 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              frame transforms z_up_to_y_up_ / y_up_to_z_up_ / rotateX_ / rotateY_ / rotateZ_
                                              (rfstudio/graphics/_mesh/_texture.py:307-503): a stage-1 cube map becomes the stage-2
                                              lat-long light and back, and the relighting loop of tests/model/test_geosplat_defer.py:303-334
+  geometry.PointGrid / k_nearest / k_nearest_in / chamfer_distance / sample_mesh_surface / chamfer / chamfer_fscore
+                                          == Points.k_nearest / k_nearest_in, ChamferDistance, TriangleMesh.uniformly_sample and
+                                             ChamferDistanceMetric / ChamferDistanceFscoreMetric (rfstudio/graphics/_points.py:38-67,
+                                             rfstudio/loss/_chamfer, _triangle_mesh.py:768-859, rfstudio/loss/geometric_loss.py): an exact
+                                             nearest-neighbour search on a uniform grid, the number the reference reports for a mesh
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -64,6 +69,8 @@ from .envshade import LatLngEnvMap, env_shade, make_perms  # noqa: F401
 from .field import HashEncoding, hash_encode  # noqa: F401
 from .flexicubes import FlexiCubes, get_geometry  # noqa: F401
 from .fusion import TSDFVolume, mesh_from_depth_fusion, save_obj  # noqa: F401
+from .geometry import (PointGrid, chamfer, chamfer_distance, chamfer_fscore, k_nearest, k_nearest_in,  # noqa: F401
+                       sample_mesh_surface)
 from .gsplat3d import GaussianSet, GSplatModel, GSplatTrainer, mutate_adam  # noqa: F401
 from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401

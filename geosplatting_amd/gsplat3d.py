@@ -103,15 +103,30 @@ class GaussianSet:
 
     @classmethod
     def from_points(cls, positions: Tensor, colors: Tensor, *, sh_degree: int, device=None, requires_grad: bool = False,
-                    generator: Optional[torch.Generator] = None) -> "GaussianSet":
-        """Splats.from_points (rfstudio/graphics/_splats.py:38-58)"""
+                    generator: Optional[torch.Generator] = None, knn: str = "host") -> "GaussianSet":
+        """Splats.from_points (rfstudio/graphics/_splats.py:38-58).  ``knn`` chooses where the mean distance to the three nearest
+        other points (the initial scale) is computed: 'host' (the default) is `knn_mean_distance`, a chunked float64 torch.cdist,
+        O(N^2); 'device' is `geometry.k_nearest` on the GPU (``device``, or the device of ``positions``), an exact grid search in
+        fp32.  The two differ in the last fp32 bits of the scales: float64 distances rounded once against fp32 squared distances
+        and an fp32 square root."""
+        if knn not in ("host", "device"):
+            raise ValueError(f"knn must be 'host' or 'device', got {knn!r}")
+        dist = None
+        if knn == "device":
+            from .geometry import k_nearest
+            dev = torch.device(device) if device is not None else positions.device
+            n = positions.shape[0]
+            if n < 2:
+                raise ValueError("knn='device' needs at least two points")
+            dist = k_nearest(positions.detach().float().to(dev), min(3, n - 1))[0].mean(-1).cpu()
         return cls._from_positions(positions.detach().cpu().float(), colors.detach().cpu().float(), sh_degree, device, requires_grad,
-                                   generator)
+                                   generator, dist)
 
     @classmethod
-    def _from_positions(cls, points, colors, sh_degree, device, requires_grad, generator):
+    def _from_positions(cls, points, colors, sh_degree, device, requires_grad, generator, dist=None):
         size = points.shape[0]
-        dist = knn_mean_distance(points, 3)
+        if dist is None:
+            dist = knn_mean_distance(points, 3)
         gs = cls(means=points.clone(), scales=dist[:, None].log().repeat(1, 3), quats=_random_quaternion(size, generator),
                  opacities=torch.logit(0.1 * torch.ones(size, 1)), colors=colors.clone(),
                  shs=torch.zeros(size, _sh_dim(sh_degree) - 1, 3))

@@ -1011,6 +1011,49 @@ int gs_ray_closest(int64_t V, int64_t F, const float* vertices, const int32_t* f
                    int64_t P, int S, const float* origins /*[P,3]*/, const float* dirs, int dirs_per_point, float tmin, float tmax,
                    float* t /*[P,S]*/, int32_t* face /*[P,S]*/, float* bary /*[P,S,2]*/, void* stream);
 
+/* ------------------------------------------------------------------ nearest neighbours: uniform grid, Chamfer backward ---------- */
+/* What the reference's geometry metrics get from its brute-force Chamfer kernel (rfstudio/loss/_chamfer) and from Points.k_nearest;
+ * a restatement of the semantics, and a semantics of this project's own where the reference leaves it to the hardware.
+ * csrc/gs_nn.hip; tests/chamfer_ref.py states the same in numpy.
+ *
+ * Set: points [M,3] fp32, 1 <= M <= 2^30.  Queries [N,3] fp32, 0 <= N <= 2^30.
+ * Distance (to the bit): dx = q.x - p.x, dy, dz likewise; d = (dx*dx + dy*dy) + dz*dz, every operation one fp32 round-to-nearest,
+ *   no FMA contraction.  d is the SQUARED distance and is never square-rooted here.
+ * Answer (to the bit): the lexicographically smallest pair (d, index) over the set points whose three coordinates are finite -- among
+ *   equal d the lowest index into the caller's array, whatever the traversal order.  A set point with a non-finite coordinate is
+ *   never returned.  A query with a non-finite coordinate, or a set without a finite point, gives d = +inf, index = -1.  (Two finite
+ *   points far enough apart overflow to d = +inf with a valid index.)
+ * k-nearest: dist, index [N,k], 1 <= k <= 8: the k smallest pairs in ascending order, padded with (+inf, -1).
+ * grid = NULL: every query meets every point through LDS tiles with the same distance routine.  That form defines the semantics; with
+ *   a grid the result is the same bit for bit.
+ * Grid buffer (opaque): a 256-byte header written on the device, cell starts, and one 16-byte (x, y, z, index bits) record per point
+ *   in (cell, index) order.  About M / 4 cells and at most 2^21, per-axis resolution proportional to the extent of the finite points,
+ *   one cell along an axis without extent.  The query searches Chebyshev shells of cells around the query's (clamped) cell and stops
+ *   after a shell only when the k-th best d is STRICTLY below a conservative lower bound on the fp32 d of every point outside the
+ *   searched cube, or when the cube covers the grid: a query far outside the box degrades to a scan of the set.  Every index read
+ *   from the buffer is range-checked: a buffer that holds no grid of this set gives wrong answers, not a fault or a hang.
+ *
+ *   gs_nn_grid_bytes  256 + 4 (cells + 1) + 16 M, rounded (0: M out of range)     gs_nn_ws_bytes  build workspace, about 40 M (0: same)
+ *   gs_nn_build       a full build into `grid`; rebuilding after the points moved is the same call.  Nothing is read back and no
+ *                     workgroup waits on another.
+ *   gs_nn_query       dist [N,k], index [N,k] overwritten.
+ *   gs_chamfer_bwd    the backward of (dist1, dist2) = (nearest of xyz1 in xyz2, nearest of xyz2 in xyz1) at the indices of the
+ *                     forward: with g = 2 grad1[j] and i = idx1[j], row j of grad_xyz1 gets g (xyz1[j] - xyz2[i]) and row i of
+ *                     grad_xyz2 the negative; the other direction likewise.  grad_xyz1 [N1,3] and grad_xyz2 [N2,3] are WRITTEN: every
+ *                     row is first overwritten with its own term (plain stores), the scattered terms are then added with fp32 atomics
+ *                     in a later launch -- no caller-side zeroing.  A row whose index is -1 (or outside the other set) contributes
+ *                     nothing and gets zeros as its own term.
+ * All return GS_EINVAL before touching the device for M < 1 ("empty set"), M > 2^30, k outside [1, 8], a buffer or workspace that is too
+ * small or not 16-byte aligned, negative N, or a null required pointer.  N == 0 is a no-op. */
+size_t gs_nn_grid_bytes(int64_t M);
+size_t gs_nn_ws_bytes(int64_t M);
+int gs_nn_build(int64_t M, const float* points, void* grid, size_t grid_bytes, void* ws, size_t ws_bytes, void* stream);
+int gs_nn_query(int64_t M, const float* points, const void* grid /* NULL: brute force */, int64_t N, const float* queries, int k,
+                float* dist /*[N,k]*/, int32_t* index /*[N,k]*/, void* stream);
+int gs_chamfer_bwd(int64_t N1, int64_t N2, const float* xyz1, const float* xyz2, const int32_t* idx1 /*[N1]*/,
+                   const int32_t* idx2 /*[N2]*/, const float* grad1 /*[N1]*/, const float* grad2 /*[N2]*/, float* grad_xyz1,
+                   float* grad_xyz2, void* stream);
+
 /* ------------------------------------------------------------------ Monte-Carlo environment shading on the ray routines --------- */
 /* What the reference's stage 2 gets from optix_env_shade (rfstudio/graphics/_mesh/_optix: ops.py, c_src/envsampling/kernel.cu,
  * c_src/bsdf.h); a restatement of the semantics.  csrc/gs_envshade.hip; tests/envshade_ref.py states the same in float64.
