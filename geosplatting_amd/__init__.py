@@ -58,6 +58,15 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              ChamferDistanceMetric / ChamferDistanceFscoreMetric (rfstudio/graphics/_points.py:38-67,
                                              rfstudio/loss/_chamfer, _triangle_mesh.py:768-859, rfstudio/loss/geometric_loss.py): an exact
                                              nearest-neighbour search on a uniform grid, the number the reference reports for a mesh
+  meshreg.MeshRegTopology / mesh_regularizers / laplacian_smooth_loss / mesh_edge_loss / mesh_normal_consistency
+                                          == laplacian_uniform + L.mm(v).norm(dim=1).mean(), pytorch3d.loss.mesh_edge_loss and
+                                             mesh_normal_consistency as GeoSplatterPrior.get_geometry calls them
+                                             (rfstudio/model/geosplat_prior.py:32-60, :123-136), on a topology built once
+  RenderableAttrs.splat_mc_denoised, GaussianField(occ=True), stage2.Stage2Model / PriorModel / Stage2Schedule / stage2.train_step
+                                          == splat_mc(denoise=True) (rfstudio/model/geosplat.py:192-205), the occlusion encoder,
+                                             GeoSplatterMC + GeoSplatMCTrainer and GeoSplatterPrior + GeoSplatPriorTrainer
+                                             (rfstudio/model/geosplat_mc.py, geosplat_prior.py, rfstudio/trainer/geosplat_mc_trainer.py,
+                                             geosplat_prior_trainer.py): stage-2 training on a stage-1 export or on a mesh
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -76,10 +85,13 @@ from .loss import photo_loss  # noqa: F401
 from .mesh import mesh_to_splats, vertex_normals  # noqa: F401
 from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topology, rasterize_mesh, render_mesh,  # noqa: F401
                          silhouette_loss, visible_faces)
+from .meshreg import (MeshRegTopology, laplacian_smooth_loss, mesh_edge_loss, mesh_normal_consistency,  # noqa: F401
+                      mesh_regularizers)
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .raytrace import MeshBVH, shadow_visibility  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
+from .stage2 import PriorModel, Stage2Model, Stage2Schedule  # noqa: F401
 from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401
 from . import viewbatch  # noqa: F401
 from .splitsum import TextureSplitSum, as_splitsum, diffuse_cubemap, specular_cubemap  # noqa: F401

@@ -240,20 +240,36 @@ def quaternions_from_rotations(R: Tensor) -> Tensor:
     return q.reshape(*R.shape[:-2], 4)
 
 
+def face_offsets(vertices: Tensor, faces: Tensor) -> Tensor:
+    """The offsets MGAdapter.make returns next to its splats: face normal times sqrt(face area), detached, for each of the six
+    Gaussians of a face -> [6F,3]"""
+    with torch.no_grad():                                      # MGAdapter.make: offsets = n.detach() * sqrt(area.detach())
+        p = vertices[faces]
+        fn = torch.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], dim=-1)
+        ln = fn.norm(dim=-1, keepdim=True)
+        area = ln.clamp(min=1e-10) / 2
+        n = torch.where(ln < 1e-6, torch.tensor([0.0, 0.0, 1.0], device=fn.device), fn / ln.clamp_min(1e-6))
+        return (n * area.sqrt()).repeat(6, 1)
+
+
 class GaussianField:
     """Mirror of rfstudio's GaussianField (rfstudio/model/geosplat.py:482-520) with its three default encoders and of
     `get_gaussians_from_face` (:620-672, the MGAdapter branch used by GeoSplatter): mesh -> Gaussians, with kd / ks
     from the hash-grid field at the Gaussian centres and a learned offset of the centres against the face normal.
     Every stage is a HIP op of this package (vertex normals, MGAdapter, hash encoding) or a library GEMM."""
 
-    def __init__(self, device="cuda", log2_hashmap_size: int = 18, max_res: int = 4096, seed: int = 0):
+    def __init__(self, device="cuda", log2_hashmap_size: int = 18, max_res: int = 4096, seed: int = 0, occ: bool = False):
         common = dict(max_res=max_res, log2_hashmap_size=log2_hashmap_size, grad_scaling=16.0, device=device)
         self.kd_enc = HashEncoding([-1, 32, 32, 3], activation="sigmoid", seed=seed, **common)
         self.ks_enc = HashEncoding([-1, 32, 2], activation="none", seed=seed + 1, **common)
         self.z_enc = HashEncoding([-1, 32, 1], activation="none", seed=seed + 2, **common)
+        # the occlusion encoder of the stage-2 fields (rfstudio/model/geosplat_mc.py, geosplat_prior.py: `occ_enc`, six raw channels
+        # behind the residual light sigmoid(occ - 3)); a seed of its own, so that the three encoders above keep their bits
+        self.occ_enc = HashEncoding([-1, 32, 32, 6], activation="none", seed=seed + 3, **common) if occ else None
 
     def parameters(self) -> List[Tensor]:
-        return self.kd_enc.parameters() + self.ks_enc.parameters() + self.z_enc.parameters()
+        occ = [] if self.occ_enc is None else self.occ_enc.parameters()
+        return self.kd_enc.parameters() + self.ks_enc.parameters() + self.z_enc.parameters() + occ
 
     def get_gaussians_from_vertex(self, vertices: Tensor, faces: Tensor, kd_perturb_std: float = 0.0, ks_perturb_std: float = 0.0, *,
                                   scale: float, initial_guess: Tensor, generator: Optional[torch.Generator] = None):
@@ -289,13 +305,7 @@ class GaussianField:
         from .shading import RenderableAttrs
         from .splats import SplatSet
         splats, shading_normals = mesh_to_splats(vertices, faces, vertex_normals(vertices, faces))
-        with torch.no_grad():                                  # MGAdapter.make: offsets = n.detach() * sqrt(area.detach())
-            p = vertices[faces]
-            fn = torch.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], dim=-1)
-            ln = fn.norm(dim=-1, keepdim=True)
-            area = ln.clamp(min=1e-10) / 2
-            n = torch.where(ln < 1e-6, torch.tensor([0.0, 0.0, 1.0], device=fn.device), fn / ln.clamp_min(1e-6))
-            offsets = (n * area.sqrt()).repeat(6, 1)
+        offsets = face_offsets(vertices, faces)
         means = (splats.means / scale).clamp(-1, 1)
         offsets = offsets * self.z_enc(means.detach()).sigmoid()
         shifted = splats.means - offsets
@@ -305,5 +315,5 @@ class GaussianField:
         if ks_perturb_std > 0:
             ks_jitter = (self.ks_enc((means + torch.randn(means.shape, device=means.device, generator=generator) * ks_perturb_std).clamp(-1, 1)) + initial_guess).sigmoid()
         attrs = RenderableAttrs(kd=self.kd_enc(means), ks=(self.ks_enc(means) + initial_guess).sigmoid(), normals=shading_normals,
-                                kd_jitter=kd_jitter, ks_jitter=ks_jitter)
+                                occ=None if self.occ_enc is None else self.occ_enc(means), kd_jitter=kd_jitter, ks_jitter=ks_jitter)
         return SplatSet(shifted, splats.scales, splats.quats, splats.opacities, splats.colors), attrs, offsets

@@ -55,6 +55,36 @@ def _tv(rendered: Tensor) -> Tensor:
     return (rendered[1:, :] - rendered[:-1, :]).square().mean() + (rendered[:, 1:] - rendered[:, :-1]).square().mean()
 
 
+def smoothing_regularization(model, splats, attrs, cameras: Sequence[Camera], gt_rgba: Optional[Sequence[Tensor]],
+                            batch_size: int) -> Tensor:
+    """The 'grad' / 'tv' branches and `normal_grad_weight` of render_report (:881-922): edge-aware first-order / total-variation
+    penalties on UN-shaded renders of kd, (0, ks) and normals * 0.5 + 0.5 over the model's background colour.  `model` carries
+    smooth_type, kd_grad_weight, ks_grad_weight, normal_grad_weight and background_color: the stage-1 and the stage-2 models share this."""
+    from .shading import render_rgb
+    reg = splats.means.new_zeros(())
+    need_gt = (model.smooth_type == "grad" and (model.kd_grad_weight > 0 or model.ks_grad_weight > 0)) or model.normal_grad_weight > 0
+    if need_gt and gt_rgba is None:
+        raise ValueError("smooth_type='grad' / normal_grad_weight need the ground-truth images (gt_outputs.blend(background))")
+    bg = model.background_color
+    rr = lambda colors, cam: render_rgb(splats.means, splats.scales, splats.quats, splats.opacities, colors, cam, bg)
+    gts = None if not need_gt else [g[..., :3] * g[..., 3:] + bg * (1 - g[..., 3:]) for g in gt_rgba]   # RGBAImages.blend
+    ks3 = torch.cat((torch.zeros_like(attrs.ks[..., :1]), attrs.ks), dim=-1)
+    for i, cam in enumerate(cameras):
+        if model.smooth_type == "grad":
+            if model.kd_grad_weight > 0:
+                reg = reg + _edge_aware(rr(attrs.kd, cam), gts[i]) * model.kd_grad_weight / batch_size
+            if model.ks_grad_weight > 0:
+                reg = reg + _edge_aware(rr(ks3, cam), gts[i]) * model.ks_grad_weight / batch_size
+        if model.normal_grad_weight > 0:
+            reg = reg + _edge_aware(rr(attrs.normals * 0.5 + 0.5, cam), gts[i]) * model.normal_grad_weight / batch_size
+        if model.smooth_type == "tv":
+            if model.kd_grad_weight > 0:
+                reg = reg + _tv(rr(attrs.kd, cam)) * model.kd_grad_weight / batch_size
+            if model.ks_grad_weight > 0:
+                reg = reg + _tv(rr(ks3, cam)) * model.ks_grad_weight / batch_size
+    return reg
+
+
 _INITIAL_GUESS = {"outdoor": (0.0, 0.0), "diffuse": (0.0, -3.0), "hybrid": (-3.0, -3.0), "specular": (-3.0, 0.0),
                   "glossy": (-3.0, 0.0)}                                   # geosplat.py:729-740
 
@@ -272,31 +302,8 @@ class Stage1Model:
 
     def smoothing_regularization(self, splats, attrs, cameras: Sequence[Camera], gt_rgba: Optional[Sequence[Tensor]],
                                  batch_size: int) -> Tensor:
-        """The 'grad' / 'tv' branches and `normal_grad_weight` of render_report (:881-922): edge-aware first-order / total-variation
-        penalties on UN-shaded renders of kd, (0, ks) and normals * 0.5 + 0.5 over the model's background colour."""
-        from .shading import render_rgb
-        reg = splats.means.new_zeros(())
-        need_gt = (self.smooth_type == "grad" and (self.kd_grad_weight > 0 or self.ks_grad_weight > 0)) or self.normal_grad_weight > 0
-        if need_gt and gt_rgba is None:
-            raise ValueError("smooth_type='grad' / normal_grad_weight need the ground-truth images (gt_outputs.blend(background))")
-        bg = self.background_color
-        rr = lambda colors, cam: render_rgb(splats.means, splats.scales, splats.quats, splats.opacities, colors, cam, bg)
-        gts = None if not need_gt else [g[..., :3] * g[..., 3:] + bg * (1 - g[..., 3:]) for g in gt_rgba]   # RGBAImages.blend
-        ks3 = torch.cat((torch.zeros_like(attrs.ks[..., :1]), attrs.ks), dim=-1)
-        for i, cam in enumerate(cameras):
-            if self.smooth_type == "grad":
-                if self.kd_grad_weight > 0:
-                    reg = reg + _edge_aware(rr(attrs.kd, cam), gts[i]) * self.kd_grad_weight / batch_size
-                if self.ks_grad_weight > 0:
-                    reg = reg + _edge_aware(rr(ks3, cam), gts[i]) * self.ks_grad_weight / batch_size
-            if self.normal_grad_weight > 0:
-                reg = reg + _edge_aware(rr(attrs.normals * 0.5 + 0.5, cam), gts[i]) * self.normal_grad_weight / batch_size
-            if self.smooth_type == "tv":
-                if self.kd_grad_weight > 0:
-                    reg = reg + _tv(rr(attrs.kd, cam)) * self.kd_grad_weight / batch_size
-                if self.ks_grad_weight > 0:
-                    reg = reg + _tv(rr(ks3, cam)) * self.ks_grad_weight / batch_size
-        return reg
+        """`smoothing_regularization` of this module for this model"""
+        return smoothing_regularization(self, splats, attrs, cameras, gt_rgba, batch_size)
 
     def render_report(self, cameras: Sequence[Camera], gt_rgba: Optional[Sequence[Tensor]] = None,
                       batch_size: Optional[int] = None) -> Tuple[List[Tensor], int, Tensor]:

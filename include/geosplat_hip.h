@@ -1159,6 +1159,35 @@ int gs_cube_sample_linear_bwd(int64_t n, int R, const float* dirs, float scale, 
 int gs_env_background_fwd(int R, int H, int W, const float* cube, float fx, float fy, float cx, float cy, const float* c2w,
                           const float* transform, int srgb, float* out, void* stream);
 
+/* ------------------------------------------------------------------ mesh-prior regularisers ------------------------------------ */
+/* The three mesh regularisers the reference's GeoSplatterPrior deforms a mesh under (rfstudio/model/geosplat_prior.py: a uniform
+ * Laplacian term, pytorch3d's mesh_edge_loss and mesh_normal_consistency), on a topology built once; a restatement of the published
+ * formulas.  csrc/gs_meshreg.hip; geosplatting_amd/meshreg.py builds the topology; tests/meshreg_ref.py states the same in float64.
+ *
+ * vertices [V,3] fp32.  edges [E,2] int32 (lo, hi), lo < hi, unique.  pairs [P,4] int32 (v0, v1, a, b): two faces on the side
+ * (v0, v1), a and b their opposite vertices.  nbr_off [V+1], nbr [2E]: per vertex its distinct neighbours, ascending (CSR).
+ * pr_off [V+1], pr [4P]: per vertex the codes 4 pair + role (role 0..3 = v0, v1, a, b) of its appearances in pairs, ascending (CSR).
+ * long_verts [NL]: the vertices with more than 64 neighbours or more than 64 codes, ascending; a wave walks their lists, a lane the
+ *   others'.  Every index must be inside its array: the kernels do not check.
+ * Terms:  lap_i  = |deg_i v_i - sum_{j in N(i)} v_j|                                  (0 for a vertex without neighbours)
+ *         edge_e = (|v_lo - v_hi| - target_length)^2
+ *         nc_p   = 1 - (n0 . -n1) / (max(|n0|, 1e-8) max(|n1|, 1e-8)),  n0 = (v1 - v0) x (a - v0),  n1 = (v1 - v0) x (b - v0)
+ * gs_meshreg_fwd  terms [V+E+P] (lap, then edge, then nc) and out [3] = (mean lap, mean edge, mean nc; 0 for an empty set) overwritten.
+ *   partials: gs_meshreg_partial_rows(V, E, P, NL) x 3 doubles of workspace: a workgroup's sums per term in a fixed order, added by a
+ *   final one-workgroup pass in double.  lap_dir [V,3] and pair_grad [P,4,3]: both or none; what the backward gathers (the unit
+ *   Laplacian vectors, d nc_p / d (v0, v1, a, b)); a zero-length vector under a norm gives the zero subgradient.
+ * gs_meshreg_bwd  grad [V,3] overwritten with out_grad[0] d(mean lap) + out_grad[1] d(mean edge) + out_grad[2] d(mean nc); out_grad: DEVICE
+ *   pointer to 3 floats.  A gather per vertex through nbr and pr.
+ * No atomics in either: the same inputs give the same bits.  Both return GS_EINVAL before touching the device for a negative count,
+ *   V + E + P or 4 P above 2^30, or a null required pointer (an array of a zero count may be null). */
+int gs_meshreg_partial_rows(int V, int E, int P, int NL);
+int gs_meshreg_fwd(int V, int E, int P, int NL, const float* vertices, const int32_t* edges, const int32_t* pairs, const int32_t* nbr_off,
+                   const int32_t* nbr, const int32_t* pr_off, const int32_t* long_verts, float target_length, float* terms, float* lap_dir,
+                   float* pair_grad, double* partials, float* out, void* stream);
+int gs_meshreg_bwd(int V, int E, int P, int NL, const float* vertices, const int32_t* nbr_off, const int32_t* nbr, const int32_t* pr_off,
+                   const int32_t* pr, const int32_t* long_verts, float target_length, const float* lap_dir, const float* pair_grad,
+                   const float* out_grad, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
