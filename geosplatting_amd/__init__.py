@@ -67,6 +67,11 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              GeoSplatterMC + GeoSplatMCTrainer and GeoSplatterPrior + GeoSplatPriorTrainer
                                              (rfstudio/model/geosplat_mc.py, geosplat_prior.py, rfstudio/trainer/geosplat_mc_trainer.py,
                                              geosplat_prior_trainer.py): stage-2 training on a stage-1 export or on a mesh
+  stage3.Stage3Model / Stage3Schedule / stage3.train_step / albedo_scaling / evaluate_relighting
+                                          == GeoSplatterDefer + GeoSplatDeferTrainer and the RelightEvaler task
+                                             (rfstudio/model/geosplat_defer.py, rfstudio/trainer/geosplat_defer_trainer.py,
+                                             tests/model/test_geosplat_defer.py:345-493): stage-3 training on a stage-2 export with
+                                             deferred shading on the frozen mesh, and NVS / relighting / albedo PSNR
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -92,6 +97,7 @@ from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .raytrace import MeshBVH, shadow_visibility  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401
 from .stage2 import PriorModel, Stage2Model, Stage2Schedule  # noqa: F401
+from .stage3 import Stage3Model, Stage3Schedule, albedo_scaling, evaluate_relighting  # noqa: F401
 from .surfels import SurfelModel, SurfelTrainer, depth_to_normal, rasterization_2dgs  # noqa: F401
 from . import viewbatch  # noqa: F401
 from .splitsum import TextureSplitSum, as_splitsum, diffuse_cubemap, specular_cubemap  # noqa: F401
