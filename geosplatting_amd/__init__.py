@@ -32,8 +32,9 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == TriangleMesh.render(cameras, shader=NormalShader() / DepthShader()) and
                                              TriangleMesh.visible_faces (rfstudio/graphics/_mesh/_triangle_mesh.py:496-555,
                                              rfstudio/graphics/shaders.py:107-132): nvdiffrast's rasterize + interpolate + antialias
-                                             restated (no near clipping): depth, normal, silhouette and face-index maps, with
-                                             silhouette gradients to the vertices through antialias
+                                             restated (near clipping opt-in: near_clip=True; not the far plane, not images wider
+                                             than the guard band, no antialias weight on clipped foreground faces): depth, normal,
+                                             silhouette and face-index maps, with silhouette gradients to the vertices through antialias
   meshshade.texture2d / Texture2D / shade_pixels, render_mesh(outputs=(..., 'color'), kd=, ks=, uvs=, envmap=)
                                           == TriangleMesh.render(cameras, shader=PBRShader(envmap=...)) and
                                              PrettyShader(occlusion_type='none') (rfstudio/graphics/shaders.py:44-105, 199-233):

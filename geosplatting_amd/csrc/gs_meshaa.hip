@@ -7,9 +7,12 @@
 //   gs_meshaa_fwd          : a gather, one thread per output pixel.  A pixel whose four neighbours carry its own face id copies its
 //                            colour; another analyses its (at most four) pairs and writes `out` once.  No atomics.
 //   gs_meshaa_bwd          : the same shape.  d color is gathered; the pixel that comes first in a pair issues its six vertex atomics.
+//   gs_meshclip_aa_fwd/bwd : the same kernels with CLIP (near_clip): a face that crosses the near plane counts as a neighbour in the
+//                            silhouette test (aa_crossing_side); as a foreground face it blends nothing.
 // Every decision (foreground, exit edge, silhouette) is made in integers on the snapped positions, so it does not depend on launch
 // order or on rounding; only the weight is fp32, from the unsnapped positions (the convention of mr_values).
 #include "gs_meshraster_dev.h"
+#include "gs_meshclip_dev.h"
 
 #define AA_EMPTY 0xffffffffffffffffull
 
@@ -107,7 +110,47 @@ __device__ __forceinline__ int aa_pick(const int (&A)[3], int k) { return k == 0
 __device__ __forceinline__ float aa_pick(const float (&A)[3], int k) { return k == 0 ? A[0] : (k == 1 ? A[1] : A[2]); }
 __device__ __forceinline__ long long aa_pick(const long long (&A)[3], int k) { return k == 0 ? A[0] : (k == 1 ? A[1] : A[2]); }
 
+// near_clip: does the crossing face f2 (gs_meshclip_dev.h) count as a neighbour on its half-edge i2, and on which side of the line
+// through (x1, y1) with direction (dx, dy) does it lie?  It counts when at least one sub-triangle of its clipped polygon survives
+// mr_edges and the cull, as in mr_cross_kernel.  The side is decided on the snapped position of the polygon vertex that follows the
+// edge's second endpoint (f2's vertex i2 + 2): f2's opposite vertex when that is inside, else the cut towards it; every vertex of the
+// polygon off the edge lies on that side in exact arithmetic.  false: not a neighbour (also when the guard band removed the endpoint).
+__device__ __forceinline__ bool aa_crossing_side(const float* __restrict__ vc, const int* __restrict__ faces, long long V, long long f2,
+                                                 int i2, const MrCam& cam, int cull, long long x1, long long y1, long long dx,
+                                                 long long dy, long long& side2)
+{
+    float Pc[3][3];
+    if (!mc_crossing(vc, faces, V, f2, cam, Pc)) return false;
+    McPoly Q;
+    mc_clip(Pc, cam, Q);
+    bool kept = false;
+#pragma unroll 1
+    for (int k = 1; k + 1 < Q.n; ++k) {
+        MrTri T;
+        MrEdges E;
+        mc_subtri(Q, k, cam, T);
+        if (mr_edges(T, cam, E) && !mr_culled(E, cull)) kept = true;
+    }
+    if (!kept) return false;
+    const int want = (i2 + 2) % 3;
+    int m = -1;
+#pragma unroll
+    for (int j = 0; j < MC_MAX_VERTS; ++j)
+        if (j < Q.n && Q.tag[j] == want) m = j;
+    if (m < 0) return false;
+    float x, y, z;
+    mc_get(Q, m + 1 < Q.n ? m + 1 : 0, x, y, z);
+    MrTri T;
+    mc_project(x, y, z, cam, T, 0);
+    const float sx = T.xs[0] * (float)MR_SNAP, sy = T.ys[0] * (float)MR_SNAP;
+    if (!(fabsf(sx) <= MR_RANGE && fabsf(sy) <= MR_RANGE)) return false;
+    side2 = dx * ((long long)__builtin_rintf(sy) - y1) - dy * ((long long)__builtin_rintf(sx) - x1);
+    return true;
+}
+
 // The pair (p, q), q = p + (1, 0) (horizontal) or p + (0, 1), whose face-id channels differ.  false: the pair blends nothing.
+// CLIP (near_clip): crossing faces count as neighbours (aa_crossing_side); a crossing foreground face fails mr_load and blends nothing.
+template <bool CLIP>
 __device__ __forceinline__ bool aa_pair(const AaCtx& K, long long p, long long q, int horizontal, AaPair& R)
 {
     const float4 rp = K.rast[p], rq = K.rast[q];
@@ -165,7 +208,14 @@ __device__ __forceinline__ bool aa_pair(const AaCtx& K, long long p, long long q
             MrEdges E2;
             float P2[3][3];
             int X2[3], Y2[3];
-            if (!mr_load(K.vc, K.faces, K.V, f2, K.cam, T2, P2)) continue;
+            if (!mr_load(K.vc, K.faces, K.V, f2, K.cam, T2, P2)) {
+                if (CLIP) {
+                    long long side2;
+                    if (aa_crossing_side(K.vc, K.faces, K.V, f2, i2, K.cam, K.cull, x1, y1, dx, dy, side2) &&
+                        ((side > 0 && side2 < 0) || (side < 0 && side2 > 0))) return false;
+                }
+                continue;
+            }
             if (!mr_edges(T2, K.cam, E2, X2, Y2)) continue;
             if (mr_culled(E2, K.cull)) continue;
             const long long side2 = dx * (aa_pick(Y2, i2) - y1) - dy * (aa_pick(X2, i2) - x1);
@@ -236,6 +286,7 @@ __device__ __forceinline__ bool aa_pair_of(const AaCtx& K, long long p, int px, 
     return py + 1 < H;
 }
 
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) aa_fwd_kernel(AaCtx K, int C, const float* __restrict__ color, float* __restrict__ out,
                                                                  int* __restrict__ dbg)
 {
@@ -253,7 +304,7 @@ static __global__ void __launch_bounds__(MR_BLOCK) aa_fwd_kernel(AaCtx K, int C,
         if (!aa_pair_of(K, p, px, py, k, first, second)) continue;
         if (K.rast[k & 1 ? second : first].w == me) continue;
         AaPair R;
-        if (!aa_pair(K, first, second, k < 2, R)) continue;
+        if (!aa_pair<CLIP>(K, first, second, k < 2, R)) continue;
         if (k == 1) code[0] = R.code;
         if (k == 3) code[1] = R.code;
         if (R.target == p) { aa_set(wk, k, R.w); aa_set(ok, k, R.other); any = true; }
@@ -276,6 +327,7 @@ static __global__ void __launch_bounds__(MR_BLOCK) aa_fwd_kernel(AaCtx K, int C,
     }
 }
 
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) aa_bwd_kernel(AaCtx K, int C, const float* __restrict__ color,
                                                                  const float* __restrict__ d_out, float* __restrict__ d_color,
                                                                  float* __restrict__ d_vc)
@@ -294,7 +346,7 @@ static __global__ void __launch_bounds__(MR_BLOCK) aa_bwd_kernel(AaCtx K, int C,
         if (!aa_pair_of(K, p, px, py, k, first, second)) continue;
         if (K.rast[k & 1 ? second : first].w == me) continue;
         AaPair R;
-        if (!aa_pair(K, first, second, k < 2, R)) continue;
+        if (!aa_pair<CLIP>(K, first, second, k < 2, R)) continue;
         if (R.target < 0) continue;
         aa_set(wk, k, R.target == p ? -R.w : R.w);
         aa_set(tk, k, R.target);
@@ -386,8 +438,8 @@ int gs_meshaa_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, f
     }
     GS_CHECK_ARG(rast && color && out && (F == 0 || (vc && faces)), "null pointer");
     AaCtx K{(long long)V, (long long)F, vc, faces, MrCam{fx, fy, cx, cy, near, H, W}, cull, (const float4*)rast, aa_topo(topo, L, F)};
-    hipLaunchKernelGGL(aa_fwd_kernel, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color, out,
-                       (int*)dbg);
+    hipLaunchKernelGGL(aa_fwd_kernel<false>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color,
+                       out, (int*)dbg);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -407,8 +459,50 @@ int gs_meshaa_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, f
     GS_CHECK_ARG(rast && color && d_out && d_color && (F == 0 || (vc && faces)), "null pointer");
     if (d_vc && V > 0) GS_CHECK_HIP(gs_zero_async(d_vc, (size_t)V * 12, (hipStream_t)stream));
     AaCtx K{(long long)V, (long long)F, vc, faces, MrCam{fx, fy, cx, cy, near, H, W}, cull, (const float4*)rast, aa_topo(topo, L, F)};
-    hipLaunchKernelGGL(aa_bwd_kernel, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color, d_out,
-                       d_color, d_vc);
+    hipLaunchKernelGGL(aa_bwd_kernel<false>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color,
+                       d_out, d_color, d_vc);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+// ---- near_clip: the same pass on a rast made by gs_meshclip_fwd / gs_meshclip_resolve
+int gs_meshclip_aa_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                       float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
+                       float* out, int32_t* dbg, void* stream)
+{
+    GS_CHECK_ARG(aa_dims_ok(V, F, H, W, C), "need V < 2^31, F <= 2^24, H, W >= 1, H W < 2^31 and 1 <= C <= 4096");
+    GS_CHECK_ARG(fx > 0.0f && fy > 0.0f && near > 0.0f, "fx, fy and near must be > 0");
+    GS_CHECK_ARG(cull == 0 || cull == 1, "cull must be 0 (none) or 1 (back)");
+    const AaLayout L = aa_layout(F);
+    if (!topo || topo_bytes < L.total) {
+        gs_set_error("%s: topology buffer too small (%zu < %zu)", __func__, topo ? topo_bytes : (size_t)0, L.total);
+        return topo ? GS_ENOSPC : GS_EINVAL;
+    }
+    GS_CHECK_ARG(rast && color && out && (F == 0 || (vc && faces)), "null pointer");
+    AaCtx K{(long long)V, (long long)F, vc, faces, MrCam{fx, fy, cx, cy, near, H, W}, cull, (const float4*)rast, aa_topo(topo, L, F)};
+    hipLaunchKernelGGL(aa_fwd_kernel<true>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color,
+                       out, (int*)dbg);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+int gs_meshclip_aa_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                       float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
+                       const float* d_out, float* d_color, float* d_vc, void* stream)
+{
+    GS_CHECK_ARG(aa_dims_ok(V, F, H, W, C), "need V < 2^31, F <= 2^24, H, W >= 1, H W < 2^31 and 1 <= C <= 4096");
+    GS_CHECK_ARG(fx > 0.0f && fy > 0.0f && near > 0.0f, "fx, fy and near must be > 0");
+    GS_CHECK_ARG(cull == 0 || cull == 1, "cull must be 0 (none) or 1 (back)");
+    const AaLayout L = aa_layout(F);
+    if (!topo || topo_bytes < L.total) {
+        gs_set_error("%s: topology buffer too small (%zu < %zu)", __func__, topo ? topo_bytes : (size_t)0, L.total);
+        return topo ? GS_ENOSPC : GS_EINVAL;
+    }
+    GS_CHECK_ARG(rast && color && d_out && d_color && (F == 0 || (vc && faces)), "null pointer");
+    if (d_vc && V > 0) GS_CHECK_HIP(gs_zero_async(d_vc, (size_t)V * 12, (hipStream_t)stream));
+    AaCtx K{(long long)V, (long long)F, vc, faces, MrCam{fx, fy, cx, cy, near, H, W}, cull, (const float4*)rast, aa_topo(topo, L, F)};
+    hipLaunchKernelGGL(aa_bwd_kernel<true>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, K, C, color,
+                       d_out, d_color, d_vc);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }

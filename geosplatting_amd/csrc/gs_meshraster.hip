@@ -8,10 +8,15 @@
 //   gs_meshraster_resolve  : one thread per pixel decodes the winner, recomputes b, one 16-byte store
 //   gs_meshraster_bwd      : d(b0, b1, depth) -> d vc with the face ids fixed; fp32 atomics, nine per covered pixel
 //   gs_mesh_interp_fwd/bwd : out = sum_i b_i attr[...]; d attr by fp32 atomics, d(b0, b1) per pixel
+//   gs_meshclip_fwd/resolve/bwd : the same with near_clip (gs_meshclip_dev.h).  The kernels above are templates on CLIP; without it they
+//                            are the code they were.  With it pass 1 also appends the faces that cross the near plane to a second
+//                            compacted list, and one more launch (mr_cross_kernel, one wave per listed face) clips each face and
+//                            walks its sub-triangles; resolve and backward evaluate a crossing face's values per face (mc_values).
 // Every kernel is bounded: no workgroup waits on another.  Coverage is decided in 64-bit integers on 1/256 px coordinates, so a pixel
 // on an edge shared by two triangles is covered exactly once (top-left rule) whatever the launch order.
 #include "gs_common.h"
 #include "gs_meshraster_dev.h"
+#include "gs_meshclip_dev.h"
 
 __device__ __forceinline__ void mr_emit(unsigned long long* __restrict__ keys, const MrCam& cam, const MrTri& T, int px, int py,
                                         unsigned fid, unsigned& n_frag, unsigned& n_atomic)
@@ -27,11 +32,14 @@ __device__ __forceinline__ void mr_emit(unsigned long long* __restrict__ keys, c
     ++n_atomic;
 }
 
+// CLIP (near_clip): the count of crossing faces sits next to the count of large triangles
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) mr_fill_kernel(unsigned long long* __restrict__ keys, size_t n_keys,
                                                                   unsigned* __restrict__ n_big)
 {
     const size_t i = (size_t)blockIdx.x * MR_BLOCK + threadIdx.x;
     if (i == 0) *n_big = 0u;
+    if (CLIP && i == 0) n_big[1] = 0u;
     // two keys per thread: one 16-byte store
     if (2 * i + 1 < n_keys) reinterpret_cast<ulonglong2*>(keys)[i] = make_ulonglong2(MR_EMPTY, MR_EMPTY);
     else if (2 * i < n_keys) keys[2 * i] = MR_EMPTY;
@@ -45,17 +53,30 @@ __device__ __forceinline__ void mr_commit_stats(unsigned long long* stats, int s
     if (n_atomic) atomicAdd(stats + slot + 1, (unsigned long long)n_atomic);
 }
 
+// CLIP: a face that fails mr_load because it crosses the near plane goes to the list `cross` (count n_big[1]) for mr_cross_kernel;
+// every other face takes the same code as without CLIP.
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) mr_small_kernel(long long V, long long F, const float* __restrict__ vc,
                                                                    const int* __restrict__ faces, MrCam cam, int cull,
                                                                    unsigned long long* __restrict__ keys, unsigned* __restrict__ n_big,
-                                                                   unsigned* __restrict__ big, unsigned long long* stats)
+                                                                   unsigned* __restrict__ big, unsigned* __restrict__ cross,
+                                                                   unsigned long long* stats)
 {
     const long long f = (long long)blockIdx.x * MR_BLOCK + threadIdx.x;
     if (f >= F) return;
     MrTri T;
     MrEdges E;
     float P[3][3];
-    if (!mr_load(vc, faces, V, f, cam, T, P)) return;
+    if (!mr_load(vc, faces, V, f, cam, T, P)) {
+        if (CLIP) {
+            float Pc[3][3];
+            if (mc_crossing(vc, faces, V, f, cam, Pc)) {
+                const unsigned slot = atomicAdd(n_big + 1, 1u);
+                if (slot < (unsigned long long)F) cross[slot] = (unsigned)f;
+            }
+        }
+        return;
+    }
     if (!mr_edges(T, cam, E)) return;
     if (mr_culled(E, cull)) return;
     if (E.x1 < E.x0 || E.y1 < E.y0) return;
@@ -112,6 +133,60 @@ static __global__ void __launch_bounds__(MR_BLOCK) mr_big_kernel(long long V, lo
     mr_commit_stats(stats, 2, n_frag, n_atomic);
 }
 
+// near_clip: one wave per crossing face.  Every lane clips the face (the same work in every lane: the polygon stays in registers),
+// then the lanes stride over the box of each sub-triangle of the fan, set up by mr_edges like any triangle; the fragment carries the
+// FACE's values (mc_values) and the face's id.
+static __global__ void __launch_bounds__(MR_BLOCK) mr_cross_kernel(long long V, long long F, const float* __restrict__ vc,
+                                                                   const int* __restrict__ faces, MrCam cam, int cull,
+                                                                   unsigned long long* __restrict__ keys,
+                                                                   const unsigned* __restrict__ n_cross,
+                                                                   const unsigned* __restrict__ cross, unsigned long long* stats)
+{
+    const unsigned total = *n_cross;
+    const unsigned count = total < (unsigned long long)F ? total : (unsigned)F;
+    const unsigned n_waves = gridDim.x * (MR_BLOCK / GS_WAVE);
+    const int lane = gs_lane_id();
+    unsigned n_frag = 0u, n_atomic = 0u;
+    for (unsigned w = blockIdx.x * (MR_BLOCK / GS_WAVE) + (threadIdx.x >> 6); w < count; w += n_waves) {
+        const long long f = cross[w];
+        if (f >= F) continue;
+        float P[3][3];
+        if (!mc_crossing(vc, faces, V, f, cam, P)) continue;     // (cannot fail: pass 1 listed it; wave-uniform either way)
+        McPoly Q;
+        mc_clip(P, cam, Q);
+#pragma unroll 1
+        for (int k = 1; k + 1 < Q.n; ++k) {
+            MrTri T;
+            MrEdges E;
+            mc_subtri(Q, k, cam, T);
+            if (!mr_edges(T, cam, E)) continue;
+            if (mr_culled(E, cull)) continue;
+            if (E.x1 < E.x0 || E.y1 < E.y0) continue;
+            const int bw = E.x1 - E.x0 + 1, bh = E.y1 - E.y0 + 1;
+            const int n = bw * bh;                               // <= W H < 2^31
+            for (int i = lane; i < n; i += GS_WAVE) {
+                const int ry = i / bw, rx = i - ry * bw;
+                const long long e0 = E.c[0] + E.ax[0] * rx + E.ay[0] * ry;
+                const long long e1 = E.c[1] + E.ax[1] * rx + E.ay[1] * ry;
+                const long long e2 = E.c[2] + E.ax[2] * rx + E.ay[2] * ry;
+                if (((e0 + E.bias[0]) | (e1 + E.bias[1]) | (e2 + E.bias[2])) < 0) continue;
+                const int px = E.x0 + rx, py = E.y0 + ry;
+                float b0, b1, depth;
+                mc_values(P, cam, px, py, b0, b1, depth);
+                if (!(depth > 0.0f && depth < 3.0e38f)) continue;                       // (a NaN fails)
+                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)f;
+                unsigned long long* slot = keys + (size_t)py * (size_t)cam.W + (size_t)px;
+                ++n_frag;
+                if (*slot <= key) continue;
+                atomicMin(slot, key);
+                ++n_atomic;
+            }
+        }
+    }
+    mr_commit_stats(stats, 2, n_frag, n_atomic);
+}
+
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) mr_resolve_kernel(long long V, long long F, const float* __restrict__ vc,
                                                                      const int* __restrict__ faces, MrCam cam,
                                                                      const unsigned long long* __restrict__ keys,
@@ -130,12 +205,48 @@ static __global__ void __launch_bounds__(MR_BLOCK) mr_resolve_kernel(long long V
             float b0, b1, depth;
             mr_values(T, px, py, b0, b1, depth);
             out = make_float4(b0, b1, __uint_as_float((unsigned)(key >> 32)), (float)(f + 1));      // the depth that won
+        } else if (CLIP) {
+            float Pc[3][3];
+            if (mc_crossing(vc, faces, V, f, cam, Pc)) {
+                const int py = (int)(p / cam.W), px = (int)(p - (long long)py * cam.W);
+                float b0, b1, depth;
+                mc_values(Pc, cam, px, py, b0, b1, depth);
+                out = make_float4(b0, b1, __uint_as_float((unsigned)(key >> 32)), (float)(f + 1));
+            }
         }
     }
     rast[p] = out;
 }
 
 // d(b0, b1, depth) -> d vc at fixed face ids.  With w_i = e_i iz_i, N = sum w, S = sum e:  b_i = w_i / N,  depth = S / N.
+// near_clip, a pixel of a crossing face.  (b1, b2, depth)^T = -M P0 with M = (h, e1 x d, e1 x e2)^T / a the inverse of [e1 e2 -d]
+// (mc_values).  Moving vertex m by delta moves the solution by -b_m M delta, so with R = ((g1 - g0) h - g0 (e1 x d) + gz n) / a the
+// gradient of g0 b0 + g1 b1 + gz depth with respect to vertex m is -b_m R: all three original vertices, the ones behind the plane too.
+__device__ __forceinline__ void mr_bwd_crossing(const float (&P)[3][3], const MrCam& cam, int px, int py, const float4& g,
+                                                const int* __restrict__ tri, float* __restrict__ d_vc)
+{
+    McRay R;
+    mc_ray(P, cam, px, py, R);
+    float b0, b1, depth;
+    mc_values(P, cam, px, py, b0, b1, depth);
+    const float b[3] = {b0, b1, (1.0f - b0) - b1};
+    const float c[3] = {R.e1[1] - R.dy * R.e1[2], R.dx * R.e1[2] - R.e1[0], R.dy * R.e1[0] - R.dx * R.e1[1]};         // e1 x d
+    const float n[3] = {R.e1[1] * R.e2[2] - R.e1[2] * R.e2[1], R.e1[2] * R.e2[0] - R.e1[0] * R.e2[2],
+                        R.e1[0] * R.e2[1] - R.e1[1] * R.e2[0]};
+    const float ra = 1.0f / R.a;
+    float Rv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Rv[k] = ((g.y - g.x) * R.h[k] - g.x * c[k] + g.z * n[k]) * ra;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        float* dst = d_vc + 3 * (size_t)tri[m];
+        gs_atomic_add(dst + 0, -b[m] * Rv[0]);
+        gs_atomic_add(dst + 1, -b[m] * Rv[1]);
+        gs_atomic_add(dst + 2, -b[m] * Rv[2]);
+    }
+}
+
+template <bool CLIP>
 static __global__ void __launch_bounds__(MR_BLOCK) mr_bwd_kernel(long long V, long long F, const float* __restrict__ vc,
                                                                  const int* __restrict__ faces, MrCam cam,
                                                                  const float4* __restrict__ rast, const float4* __restrict__ d_rast,
@@ -151,8 +262,14 @@ static __global__ void __launch_bounds__(MR_BLOCK) mr_bwd_kernel(long long V, lo
     if (g.x == 0.0f && g.y == 0.0f && g.z == 0.0f) return;
     MrTri T;
     float P[3][3];
-    if (!mr_load(vc, faces, V, f, cam, T, P)) return;
     const int py = (int)(p / cam.W), px = (int)(p - (long long)py * cam.W);
+    if (!mr_load(vc, faces, V, f, cam, T, P)) {
+        if (CLIP) {
+            float Pc[3][3];
+            if (mc_crossing(vc, faces, V, f, cam, Pc)) mr_bwd_crossing(Pc, cam, px, py, g, faces + 3 * f, d_vc);
+        }
+        return;
+    }
     const float pcx = (float)px + 0.5f, pcy = (float)py + 0.5f;
     float qx[3], qy[3];
 #pragma unroll
@@ -271,17 +388,19 @@ static __global__ void __launch_bounds__(MR_BLOCK) mi_bwd_kernel(long long P, in
 }
 
 // ------------------------------------------------------------------------------------------------ entry points
-// workspace: [ keys u64[H W] | big-triangle count u32 (16 bytes) | big-triangle list u32[F] ]
+// workspace: [ keys u64[H W] | big-triangle count u32, crossing-face count u32 (16 bytes) | big-triangle list u32[F] ]
+// and, with near_clip (gs_meshclip_*), [ ... | crossing-face list u32[F] ]
 struct MrLayout {
-    size_t off_count, off_big, total;
+    size_t off_count, off_big, off_cross, total;
 };
 static inline size_t mr_align(size_t x) { return (x + 15) & ~(size_t)15; }
-static inline MrLayout mr_layout(int64_t F, int H, int W)
+static inline MrLayout mr_layout(int64_t F, int H, int W, bool clip = false)
 {
     MrLayout L;
     L.off_count = mr_align((size_t)H * (size_t)W * 8);
     L.off_big = L.off_count + 16;
-    L.total = L.off_big + mr_align((size_t)(F > 0 ? F : 1) * 4);
+    L.off_cross = L.off_big + mr_align((size_t)(F > 0 ? F : 1) * 4);
+    L.total = L.off_cross + (clip ? mr_align((size_t)(F > 0 ? F : 1) * 4) : 0);
     return L;
 }
 static bool mr_dims_ok(int64_t V, int64_t F, int H, int W)
@@ -317,12 +436,13 @@ int gs_meshraster_fwd(int64_t V, int64_t F, const float* vc, const int32_t* face
     unsigned* big = (unsigned*)(base + L.off_big);
     hipStream_t s = (hipStream_t)stream;
     const size_t n_keys = (size_t)H * (size_t)W;
-    hipLaunchKernelGGL(mr_fill_kernel, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, keys, n_keys, n_big);
+    hipLaunchKernelGGL(mr_fill_kernel<false>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, keys, n_keys,
+                       n_big);
     GS_CHECK_LAUNCH();
     if (F == 0) return GS_OK;
     MrCam cam{fx, fy, cx, cy, near, H, W};
-    hipLaunchKernelGGL(mr_small_kernel, dim3(gs_cdiv(F, MR_BLOCK)), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, cull,
-                       keys, n_big, big, (unsigned long long*)stats);
+    hipLaunchKernelGGL(mr_small_kernel<false>, dim3(gs_cdiv(F, MR_BLOCK)), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam,
+                       cull, keys, n_big, big, (unsigned*)nullptr, (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
     const int want = gs_cdiv(F, MR_BLOCK / GS_WAVE);
     hipLaunchKernelGGL(mr_big_kernel, dim3(want < MR_MAX_BIG_BLOCKS ? want : MR_MAX_BIG_BLOCKS), dim3(MR_BLOCK), 0, s, (long long)V,
@@ -343,8 +463,8 @@ int gs_meshraster_resolve(int64_t V, int64_t F, const float* vc, const int32_t* 
     }
     GS_CHECK_ARG(rast && (F == 0 || (vc && faces)), "null pointer");
     MrCam cam{fx, fy, cx, cy, near, H, W};
-    hipLaunchKernelGGL(mr_resolve_kernel, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, (long long)V,
-                       (long long)F, vc, faces, cam, (const unsigned long long*)ws, (float4*)rast);
+    hipLaunchKernelGGL(mr_resolve_kernel<false>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream,
+                       (long long)V, (long long)F, vc, faces, cam, (const unsigned long long*)ws, (float4*)rast);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -360,7 +480,87 @@ int gs_meshraster_bwd(int64_t V, int64_t F, const float* vc, const int32_t* face
     if (F == 0) return GS_OK;
     GS_CHECK_ARG(vc && faces && rast && d_rast, "null pointer");
     MrCam cam{fx, fy, cx, cy, near, H, W};
-    hipLaunchKernelGGL(mr_bwd_kernel, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, (long long)V,
+    hipLaunchKernelGGL(mr_bwd_kernel<false>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, (long long)V,
+                       (long long)F, vc, faces, cam, (const float4*)rast, (const float4*)d_rast, d_vc);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+// ---- near_clip: the same three steps with crossing faces clipped (gs_meshclip_dev.h); every other face takes the code above
+size_t gs_meshclip_ws_bytes(int64_t F, int H, int W)
+{
+    if (!mr_dims_ok(0, F, H, W)) return 0;
+    return mr_layout(F, H, W, true).total;
+}
+
+int gs_meshclip_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                    float near, int cull, void* ws, size_t ws_bytes, uint64_t* stats, void* stream)
+{
+    GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
+    GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
+    GS_CHECK_ARG(cull == 0 || cull == 1, "cull must be 0 (none) or 1 (back)");
+    const MrLayout L = mr_layout(F, H, W, true);
+    if (!ws || ws_bytes < L.total) {
+        gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
+        return ws ? GS_ENOSPC : GS_EINVAL;
+    }
+    GS_CHECK_ARG(F == 0 || (vc && faces), "null pointer");
+    char* base = (char*)ws;
+    unsigned long long* keys = (unsigned long long*)base;
+    unsigned* n_big = (unsigned*)(base + L.off_count);
+    unsigned* big = (unsigned*)(base + L.off_big);
+    unsigned* cross = (unsigned*)(base + L.off_cross);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_keys = (size_t)H * (size_t)W;
+    hipLaunchKernelGGL(mr_fill_kernel<true>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, keys, n_keys,
+                       n_big);
+    GS_CHECK_LAUNCH();
+    if (F == 0) return GS_OK;
+    MrCam cam{fx, fy, cx, cy, near, H, W};
+    hipLaunchKernelGGL(mr_small_kernel<true>, dim3(gs_cdiv(F, MR_BLOCK)), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam,
+                       cull, keys, n_big, big, cross, (unsigned long long*)stats);
+    GS_CHECK_LAUNCH();
+    const int want = gs_cdiv(F, MR_BLOCK / GS_WAVE);
+    const int blocks = want < MR_MAX_BIG_BLOCKS ? want : MR_MAX_BIG_BLOCKS;
+    hipLaunchKernelGGL(mr_big_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, keys, n_big, big,
+                       (unsigned long long*)stats);
+    GS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mr_cross_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, cull, keys,
+                       n_big + 1, cross, (unsigned long long*)stats);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+int gs_meshclip_resolve(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H,
+                        int W, float near, const void* ws, size_t ws_bytes, float* rast, void* stream)
+{
+    GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
+    GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
+    const MrLayout L = mr_layout(F, H, W, true);
+    if (!ws || ws_bytes < L.total) {
+        gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
+        return ws ? GS_ENOSPC : GS_EINVAL;
+    }
+    GS_CHECK_ARG(rast && (F == 0 || (vc && faces)), "null pointer");
+    MrCam cam{fx, fy, cx, cy, near, H, W};
+    hipLaunchKernelGGL(mr_resolve_kernel<true>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream,
+                       (long long)V, (long long)F, vc, faces, cam, (const unsigned long long*)ws, (float4*)rast);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+int gs_meshclip_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                    float near, const float* rast, const float* d_rast, float* d_vc, void* stream)
+{
+    GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
+    GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
+    if (V == 0) return GS_OK;
+    GS_CHECK_ARG(d_vc, "null pointer");
+    GS_CHECK_HIP(gs_zero_async(d_vc, (size_t)V * 12, (hipStream_t)stream));
+    if (F == 0) return GS_OK;
+    GS_CHECK_ARG(vc && faces && rast && d_rast, "null pointer");
+    MrCam cam{fx, fy, cx, cy, near, H, W};
+    hipLaunchKernelGGL(mr_bwd_kernel<true>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, (long long)V,
                        (long long)F, vc, faces, cam, (const float4*)rast, (const float4*)d_rast, d_vc);
     GS_CHECK_LAUNCH();
     return GS_OK;

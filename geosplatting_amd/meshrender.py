@@ -4,13 +4,13 @@ silhouette and face-index maps from a camera.  What the reference gets from `Tri
 nvdiffrast's `rasterize`, `interpolate` and `antialias`.  nvdiffrast is not restated line by line: the semantics below are this
 project's, the kernels are csrc/gs_meshraster.hip and csrc/gs_meshaa.hip.
 
-  rasterize_mesh(verts_cam, faces, camera_or_intrinsics, *, cull='none', near=1e-2) -> rast [H,W,4]
+  rasterize_mesh(verts_cam, faces, camera_or_intrinsics, *, cull='none', near=1e-2, near_clip=False) -> rast [H,W,4]
   interpolate(attr, rast, faces)                                                    -> [H,W,C]
   mesh_edge_topology(faces)                                                         -> EdgeTopology
-  antialias(color, rast, verts_cam, faces, camera_or_intrinsics, *, topology, cull, near) -> [H,W,C]
-  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, antialias,
+  antialias(color, rast, verts_cam, faces, camera_or_intrinsics, *, topology, cull, near, near_clip) -> [H,W,C]
+  render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, near_clip, antialias,
               kd, ks, uvs, envmap, occlusion, min_visibility, bend_back_normal)     -> dict of maps ('color': meshshade.py)
-  visible_faces(vertices, faces, camera)                                            -> sorted unique face ids
+  visible_faces(vertices, faces, camera, *, near_clip)                              -> sorted unique face ids
   silhouette_loss(alpha, target_mask)                                               -> scalar
 
 Semantics of `rasterize_mesh`
@@ -22,9 +22,28 @@ Semantics of `rasterize_mesh`
             64-bit integers at (256 px + 128, 256 py + 128) and oriented by the sign of the snapped area.  A pixel is inside when
             all three are > 0; one that lies exactly on an edge belongs to the triangle only if that edge is a top or a left edge
             (top-left fill rule), so a pixel on an edge shared by two triangles is covered exactly once.
-  Dropped   a triangle is dropped WHOLE, never clipped, when its snapped area is zero, when any vertex has Z <= near, or when any
-            snapped coordinate lies outside +-2^22 (+-16384 px).  The reference clips at the near plane; no object-centred camera
-            of this project reaches it.
+  Dropped   a triangle is dropped WHOLE when its snapped area is zero, when any snapped coordinate lies outside +-2^22 (+-16384 px)
+            and, by default, when any vertex has Z <= near.  An object-centred camera never reaches the near plane; a camera that
+            stands inside the mesh (scene-scale models, the reference's truck and courthouse configurations) does: `near_clip`.
+  near_clip (opt-in; False gives the bits above) a vertex is inside iff Z > near (a NaN fails).  Three inside: a non-crossing face,
+            the code and the bits above.  None inside, or a non-finite coordinate: dropped.  Otherwise a CROSSING face, clipped
+            (Sutherland-Hodgman, at most 8 vertices) in camera space against Z > near and then against four guard planes
+            |xs| <= G, |ys| <= G with G = 16000 px, in homogeneous form, e.g. (G - cx) Z - fx X >= 0: nothing is divided by a
+            small Z, and every snapped coordinate of the result passes the +-2^22 test.  A new vertex is always computed from the
+            inside endpoint A towards the outside endpoint B, t = dA / (dA - dB), C = fma(t, B - A, A) per coordinate in fp32:
+            two faces that share the edge get the same bits for the cut, hence the same snapped vertex, hence a watertight seam.
+            The polygon is fan-triangulated (v0, vk, vk+1) into at most 6 sub-triangles of the face's winding; each is projected,
+            snapped, set up and walked like any triangle (top-left rule, `cull` on the sign of its snapped area, dropped on zero
+            snapped area), so a pixel on an edge shared by two sub-triangles, two crossing faces, or a crossing and a
+            non-crossing face is covered exactly once.  The values at a covered pixel are those of the FACE, in its three
+            original vertices (which may lie behind the eye): the ray d = ((px + 0.5 - cx) / fx, (py + 0.5 - cy) / fy, 1) meets
+            the face's plane at depth * d = sum_i b_i P_i.  Solved relative to P0 in fp32, every operation rounded once:
+            e1 = P1 - P0, e2 = P2 - P0, h = d x e2, a = e1 . h, g = P0 x e1, b1 = -(P0 . h) / a, b2 = -(d . g) / a,
+            depth = -(e2 . g) / a, b0 = (1 - b1) - b2 (the function w_i = d . (P_{i+1} x P_{i+2}), b_i = w_i / sum w,
+            depth = det[P0 P1 P2] / sum w).  The fragment key and the resolve evaluate the same function, per face.  rast[..., 3]
+            is the original face id + 1, so `interpolate`, shade_pixels and face-attribute lookups need no change.  Backward: with
+            the face ids and the clip fixed, the gradient goes through that solve to all three original vertices, the ones behind
+            the plane included.  Not clipped: the far plane (there is none), and images wider than the guard band.
   Culling   cull='none' rasterizes both windings.  cull='back' keeps the faces the reference keeps (_triangle_mesh.py:539),
             (camera_pos - centroid) . ((v1 - v0) x (v2 - v0)) > 0.  In camera space the eye is the origin and the normal is
             orthogonal to the triangle's edges, so the test is -det[v0; v1; v2] > 0, and det[v0; v1; v2] = Z0 Z1 Z2 / (fx fy) times the
@@ -61,8 +80,15 @@ Semantics of `antialias` (the reference's `dr.antialias(rgba, rast, projected, i
             out[a] += (0.5 - d) (color[b] - color[a]).  out = color + the sum over a pixel's (at most four) pairs.
   Backward  d color: the transpose of the blend.  d verts_cam: through d, with every discrete decision and the snap held fixed (the
             unsnapped positions of the exit edge's two vertices, xs = fx X / Z + cx); zero where d is clamped.  No gradient to rast.
+  near_clip must be the value `rast` was made with.  A crossing face with at least one surviving sub-triangle counts as a neighbour
+            in the silhouette test; its side of the exit edge's line is decided on the snapped position of the vertex that follows
+            the edge's second endpoint (the face's vertex i + 2 for its half-edge i) in its clipped polygon -- every vertex of
+            that polygon off the edge lies on the same side in exact arithmetic.  (It does not count when the guard band removed
+            that endpoint.)  A pair whose FOREGROUND face is a crossing face blends nothing, with no gradient: its weight would
+            need the derivative of the clip point.
 
-Differences from nvdiffrast: no near clipping, view depth in the third channel, y-down pixel rows; in `antialias`, the pairs, the
+Differences from nvdiffrast: near clipping is opt-in (`near_clip`) and leaves out the antialias weight on crossing foreground
+faces, images wider than the guard band and the far plane; view depth in the third channel, y-down pixel rows; in `antialias`, the pairs, the
 foreground, the exit edge and the silhouette test are decided on the snapped integer positions (and depth ties on the face id) while
 the weight comes from the unsnapped ones, and a silhouette is tested against every face on the edge, not against one neighbour.
 Every op raises GeoSplatHipError on CPU tensors; there is no CPU path.
@@ -99,53 +125,63 @@ def _mesh_head(v: Tensor, f: Tensor, intr, near: float):
     return (v.shape[0], f.shape[0], _lib.ptr(v), _lib.ptr(f), fx, fy, cx, cy, H, W, float(near))
 
 
+def _entry(name: str, near_clip: bool):
+    """gs_meshraster_<name> / gs_meshaa_<name>, or their near_clip twins gs_meshclip_<name> / gs_meshclip_aa_<name>"""
+    stem, _, step = name.partition("_")
+    twin = {"meshraster": "gs_meshclip_", "meshaa": "gs_meshclip_aa_"}[stem] + step
+    return getattr(_lib.lib(), twin if near_clip else "gs_" + name), (twin if near_clip else "gs_" + name)
+
+
 def rasterize_raw(verts_cam: Tensor, faces32: Tensor, intr, *, cull: str = "none", near: float = 1e-2,
-                  stats: Optional[Tensor] = None) -> Tensor:
-    """The two forward launches without autograd: gs_meshraster_fwd, gs_meshraster_resolve -> rast.  `stats` (int64[4] on the
-    device, added to): fragments and atomics of the thread-per-triangle pass, then of the wave-per-triangle pass."""
+                  stats: Optional[Tensor] = None, near_clip: bool = False) -> Tensor:
+    """The two forward launches without autograd: gs_meshraster_fwd, gs_meshraster_resolve -> rast (gs_meshclip_* with `near_clip`).
+    `stats` (int64[4] on the device, added to): fragments and atomics of the thread-per-triangle pass, then of the wave-per-triangle
+    pass (which counts the crossing faces of `near_clip` too)."""
     if cull not in _CULL:
         raise ValueError("cull must be 'none' or 'back'")
-    lib = _lib.lib()
     H, W = intr[4], intr[5]
-    ws_bytes = lib.gs_meshraster_ws_bytes(faces32.shape[0], H, W)
+    ws_bytes = _entry("meshraster_ws_bytes", near_clip)[0](faces32.shape[0], H, W)
     if ws_bytes == 0:
         raise _lib.GeoSplatHipError("mesh or image size out of range (at most 2^24 faces, H W < 2^31)")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=verts_cam.device)
     rast = torch.empty(H, W, 4, device=verts_cam.device)
     head = _mesh_head(verts_cam, faces32, intr, near)
-    _lib.check(lib.gs_meshraster_fwd(*head, _CULL[cull], _lib.ptr(ws), ws_bytes, _lib.ptr(stats), _lib.stream()), "gs_meshraster_fwd")
-    _lib.check(lib.gs_meshraster_resolve(*head, _lib.ptr(ws), ws_bytes, _lib.ptr(rast), _lib.stream()), "gs_meshraster_resolve")
+    fwd, fwd_name = _entry("meshraster_fwd", near_clip)
+    resolve, resolve_name = _entry("meshraster_resolve", near_clip)
+    _lib.check(fwd(*head, _CULL[cull], _lib.ptr(ws), ws_bytes, _lib.ptr(stats), _lib.stream()), fwd_name)
+    _lib.check(resolve(*head, _lib.ptr(ws), ws_bytes, _lib.ptr(rast), _lib.stream()), resolve_name)
     return rast
 
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, verts_cam: Tensor, faces32: Tensor, intr, cull: str, near: float):
+    def forward(ctx, verts_cam: Tensor, faces32: Tensor, intr, cull: str, near: float, near_clip: bool):
         v = verts_cam.detach().contiguous().float()
-        rast = rasterize_raw(v, faces32, intr, cull=cull, near=near)
+        rast = rasterize_raw(v, faces32, intr, cull=cull, near=near, near_clip=near_clip)
         ctx.save_for_backward(v, faces32, rast)
-        ctx.intr, ctx.near = intr, near
+        ctx.intr, ctx.near, ctx.near_clip = intr, near, near_clip
         return rast
 
     @staticmethod
     def backward(ctx, d_rast: Tensor):
         v, f, rast = ctx.saved_tensors
         d_vc = torch.empty_like(v)
-        _lib.check(_lib.lib().gs_meshraster_bwd(*_mesh_head(v, f, ctx.intr, ctx.near), _lib.ptr(rast),
-                                                _lib.ptr(d_rast.contiguous().float()), _lib.ptr(d_vc), _lib.stream()),
-                   "gs_meshraster_bwd")
-        return d_vc, None, None, None, None
+        bwd, name = _entry("meshraster_bwd", ctx.near_clip)
+        _lib.check(bwd(*_mesh_head(v, f, ctx.intr, ctx.near), _lib.ptr(rast), _lib.ptr(d_rast.contiguous().float()), _lib.ptr(d_vc),
+                       _lib.stream()), name)
+        return d_vc, None, None, None, None, None
 
 
 def rasterize_mesh(verts_cam: Tensor, faces: Tensor, camera_or_intrinsics: Intrinsics, *, cull: str = "none",
-                   near: float = 1e-2) -> Tensor:
-    """-> rast [H,W,4] = (b0, b1, view depth, face_id + 1), zeros where empty; differentiable in `verts_cam` (module docstring)."""
+                   near: float = 1e-2, near_clip: bool = False) -> Tensor:
+    """-> rast [H,W,4] = (b0, b1, view depth, face_id + 1), zeros where empty; differentiable in `verts_cam` (module docstring).
+    `near_clip`: faces that cross the near plane are clipped instead of dropped."""
     _lib.require_cuda(verts_cam, faces)
     if verts_cam.ndim != 2 or verts_cam.shape[1] != 3:
         raise _lib.GeoSplatHipError("verts_cam must be [V,3]")
     if cull not in _CULL:
         raise ValueError("cull must be 'none' or 'back'")
-    return _Rasterize.apply(verts_cam, _faces32(faces), _intrinsics(camera_or_intrinsics), cull, float(near))
+    return _Rasterize.apply(verts_cam, _faces32(faces), _intrinsics(camera_or_intrinsics), cull, float(near), bool(near_clip))
 
 
 class _Interpolate(torch.autograd.Function):
@@ -232,7 +268,7 @@ def _aa_head(v: Tensor, f: Tensor, intr, near: float, cull: str, topo: EdgeTopol
 
 
 def antialias_raw(color: Tensor, rast: Tensor, verts_cam: Tensor, faces32: Tensor, intr, topo: EdgeTopology, *, cull: str = "none",
-                  near: float = 1e-2, debug: bool = False):
+                  near: float = 1e-2, debug: bool = False, near_clip: bool = False):
     """gs_meshaa_fwd without autograd on contiguous fp32 tensors -> out, or (out, decisions int32 [H,W,2]) with `debug`: per pixel p
     the pairs (p, p + (1,0)) and (p, p + (0,1)); 0 = nothing blended, else 1 + exit edge + 4 (0 zero weight, 1 p receives, 2 the
     other pixel receives) + 16 (the foreground is the other pixel)."""
@@ -240,20 +276,22 @@ def antialias_raw(color: Tensor, rast: Tensor, verts_cam: Tensor, faces32: Tenso
     C = color.shape[-1]
     out = torch.empty_like(color)
     dbg = torch.empty(H, W, 2, dtype=torch.int32, device=color.device) if debug else None
-    _lib.check(_lib.lib().gs_meshaa_fwd(*_aa_head(verts_cam, faces32, intr, near, cull, topo, C, rast, color), _lib.ptr(out),
-                                        _lib.ptr(dbg), _lib.stream()), "gs_meshaa_fwd")
+    fwd, name = _entry("meshaa_fwd", near_clip)
+    _lib.check(fwd(*_aa_head(verts_cam, faces32, intr, near, cull, topo, C, rast, color), _lib.ptr(out), _lib.ptr(dbg), _lib.stream()),
+               name)
     return (out, dbg) if debug else out
 
 
 class _Antialias(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, color: Tensor, verts_cam: Tensor, rast: Tensor, faces32: Tensor, topo: EdgeTopology, intr, cull: str, near: float):
+    def forward(ctx, color: Tensor, verts_cam: Tensor, rast: Tensor, faces32: Tensor, topo: EdgeTopology, intr, cull: str, near: float,
+                near_clip: bool):
         c = color.detach().contiguous().float()
         v = verts_cam.detach().contiguous().float()
         r = rast.detach().contiguous().float()
-        out = antialias_raw(c, r, v, faces32, intr, topo, cull=cull, near=near)
+        out = antialias_raw(c, r, v, faces32, intr, topo, cull=cull, near=near, near_clip=near_clip)
         ctx.save_for_backward(c, v, r, faces32)
-        ctx.topo, ctx.intr, ctx.cull, ctx.near = topo, intr, cull, near
+        ctx.topo, ctx.intr, ctx.cull, ctx.near, ctx.near_clip = topo, intr, cull, near, near_clip
         return out
 
     @staticmethod
@@ -262,16 +300,17 @@ class _Antialias(torch.autograd.Function):
         g = d_out.contiguous().float()
         d_color = torch.empty_like(c)
         d_vc = torch.empty_like(v) if ctx.needs_input_grad[1] else None
-        _lib.check(_lib.lib().gs_meshaa_bwd(*_aa_head(v, f, ctx.intr, ctx.near, ctx.cull, ctx.topo, c.shape[-1], r, c), _lib.ptr(g),
-                                            _lib.ptr(d_color), _lib.ptr(d_vc), _lib.stream()), "gs_meshaa_bwd")
-        return d_color, d_vc, None, None, None, None, None, None
+        bwd, name = _entry("meshaa_bwd", ctx.near_clip)
+        _lib.check(bwd(*_aa_head(v, f, ctx.intr, ctx.near, ctx.cull, ctx.topo, c.shape[-1], r, c), _lib.ptr(g), _lib.ptr(d_color),
+                       _lib.ptr(d_vc), _lib.stream()), name)
+        return d_color, d_vc, None, None, None, None, None, None, None
 
 
 def antialias(color: Tensor, rast: Tensor, verts_cam: Tensor, faces: Tensor, camera_or_intrinsics: Intrinsics, *,
-              topology: Optional[EdgeTopology] = None, cull: str = "none", near: float = 1e-2) -> Tensor:
+              topology: Optional[EdgeTopology] = None, cull: str = "none", near: float = 1e-2, near_clip: bool = False) -> Tensor:
     """color [H,W,C] -> [H,W,C] with the silhouette pixels blended across the outline (module docstring); differentiable in `color` and
-    in `verts_cam`, not in `rast`.  `cull` and `near` must be the values `rast` was made with; `topology` (mesh_edge_topology(faces))
-    is built here when none is passed."""
+    in `verts_cam`, not in `rast`.  `cull`, `near` and `near_clip` must be the values `rast` was made with; `topology`
+    (mesh_edge_topology(faces)) is built here when none is passed."""
     _lib.require_cuda(color, rast, verts_cam, faces)
     if cull not in _CULL:
         raise ValueError("cull must be 'none' or 'back'")
@@ -287,7 +326,7 @@ def antialias(color: Tensor, rast: Tensor, verts_cam: Tensor, faces: Tensor, cam
         topology = mesh_edge_topology(f)
     elif topology.n_faces != f.shape[0] or topology.buffer.device != color.device:
         raise _lib.GeoSplatHipError("topology was built for another face array or device")
-    return _Antialias.apply(color, verts_cam, rast, f, topology, intr, cull, float(near))
+    return _Antialias.apply(color, verts_cam, rast, f, topology, intr, cull, float(near), bool(near_clip))
 
 
 _antialias = antialias
@@ -317,7 +356,7 @@ def to_camera_space(vertices: Tensor, camera: Camera) -> Tensor:
 
 def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Sequence[str] = ("depth", "normal", "alpha", "face"),
                 normal_type: str = "vertex", cull: str = "back", vertex_normals: Optional[Tensor] = None,
-                near: float = 1e-2, antialias: bool = False, topology: Optional[EdgeTopology] = None,
+                near: float = 1e-2, near_clip: bool = False, antialias: bool = False, topology: Optional[EdgeTopology] = None,
                 kd=None, ks=None, uvs: Optional[Tensor] = None, envmap=None, occlusion: str = "texture",
                 min_visibility: float = 0.0, bend_back_normal: bool = False) -> Dict[str, Tensor]:
     """World-space mesh seen from `camera` -> {'rast' [H,W,4] and the requested maps}:
@@ -333,7 +372,8 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
     depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not, unless `antialias` is set: then the
     requested maps among depth, normal, color and alpha go through `antialias` together as one image (the way the reference
     antialiases its rgba), normal is normalised again, and alpha lies strictly between 0 and 1 along the outline with a gradient to
-    the vertices of the outline's faces.  face and rast are never changed.  `topology`: mesh_edge_topology(faces), to reuse it."""
+    the vertices of the outline's faces.  face and rast are never changed.  `topology`: mesh_edge_topology(faces), to reuse it.
+    `near_clip`: faces that cross the near plane are clipped instead of dropped (module docstring), for cameras inside the mesh."""
     _lib.require_cuda(vertices, faces)
     unknown = set(outputs) - {"depth", "normal", "alpha", "face", "color"}
     if unknown:
@@ -354,7 +394,7 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
     if want_color and uvs is not None and tuple(uvs.shape) != (f32.shape[0], 3, 2):
         raise _lib.GeoSplatHipError("uvs must be [F,3,2]")
     vc = to_camera_space(vertices, camera)
-    rast = rasterize_mesh(vc, f32, camera, cull=cull, near=near)
+    rast = rasterize_mesh(vc, f32, camera, cull=cull, near=near, near_clip=near_clip)
     out: Dict[str, Tensor] = {"rast": rast}
     if "depth" in outputs:
         out["depth"] = interpolate(vc[:, 2:3].contiguous(), rast, f32)
@@ -384,16 +424,19 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
     names = [k for k in ("depth", "normal", "color", "alpha") if k in out]
     if antialias and names:
         widths = [out[k].shape[-1] for k in names]
-        blended = _antialias(torch.cat([out[k] for k in names], -1), rast, vc, f32, camera, topology=topology, cull=cull, near=near)
+        blended = _antialias(torch.cat([out[k] for k in names], -1), rast, vc, f32, camera, topology=topology, cull=cull, near=near,
+                             near_clip=near_clip)
         for k, part in zip(names, blended.split(widths, -1)):
             out[k] = _unit_or_z(part) if k == "normal" else part
     return out
 
 
-def visible_faces(vertices: Tensor, faces: Tensor, camera: Camera, *, cull: str = "none", near: float = 1e-2) -> Tensor:
-    """TriangleMesh.visible_faces: the sorted unique ids of the faces that own at least one pixel (no culling, as there)."""
+def visible_faces(vertices: Tensor, faces: Tensor, camera: Camera, *, cull: str = "none", near: float = 1e-2,
+                  near_clip: bool = False) -> Tensor:
+    """TriangleMesh.visible_faces: the sorted unique ids of the faces that own at least one pixel (no culling, as there); with
+    `near_clip` the faces that cross the near plane are among them."""
     _lib.require_cuda(vertices, faces)
     with torch.no_grad():
-        rast = rasterize_mesh(to_camera_space(vertices, camera), faces, camera, cull=cull, near=near)
+        rast = rasterize_mesh(to_camera_space(vertices, camera), faces, camera, cull=cull, near=near, near_clip=near_clip)
     ids = rast[..., 3]
     return (ids[ids > 0].long() - 1).unique()

@@ -253,14 +253,15 @@ class Stage3Model:
             kd = kd * self.albedo_scaling
         return kd, ks, occ
 
-    def surface(self, camera: Camera) -> Tuple[Tensor, Tensor]:
+    def surface(self, camera: Camera, *, near_clip: bool = False) -> Tuple[Tensor, Tensor]:
         """-> (positions [H,W,3], mask [H,W,1]): the first visible layer of the frozen mesh, `rasterize_mesh` + `interpolate(mesh_v)`,
         mask = 1 where a face covers the pixel -- what `dr.DepthPeeler(...).rasterize_next_layer()` + `dr.interpolate` give at
-        geosplat_defer.py:202-209.  No gradient.  The rasterizer has no near clipping: the camera must see the mesh beyond its near
-        plane."""
+        geosplat_defer.py:202-209.  No gradient.  By default a face that crosses the near plane is dropped whole and leaves a hole in
+        both maps; `near_clip=True` clips it instead, for a camera that stands inside the mesh (the far
+        plane and images wider than the guard band are not clipped)."""
         from .meshrender import interpolate, rasterize_mesh, to_camera_space
         with torch.no_grad():
-            rast = rasterize_mesh(to_camera_space(self.mesh_v, camera), self.mesh_i, camera)
+            rast = rasterize_mesh(to_camera_space(self.mesh_v, camera), self.mesh_i, camera, near_clip=near_clip)
             return interpolate(self.mesh_v, rast, self.mesh_i), (rast[..., -1:] > 0).float()
 
     def render_report(self, cameras: Sequence[Camera], gt_rgba: Optional[Sequence[Tensor]] = None, *, rnd_seed: Optional[int] = None,

@@ -874,6 +874,55 @@ int gs_mesh_interp_fwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vert
 int gs_mesh_interp_bwd(int64_t P, int C, int64_t F, int64_t V, int per_face_vertex, const float* rast, const int32_t* faces,
                        const float* attr, const float* d_out, float* d_attr, float* d_rast, void* stream);
 
+/* ------------------------------------------------------------------ near-plane and guard-band clipping --- */
+/* The rasterizer above with the faces that cross the near plane CLIPPED instead of dropped (nvdiffrast clips; the reference's scene
+ * configurations put the camera inside the mesh).  csrc/gs_meshclip_dev.h, the kernels in csrc/gs_meshraster.hip and gs_meshaa.hip.
+ *
+ * Classification: a vertex is inside iff Z > near (a NaN fails).  All three inside: a non-crossing face; it takes the code of
+ *   gs_meshraster_* and gives its bits (it is still dropped whole when a snapped coordinate leaves +-2^22).  None inside, a non-finite
+ *   coordinate or an index outside [0, V): dropped.  Otherwise a crossing face.
+ * Clip of a crossing face: Sutherland-Hodgman in camera space against Z > near, then against the guard planes xs <= G, xs >= -G,
+ *   ys <= G, ys >= -G with G = 16000 px, in homogeneous form (distances (G - cx) Z - fx X, (G + cx) Z + fx X, (G - cy) Z - fy Y,
+ *   (G + cy) Z + fy Y, each one fma of a product; inside when >= 0): at most 8 vertices.  A new vertex is always computed from the
+ *   inside endpoint A towards the outside endpoint B:  t = dA / (dA - dB),  C = fma(t, B - A, A) per coordinate, without contraction,
+ *   so two faces that share the edge get the same bits and the same snapped vertex.  The polygon (v0 .. vn-1, the face's winding) is
+ *   fan-triangulated into (v0, vk, vk+1), at most 6 sub-triangles.
+ * Coverage: every sub-triangle is projected (xs = fma(fx, X / Z, cx)), snapped, set up and walked like a triangle above: top-left
+ *   rule, cull on the sign of its snapped area, dropped on zero snapped area.  A pixel on an edge shared by two sub-triangles, two
+ *   crossing faces, or a crossing and a non-crossing face is covered once.
+ * Values of a crossing face, per FACE (not per sub-triangle), from its three original vertices, which may lie behind the eye: where
+ *   the ray d = ((px + 0.5 - cx) / fx, (py + 0.5 - cy) / fy, 1) meets the plane of P0 P1 P2, solved relative to P0, every operation
+ *   rounded once, no contraction:  e1 = P1 - P0, e2 = P2 - P0;  h = d x e2;  a = (e1x hx + e1y hy) + e1z hz;  g = P0 x e1;
+ *   nu = (P0x hx + P0y hy) + P0z hz;  nv = (dx gx + dy gy) + gz;  nt = (e2x gx + e2y gy) + e2z gz;  r = -1 / a;
+ *   b1 = nu r,  b2 = nv r,  depth = nt r,  b0 = (1 - b1) - b2.  (The same function as w_i = d . (P_{i+1} x P_{i+2}), b_i = w_i / sum w,
+ *   depth = det[P0 P1 P2] / sum w.)  The fragment key and the resolve evaluate this one function.  rast[..., 3] = the face id + 1.
+ * Depth test, determinism, F <= 2^24: as above.
+ * Backward: face ids and the clip fixed.  (b1, b2, depth)^T = -M P0 with M = (h, e1 x d, e1 x e2)^T / a; the gradient of
+ *   g0 b0 + g1 b1 + gz depth to vertex m is -b_m ((g1 - g0) h - g0 (e1 x d) + gz (e1 x e2)) / a, for all three original vertices.
+ * Antialias: a crossing face with at least one surviving sub-triangle counts as a neighbour in the silhouette test; its side of the
+ *   exit edge's line is decided on the snapped position of the polygon vertex that follows the edge's second endpoint (the face's vertex
+ *   i + 2 for its half-edge i) in the clipped polygon; it does not count when the guard band removed that endpoint.  A pair whose
+ *   foreground face is a crossing face blends nothing (decision 0, no gradient).
+ * Not clipped: the far plane; images wider than the guard band (a non-crossing face beyond +-2^22 is still dropped whole).
+ *
+ *   gs_meshclip_ws_bytes    8 bytes per pixel + 8 per face + 48 (0: sizes out of range)
+ *   gs_meshclip_fwd / _resolve / _bwd       the arguments of gs_meshraster_fwd / _resolve / _bwd; `stats` counts the crossing faces'
+ *                           fragments and atomics with the wave-per-triangle pass
+ *   gs_meshclip_aa_fwd / _bwd               the arguments of gs_meshaa_fwd / _bwd (below), on a rast made by gs_meshclip_* */
+size_t gs_meshclip_ws_bytes(int64_t F, int H, int W);
+int gs_meshclip_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                    float near, int cull, void* ws, size_t ws_bytes, uint64_t* stats, void* stream);
+int gs_meshclip_resolve(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H,
+                        int W, float near, const void* ws, size_t ws_bytes, float* rast, void* stream);
+int gs_meshclip_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                    float near, const float* rast, const float* d_rast, float* d_vc, void* stream);
+int gs_meshclip_aa_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                       float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
+                       float* out, int32_t* dbg, void* stream);
+int gs_meshclip_aa_bwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
+                       float near, int cull, const void* topo, size_t topo_bytes, int C, const float* rast, const float* color,
+                       const float* d_out, float* d_color, float* d_vc, void* stream);
+
 /* ------------------------------------------------------------------ mesh silhouette antialiasing --------- */
 /* What TriangleMesh.render gets from `dr.antialias(rgba, rast, projected, indices)` (_triangle_mesh.py:552-553); a restatement of the
  * semantics, not of nvdiffrast.  csrc/gs_meshaa.hip; faces are loaded, snapped and culled by the rasterizer's own device code.

@@ -3,7 +3,11 @@
 800 x 800 on the meshes this project extracts, and count the rasterizer's atomics.
 
     python scripts/mesh_render_bench.py [--meshes flexicubes96,tsdf512,ico3,ico5,ico7,plane] [--size 800] [--runs 20] [--warmup 3]
-                                        [--lib PATH/libgeosplat_hip.so] [--out FILE.json]
+                                        [--lib PATH/libgeosplat_hip.so] [--out FILE.json] [--near-clip]
+
+--near-clip adds a section: `rasterize_raw` (forward + resolve) on flexicubes96 with near_clip=False and True in the same process,
+median of 5, cull='none', for the object-centred view (no face crosses the near plane) and for an eye 2 mm inside the wall looking
+along it, with the number of crossing faces.  `--meshes ""` runs that section alone.
 
 Meshes
   flexicubes96  the stage-1 FlexiCubes mesh at 96^3 (Stage1Model with a sphere SDF of radius 0.8)
@@ -82,8 +86,38 @@ def build_mesh(name, gs, syn, dev):
     raise SystemExit(f"unknown mesh {name}")
 
 
+def near_clip_section(gs, mr, syn, dev, size, runs=5, warmup=3):
+    """rasterize_raw (forward + resolve) on the flexicubes96 mesh with near_clip False and True, alternating in one process, for the
+    object-centred view (no crossing face: both take the same code) and for an eye 2 mm inside the wall looking along it"""
+    v, f = build_mesh("flexicubes96", gs, syn, dev)
+    f32 = f.to(torch.int32).contiguous()
+    outside = syn.blender_cameras(8, size, size)[0].to(dev)
+    c2w = torch.tensor([[1.0, 0.0, 0.0, 0.798], [0.0, 0.0, -1.0, 0.0], [0.0, 1.0, 0.0, 0.0]], device=dev)
+    inside = gs.Camera(c2w, outside.fx, outside.fy, outside.cx, outside.cy, size, size)
+    out = {"faces": int(f32.shape[0]), "image": size, "runs": runs}
+    for label, cam in (("object_centred", outside), ("inside", inside)):
+        intr = (cam.fx, cam.fy, cam.cx, cam.cy, cam.height, cam.width)
+        with torch.no_grad():
+            vc = mr.to_camera_space(v, cam).contiguous()
+        z = vc[f32.long()][..., 2]
+        n_in = (z > 1e-2).sum(-1)
+        row = {"crossing_faces": int(((n_in > 0) & (n_in < 3) & torch.isfinite(vc[f32.long()]).all(-1).all(-1)).sum())}
+        for clip in (False, True):
+            kept = {}
+
+            def call():
+                kept["rast"] = mr.rasterize_raw(vc, f32, intr, cull="none", near=1e-2, near_clip=clip)
+
+            t = timed(call, runs, warmup)
+            row["near_clip" if clip else "plain"] = {"ms": t[0], "min_max": t[1:], "covered_pixels": int((kept["rast"][..., 3] > 0).sum())}
+        out[label] = row
+        print("near_clip", label, json.dumps(row), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--near-clip", action="store_true", help="also time near_clip=False against True (flexicubes96, median of 5)")
     ap.add_argument("--meshes", default="flexicubes96,tsdf512,ico3,ico5,ico7,plane")
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--runs", type=int, default=20)
@@ -103,7 +137,7 @@ def main():
     cam = syn.blender_cameras(8, a.size, a.size)[0].to(dev)
     lib = _lib.lib()
     results = {"image": a.size, "lib": a.lib or "default", "meshes": {}}
-    for name in a.meshes.split(","):
+    for name in [m for m in a.meshes.split(",") if m]:
         v, f = build_mesh(name, gs, syn, dev)
         f32 = f.to(torch.int32).contiguous()
         intr = (cam.fx, cam.fy, cam.cx, cam.cy, cam.height, cam.width)
@@ -185,6 +219,8 @@ def main():
         print(name, json.dumps(results["meshes"][name]), flush=True)
         del v, f, f32, vc, ws, rast, d_rast, d_vc, vg, kept, topo, color, d_out, aa_out, d_color, dbg
         torch.cuda.empty_cache()
+    if a.near_clip:
+        results["near_clip"] = near_clip_section(gs, mr, syn, dev, a.size)
     print(json.dumps(results))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
