@@ -40,6 +40,16 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              PrettyShader(occlusion_type='none') (rfstudio/graphics/shaders.py:44-105, 199-233):
                                              dr.texture's 2-D lookup ('wrap' / 'clamp') and the per-pixel split-sum PBR shader, with
                                              gradients to the textures, the environment, the normals and the positions
+  occlusion.ambient_occlusion / face_ambient_occlusion, shade_pixels(occlusion='ao' | 'screen', visibility=),
+  render_mesh(occlusion='ao' | 'screen', outputs=(..., 'ao')), meshmc.render_mesh_mc
+                                          == PBRShader(occlusion_type='ao' | 'ssao') on a given visibility map and MCShader
+                                             (rfstudio/graphics/shaders.py:92-104, 282-359) with
+                                             TriangleMesh.compute_ambient_occlusion
+                                             (rfstudio/graphics/_mesh/_triangle_mesh.py:108-114, 616-678): per-face ambient
+                                             occlusion by shadow segments on a MeshBVH instead of 128 rasterized views, the two
+                                             visibility modes of the shading kernel (the second is spelled 'screen'; the screen-space
+                                             map itself, ShadingContext.ssao, is not provided), and the Monte-Carlo shader composed
+                                             from env_shade and the denoiser
   envshade.env_shade / LatLngEnvMap / make_perms, RenderableAttrs.splat_mc
                                           == optix_env_shade, TextureLatLng.compute_pdf_ and RenderableAttrs.splat_mc without the denoiser
                                              (rfstudio/graphics/_mesh/_optix/ops.py, _texture.py:287-305, rfstudio/model/geosplat.py:134-244):
@@ -93,7 +103,9 @@ from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topolog
                          silhouette_loss, visible_faces)
 from .meshreg import (MeshRegTopology, laplacian_smooth_loss, mesh_edge_loss, mesh_normal_consistency,  # noqa: F401
                       mesh_regularizers)
+from .meshmc import render_mesh_mc  # noqa: F401
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
+from .occlusion import ambient_occlusion, face_ambient_occlusion  # noqa: F401
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .raytrace import MeshBVH, shadow_visibility  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401

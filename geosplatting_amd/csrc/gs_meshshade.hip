@@ -209,10 +209,13 @@ __device__ __forceinline__ void ms_pre(const float* pos, const float* nrm, const
     } else { t.vis = 1.0f; t.vis_pass = false; }
 }
 
+// VM: 0 the two modes of MsCfg (GS_OCC_TEXTURE / GS_OCC_NONE, the code and the bits these kernels always had); GS_OCC_AO /
+// GS_OCC_SCREEN: v = max(vis_map[p], min_visibility) scales the diffuse term alone / the whole colour.  vis_map carries no gradient.
+template <int VM>
 __global__ void __launch_bounds__(256)
 meshshade_fwd_kernel(long long P, const float* __restrict__ rast, const float* __restrict__ position, const float* __restrict__ normal,
                      const float* __restrict__ uv, Tex2Dev kd, Tex2Dev ks, const float* __restrict__ cam_pos, EnvDev env, MsCfg cfg,
-                     float* __restrict__ color)
+                     const float* __restrict__ vis_map, float* __restrict__ color)
 {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
@@ -227,7 +230,14 @@ meshshade_fwd_kernel(long long P, const float* __restrict__ rast, const float* _
         cube_fetch<false>(env.base, env.base_res, t.n, ld, dd, fp);
         cube_mip_fetch<false>(env, t.refl, t.mip, ls);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) out[c] = (ld[c] * t.diff[c] + ls.out[c] * (t.spec[c] * t.fg[0] + t.fg[1])) * t.vis;
+        for (int c = 0; c < 3; ++c) {
+            if (VM == 0) out[c] = (ld[c] * t.diff[c] + ls.out[c] * (t.spec[c] * t.fg[0] + t.fg[1])) * t.vis;
+            else {
+                const float v = fmaxf(vis_map[p], cfg.min_visibility);
+                if (VM == GS_OCC_AO) out[c] = ld[c] * t.diff[c] * v + ls.out[c] * (t.spec[c] * t.fg[0] + t.fg[1]);
+                else out[c] = (ld[c] * t.diff[c] + ls.out[c] * (t.spec[c] * t.fg[0] + t.fg[1])) * v;
+            }
+        }
     }
     color[3 * p] = out[0]; color[3 * p + 1] = out[1]; color[3 * p + 2] = out[2];
 }
@@ -270,10 +280,11 @@ __device__ __forceinline__ void ms_tex_scatter(float* glob, float* s_grad, int l
     }
 }
 
+template <int VM>
 __global__ void __launch_bounds__(GS_MS_BLOCK)
 meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* __restrict__ position, const float* __restrict__ normal,
                      const float* __restrict__ uv, Tex2Dev kd, Tex2Dev ks, const float* __restrict__ cam_pos, EnvDev env, MsCfg cfg,
-                     const float* __restrict__ d_color, float* __restrict__ d_position, float* __restrict__ d_normal,
+                     const float* __restrict__ vis_map, const float* __restrict__ d_color, float* __restrict__ d_position, float* __restrict__ d_normal,
                      float* __restrict__ d_uv, MsGradDev mg, EnvGradDev eg)
 {
     extern __shared__ __attribute__((aligned(16))) float s_grad[];
@@ -304,6 +315,10 @@ meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* _
                 l0 = sel.l0; l1 = sel.l1; f = sel.f;
                 const bool clamped = sel.clamped;
                 float refl_c[3];
+                // GS_OCC_SCREEN: the map's visibility v, a constant of the backward pass, takes the place of t.vis (which is 1 without
+                // GS_OCC_TEXTURE); the chain rule below stays the expression tree it always was, so a map of ones gives the bits of
+                // GS_OCC_NONE.  (GS_OCC_AO runs instantiation 0 and meshshade_ao_fix_kernel after it.)
+                if (VM == GS_OCC_SCREEN) t.vis = fmaxf(vis_map[p], cfg.min_visibility);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     refl_c[c] = t.spec[c] * t.fg[0] + t.fg[1];
@@ -393,14 +408,116 @@ meshshade_bwd_kernel(long long P, const float* __restrict__ rast, const float* _
     env_lds_flush(s_grad, eg, env);
 }
 
-static int meshshade_check(const char* fn, int H, int W, int kd_h, int kd_w, int ks_h, int ks_w, int occlusion, const GsEnv* env, EnvDev& e)
+// GS_OCC_AO, backward.  colour_ao = colour_none + (v - 1) l_diff diff, so the gradient is that of GS_OCC_NONE -- instantiation 0 of the
+// kernel above, the very code 'none' runs, launched first -- plus the gradient of the second term, added here: to the base texels and
+// the normal through the diffuse lookup, to kd, to the metallic channel of ks, and to uv through the two texture lookups; nothing
+// depends on the position.  A pixel with v = 1 adds nothing at all, so a map of ones leaves the bits of 'none'.  The skeleton
+// (persistent blocks, private LDS copies, wave-wide commits, one flush) is meshshade_bwd_kernel's, with its launch configuration.
+__global__ void __launch_bounds__(GS_MS_BLOCK)
+meshshade_ao_fix_kernel(long long P, const float* __restrict__ rast, const float* __restrict__ position, const float* __restrict__ normal,
+                        const float* __restrict__ uv, Tex2Dev kd, Tex2Dev ks, const float* __restrict__ cam_pos, EnvDev env, MsCfg cfg,
+                        const float* __restrict__ vis_map, const float* __restrict__ d_color, float* __restrict__ d_normal,
+                        float* __restrict__ d_uv, MsGradDev mg, EnvGradDev eg)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_grad[];
+    for (int i = threadIdx.x; i < eg.lds_floats; i += blockDim.x) s_grad[i] = 0.0f;
+    __syncthreads();
+    float* const stage = s_grad + eg.stage_off + (threadIdx.x >> 6) * 640;
+    const float cam[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
+    const long long span = (long long)gridDim.x * blockDim.x;
+    const int n_iter = (int)((P + span - 1) / span);                  // wave-uniform: every lane reaches the wave-wide commits
+    for (int it = 0; it < n_iter; ++it) {
+        const long long p = it * span + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        bool act = false;
+        MsPre t;
+        t.kd_fp = Tex2Fp{}; t.ks_fp = Tex2Fp{};
+        CubeFp fp_b{};
+        float v_kd[3] = { 0, 0, 0 }, v_ks[3] = { 0, 0, 0 }, v_ld[3] = { 0, 0, 0 };
+        if (p < P) {
+            float pos[3], nrm[3], q[2];
+            const bool shaded = ms_load_pixel(p, rast, position, normal, uv, pos, nrm, q);
+            const float g[3] = { d_color[3 * p], d_color[3 * p + 1], d_color[3 * p + 2] };
+            const float s = fmaxf(vis_map[p], cfg.min_visibility) - 1.0f;
+            if (shaded && s != 0.0f && (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f)) {
+                act = true;
+                ms_pre(pos, nrm, q, kd, ks, cam, env, cfg, t);
+                float gs[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { gs[c] = g[c] * s; v_ld[c] = gs[c] * t.diff[c]; }
+                float ld[3], s_b, vd_b[3];
+                cube_fetch_vjp(env.base, env.base_res, t.n, v_ld, ld, s_b, vd_b, fp_b);
+                const float metal = t.ks[2];
+                float v_metal = 0.0f, gu = 0.0f, gv = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float v_diff = gs[c] * ld[c];
+                    v_kd[c] = v_diff * (1.0f - metal);
+                    v_metal -= v_diff * t.kd[c];
+                    gu += v_kd[c] * t.kd_du[c]; gv += v_kd[c] * t.kd_dv[c];
+                }
+                v_ks[2] = v_metal;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) d_normal[3 * p + k] += t.sgn * vd_b[k];
+                d_uv[2 * p] += gu * ms_sample_scale(kd.W) + v_metal * t.ks_du[2] * ms_sample_scale(ks.W);
+                d_uv[2 * p + 1] += gv * ms_sample_scale(kd.H) + v_metal * t.ks_dv[2] * ms_sample_scale(ks.H);
+            }
+        }
+        ms_tex_scatter(mg.kd, s_grad, mg.lds_kd, kd, t.kd_fp, v_kd, act, stage);
+        ms_tex_scatter(mg.ks, s_grad, mg.lds_ks, ks, t.ks_fp, v_ks, act, stage);
+        const CommitDevice commit{};
+        env_scatter_wave(eg, s_grad, stage, commit, true, act ? 0 : -1, fp_b, v_ld, 1.0f);
+    }
+    __syncthreads();
+    if (mg.lds_kd >= 0) {
+        const int cnt = 3 * kd.W * kd.H;
+        for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_kd + i]; if (v != 0.0f) gs_atomic_add(mg.kd + i, v); }
+    }
+    if (mg.lds_ks >= 0) {
+        const int cnt = 3 * ks.W * ks.H;
+        for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const float v = s_grad[mg.lds_ks + i]; if (v != 0.0f) gs_atomic_add(mg.ks + i, v); }
+    }
+    env_lds_flush(s_grad, eg, env);
+}
+
+static int meshshade_check(const char* fn, int H, int W, int kd_h, int kd_w, int ks_h, int ks_w, int occlusion, bool with_map,
+                           const GsEnv* env, EnvDev& e)
 {
     if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) { gs_set_error("%s: bad image size", fn); return GS_EINVAL; }
     if (kd_h < 1 || kd_w < 1 || ks_h < 1 || ks_w < 1 || (long long)kd_h * kd_w > (1ll << 28) || (long long)ks_h * ks_w > (1ll << 28)) {
         gs_set_error("%s: bad texture size", fn); return GS_EINVAL;
     }
-    if (occlusion != GS_OCC_TEXTURE && occlusion != GS_OCC_NONE) { gs_set_error("%s: unknown occlusion mode", fn); return GS_EINVAL; }
+    const bool known = with_map ? (occlusion == GS_OCC_AO || occlusion == GS_OCC_SCREEN) : (occlusion == GS_OCC_TEXTURE || occlusion == GS_OCC_NONE);
+    if (!known) { gs_set_error("%s: unknown occlusion mode", fn); return GS_EINVAL; }
     if (env_to_dev(env, e) != 0 || e.L < 2 || e.lut_res < 1 || e.base_res < 1) { gs_set_error("%s: bad GsEnv", fn); return GS_EINVAL; }
+    return GS_OK;
+}
+
+// the body of gs_meshshade_fwd and gs_meshshade_vis_fwd (vis == NULL: the former)
+static int meshshade_fwd_impl(const char* fn, int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                              int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                              const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* vis, bool with_map,
+                              float* color, void* stream)
+{
+    EnvDev e;
+    { const int rc = meshshade_check(fn, H, W, kd_h, kd_w, ks_h, ks_w, occlusion, with_map, env, e); if (rc != GS_OK) return rc; }
+    if (!(rast != nullptr && position != nullptr && normal != nullptr && uv != nullptr && kd != nullptr && ks != nullptr &&
+          cam_pos != nullptr && color != nullptr && (!with_map || vis != nullptr))) {
+        gs_set_error("%s: null pointer", fn); return GS_EINVAL;
+    }
+    const long long P = (long long)H * W;
+    const Tex2Dev tkd = { kd, kd_w, kd_h }, tks = { ks, ks_w, ks_h };
+    const MsCfg cfg = { occlusion, min_visibility, bend_back_normal ? 1 : 0 };
+    const dim3 grid(gs_cdiv(P, 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (!with_map)
+        hipLaunchKernelGGL(meshshade_fwd_kernel<0>, grid, block, 0, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg,
+                           (const float*)nullptr, color);
+    else if (occlusion == GS_OCC_AO)
+        hipLaunchKernelGGL(meshshade_fwd_kernel<GS_OCC_AO>, grid, block, 0, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg, vis, color);
+    else
+        hipLaunchKernelGGL(meshshade_fwd_kernel<GS_OCC_SCREEN>, grid, block, 0, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg, vis,
+                           color);
+    GS_CHECK_LAUNCH();
     return GS_OK;
 }
 
@@ -408,33 +525,49 @@ extern "C" int gs_meshshade_fwd(int H, int W, const float* rast, const float* po
                                 int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
                                 const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, float* color, void* stream)
 {
-    EnvDev e;
-    { const int rc = meshshade_check(__func__, H, W, kd_h, kd_w, ks_h, ks_w, occlusion, env, e); if (rc != GS_OK) return rc; }
-    GS_CHECK_ARG(rast != nullptr && position != nullptr && normal != nullptr && uv != nullptr && kd != nullptr && ks != nullptr &&
-                 cam_pos != nullptr && color != nullptr, "null pointer");
-    const long long P = (long long)H * W;
-    const Tex2Dev tkd = { kd, kd_w, kd_h }, tks = { ks, ks_w, ks_h };
-    const MsCfg cfg = { occlusion, min_visibility, bend_back_normal ? 1 : 0 };
-    hipLaunchKernelGGL(meshshade_fwd_kernel, dim3(gs_cdiv(P, 256)), dim3(256), 0, (hipStream_t)stream, P, rast, position, normal, uv,
-                       tkd, tks, cam_pos, e, cfg, color);
+    return meshshade_fwd_impl(__func__, H, W, rast, position, normal, uv, kd_h, kd_w, kd, ks_h, ks_w, ks, cam_pos, env, occlusion,
+                              min_visibility, bend_back_normal, nullptr, false, color, stream);
+}
+
+extern "C" int gs_meshshade_vis_fwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                                    int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                                    const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* vis,
+                                    float* color, void* stream)
+{
+    return meshshade_fwd_impl(__func__, H, W, rast, position, normal, uv, kd_h, kd_w, kd, ks_h, ks_w, ks, cam_pos, env, occlusion,
+                              min_visibility, bend_back_normal, vis, true, color, stream);
+}
+
+template <int VM>
+static int meshshade_bwd_launch(int blocks, size_t lds_bytes, hipStream_t s, long long P, const float* rast, const float* position,
+                                const float* normal, const float* uv, Tex2Dev tkd, Tex2Dev tks, const float* cam_pos, const EnvDev& e,
+                                const MsCfg& cfg, const float* vis, const float* d_color, float* d_position, float* d_normal, float* d_uv,
+                                const MsGradDev& mg, const EnvGradDev& eg)
+{
+    GS_CHECK_HIP(hipFuncSetAttribute((const void*)meshshade_bwd_kernel<VM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(meshshade_bwd_kernel<VM>, dim3(blocks), dim3(GS_MS_BLOCK), lds_bytes, s, P, rast, position, normal, uv, tkd, tks,
+                       cam_pos, e, cfg, vis, d_color, d_position, d_normal, d_uv, mg, eg);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
 
-extern "C" int gs_meshshade_bwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
-                                int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
-                                const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* d_color,
-                                float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks, const GsEnvGrad* env_grad,
-                                void* stream)
+// the body of gs_meshshade_bwd and gs_meshshade_vis_bwd
+static int meshshade_bwd_impl(const char* fn, int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                              int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                              const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* vis, bool with_map,
+                              const float* d_color, float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks,
+                              const GsEnvGrad* env_grad, void* stream)
 {
     EnvDev e;
-    { const int rc = meshshade_check(__func__, H, W, kd_h, kd_w, ks_h, ks_w, occlusion, env, e); if (rc != GS_OK) return rc; }
-    GS_CHECK_ARG(rast != nullptr && position != nullptr && normal != nullptr && uv != nullptr && kd != nullptr && ks != nullptr &&
-                 cam_pos != nullptr && d_color != nullptr && d_position != nullptr && d_normal != nullptr && d_uv != nullptr &&
-                 d_kd != nullptr && d_ks != nullptr && env_grad != nullptr && env_grad->base != nullptr, "null pointer");
+    { const int rc = meshshade_check(fn, H, W, kd_h, kd_w, ks_h, ks_w, occlusion, with_map, env, e); if (rc != GS_OK) return rc; }
+    if (!(rast != nullptr && position != nullptr && normal != nullptr && uv != nullptr && kd != nullptr && ks != nullptr &&
+          cam_pos != nullptr && d_color != nullptr && d_position != nullptr && d_normal != nullptr && d_uv != nullptr &&
+          d_kd != nullptr && d_ks != nullptr && env_grad != nullptr && env_grad->base != nullptr && (!with_map || vis != nullptr))) {
+        gs_set_error("%s: null pointer", fn); return GS_EINVAL;
+    }
     const long long P = (long long)H * W;
     EnvGradDev eg;
-    { const int rc = env_grad_to_dev(__func__, env_grad, e, GS_MODE_PBR, eg); if (rc != GS_OK) return rc; }
+    { const int rc = env_grad_to_dev(fn, env_grad, e, GS_MODE_PBR, eg); if (rc != GS_OK) return rc; }
     eg.priv = nullptr; eg.priv_stride = 0; eg.priv_base = -1;
     for (int l = 0; l < GS_MAX_LEVELS; ++l) eg.priv_level[l] = -1;
     // LDS layout: the two textures, the base level, then the pyramid from its coarsest level up, while they fit
@@ -459,9 +592,42 @@ extern "C" int gs_meshshade_bwd(int H, int W, const float* rast, const float* po
     const int blocks = want < max_blocks ? want : max_blocks;
     const MsCfg cfg = { occlusion, min_visibility, bend_back_normal ? 1 : 0 };
     const Tex2Dev tkd = { kd, kd_w, kd_h }, tks = { ks, ks_w, ks_h };
-    GS_CHECK_HIP(hipFuncSetAttribute((const void*)meshshade_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(meshshade_bwd_kernel, dim3(blocks), dim3(GS_MS_BLOCK), lds_bytes, (hipStream_t)stream, P, rast, position, normal, uv,
-                       tkd, tks, cam_pos, e, cfg, d_color, d_position, d_normal, d_uv, mg, eg);
-    GS_CHECK_LAUNCH();
-    return GS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!with_map)
+        return meshshade_bwd_launch<0>(blocks, lds_bytes, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg, nullptr, d_color,
+                                       d_position, d_normal, d_uv, mg, eg);
+    if (occlusion == GS_OCC_AO) {
+        const int rc = meshshade_bwd_launch<0>(blocks, lds_bytes, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg, nullptr, d_color,
+                                               d_position, d_normal, d_uv, mg, eg);
+        if (rc != GS_OK) return rc;
+        GS_CHECK_HIP(hipFuncSetAttribute((const void*)meshshade_ao_fix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        hipLaunchKernelGGL(meshshade_ao_fix_kernel, dim3(blocks), dim3(GS_MS_BLOCK), lds_bytes, s, P, rast, position, normal, uv, tkd, tks,
+                           cam_pos, e, cfg, vis, d_color, d_normal, d_uv, mg, eg);
+        GS_CHECK_LAUNCH();
+        return GS_OK;
+    }
+    return meshshade_bwd_launch<GS_OCC_SCREEN>(blocks, lds_bytes, s, P, rast, position, normal, uv, tkd, tks, cam_pos, e, cfg, vis, d_color,
+                                               d_position, d_normal, d_uv, mg, eg);
+}
+
+extern "C" int gs_meshshade_bwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                                int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                                const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* d_color,
+                                float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks, const GsEnvGrad* env_grad,
+                                void* stream)
+{
+    return meshshade_bwd_impl(__func__, H, W, rast, position, normal, uv, kd_h, kd_w, kd, ks_h, ks_w, ks, cam_pos, env, occlusion,
+                              min_visibility, bend_back_normal, nullptr, false, d_color, d_position, d_normal, d_uv, d_kd, d_ks, env_grad,
+                              stream);
+}
+
+extern "C" int gs_meshshade_vis_bwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                                    int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                                    const GsEnv* env, int occlusion, float min_visibility, int bend_back_normal, const float* vis,
+                                    const float* d_color, float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks,
+                                    const GsEnvGrad* env_grad, void* stream)
+{
+    return meshshade_bwd_impl(__func__, H, W, rast, position, normal, uv, kd_h, kd_w, kd, ks_h, ks_w, ks, cam_pos, env, occlusion,
+                              min_visibility, bend_back_normal, vis, true, d_color, d_position, d_normal, d_uv, d_kd, d_ks, env_grad,
+                              stream);
 }

@@ -9,8 +9,13 @@ project's, the kernels are csrc/gs_meshraster.hip and csrc/gs_meshaa.hip.
   mesh_edge_topology(faces)                                                         -> EdgeTopology
   antialias(color, rast, verts_cam, faces, camera_or_intrinsics, *, topology, cull, near, near_clip) -> [H,W,C]
   render_mesh(vertices, faces, camera, *, outputs, normal_type, cull, vertex_normals, near_clip, antialias,
-              kd, ks, uvs, envmap, occlusion, min_visibility, bend_back_normal)     -> dict of maps ('color': meshshade.py)
+              kd, ks, uvs, envmap, occlusion, min_visibility, bend_back_normal,
+              ao, bvh, visibility)                                                  -> dict of maps ('color': meshshade.py;
+                                                                                       'ao': occlusion.py)
   visible_faces(vertices, faces, camera, *, near_clip)                              -> sorted unique face ids
+`render_mesh` with occlusion='ao' is the reference's PBRShader(occlusion_type='ao') (rfstudio/graphics/shaders.py:92-94) and its
+output 'ao' is ShadingContext.ao; occlusion='screen' shades with a map the caller passes (the reference's 'ssao' map is not provided);
+the Monte-Carlo shader is meshmc.py.
   silhouette_loss(alpha, target_mask)                                               -> scalar
 
 Semantics of `rasterize_mesh`
@@ -358,7 +363,8 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
                 normal_type: str = "vertex", cull: str = "back", vertex_normals: Optional[Tensor] = None,
                 near: float = 1e-2, near_clip: bool = False, antialias: bool = False, topology: Optional[EdgeTopology] = None,
                 kd=None, ks=None, uvs: Optional[Tensor] = None, envmap=None, occlusion: str = "texture",
-                min_visibility: float = 0.0, bend_back_normal: bool = False) -> Dict[str, Tensor]:
+                min_visibility: float = 0.0, bend_back_normal: bool = False, ao: Optional[Tensor] = None, bvh=None,
+                visibility: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """World-space mesh seen from `camera` -> {'rast' [H,W,4] and the requested maps}:
       depth  [H,W,1]  interpolated view depth (DepthShader), 0 where empty
       normal [H,W,3]  world-space normals (NormalShader): 'vertex' safe_normalize of the interpolated `vertex_normals` (default: the
@@ -369,28 +375,38 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
                       interpolated `uvs` [F,3,2] (per face-vertex), with the Texture2D `kd`, `ks` under the TextureSplitSum `envmap`;
                       `occlusion`, `min_visibility`, `bend_back_normal` as there.  `uvs=None` is allowed only with 1x1 textures and means
                       zeros (PrettyShader).  0 where empty.  Differentiable in the textures, the environment and `vertices`.
+                      occlusion='ao' shades with the map 'ao' below, occlusion='screen' with the map `visibility` [H,W] (required
+                      there, refused otherwise).
+      ao     [H,W,1]  ShadingContext.ao: the per-face ambient occlusion `ao` [F] (default: occlusion.face_ambient_occlusion of the mesh,
+                      on `bvh` when one is passed) looked up through the face ids, face 0 where empty as face_attribute_map does; no
+                      gradient, not antialiased
     depth and normal are differentiable in `vertices` (and `vertex_normals`); coverage is not, unless `antialias` is set: then the
     requested maps among depth, normal, color and alpha go through `antialias` together as one image (the way the reference
     antialiases its rgba), normal is normalised again, and alpha lies strictly between 0 and 1 along the outline with a gradient to
     the vertices of the outline's faces.  face and rast are never changed.  `topology`: mesh_edge_topology(faces), to reuse it.
     `near_clip`: faces that cross the near plane are clipped instead of dropped (module docstring), for cameras inside the mesh."""
     _lib.require_cuda(vertices, faces)
-    unknown = set(outputs) - {"depth", "normal", "alpha", "face", "color"}
+    unknown = set(outputs) - {"depth", "normal", "alpha", "face", "color", "ao"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
     if normal_type not in ("vertex", "flat"):
         raise ValueError("normal_type must be 'vertex' or 'flat'")
     want_color = "color" in outputs
     if want_color:
-        from .meshshade import _OCCLUSION, _as_texture
+        from .meshshade import _as_texture, check_occlusion
         if kd is None or ks is None or envmap is None:
             raise ValueError("outputs 'color' needs kd, ks and envmap")
-        if occlusion not in _OCCLUSION:
-            raise ValueError("occlusion must be 'texture' or 'none' ('ao' and 'ssao' are not provided)")
+        check_occlusion(occlusion)
         kd, ks = _as_texture(kd, "kd"), _as_texture(ks, "ks")
         if uvs is None and not (kd.data.shape[:2] == (1, 1) and ks.data.shape[:2] == (1, 1)):
             raise ValueError("uvs=None is allowed only with 1x1 textures")
     f32 = _faces32(faces)
+    want_ao = "ao" in outputs or (want_color and occlusion == "ao")
+    if (visibility is not None) != (want_color and occlusion == "screen"):
+        raise ValueError("visibility [H,W] is the map of outputs 'color' with occlusion='screen': required there, refused otherwise")
+    _lib.require_cuda(ao)
+    if ao is not None and (not isinstance(ao, Tensor) or tuple(ao.shape) != (f32.shape[0],)):
+        raise ValueError(f"ao must be a tensor [F] = [{f32.shape[0]}], got {tuple(ao.shape) if isinstance(ao, Tensor) else type(ao).__name__}")
     if want_color and uvs is not None and tuple(uvs.shape) != (f32.shape[0], 3, 2):
         raise _lib.GeoSplatHipError("uvs must be [F,3,2]")
     vc = to_camera_space(vertices, camera)
@@ -411,12 +427,20 @@ def render_mesh(vertices: Tensor, faces: Tensor, camera: Camera, *, outputs: Seq
             normal_map = fn[(rast[..., 3].long() - 1).clamp_min(0)]            # (face_attribute_map: face 0 where empty)
         if "normal" in outputs:
             out["normal"] = normal_map
+    ao_map = None
+    if want_ao:
+        from .occlusion import face_ambient_occlusion
+        per_face = ao.detach().float() if ao is not None else face_ambient_occlusion(vertices, f32, bvh)
+        ao_map = per_face[(rast[..., 3].long() - 1).clamp_min(0)]                     # (face_attribute_map: face 0 where empty)
+        if "ao" in outputs:
+            out["ao"] = ao_map[..., None]
     if want_color:
         from .meshshade import shade_pixels
         position = interpolate(vertices.float().contiguous(), rast, f32)
         uv = interpolate(uvs.float(), rast, f32) if uvs is not None else torch.zeros(*rast.shape[:2], 2, device=rast.device)
         out["color"] = shade_pixels(position, normal_map, uv, rast, kd, ks, camera.c2w[:, 3].to(rast.device), envmap,
-                                    occlusion=occlusion, min_visibility=min_visibility, bend_back_normal=bend_back_normal)
+                                    occlusion=occlusion, min_visibility=min_visibility, bend_back_normal=bend_back_normal,
+                                    visibility=ao_map if occlusion == "ao" else visibility)
     if "alpha" in outputs:
         out["alpha"] = (rast[..., 3:] > 0).float()
     if "face" in outputs:

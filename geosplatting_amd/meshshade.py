@@ -15,8 +15,8 @@ csrc/gs_meshshade.hip; the semantics are this project's and are stated in full i
   Texture2D(data [Ht,Wt,3])
       .from_constants((r, g, b), device=) a 1x1 texture;  .sample(uv) the wrap lookup at (u (1 - 1/Wt) + 0.5/Wt,
       v (1 - 1/Ht) + 0.5/Ht)  (rfstudio/graphics/_mesh/_texture.py:168-175).
-  shade_pixels(position, normal, uv, rast, kd, ks, camera_pos, envmap, *, occlusion='texture' | 'none', min_visibility=0.0,
-               bend_back_normal=False, fg_lut=None) -> colour [H,W,3]
+  shade_pixels(position, normal, uv, rast, kd, ks, camera_pos, envmap, *, occlusion='texture' | 'none' | 'ao' | 'screen',
+               visibility=None, min_visibility=0.0, bend_back_normal=False, fg_lut=None) -> colour [H,W,3]
       PBRShader.shade on a G-buffer: position [H,W,3] world space, normal [H,W,3] unit vectors in world space, uv [H,W,2],
       kd / ks Texture2D (ks = occlusion, roughness, metallic -- no min_roughness / max_metallic remap).  Per pixel with
       rast[..., 3] > 0:
@@ -28,9 +28,15 @@ csrc/gs_meshshade.hip; the semantics are this project's and are stated in full i
         l_diff = cube(base, n);  l_spec = cube_mip(levels, refl, mip_from_roughness(rough))  (TextureSplitSum.sample, no transform)
         visibility = max(1 - ks[0], min_visibility) for 'texture', 1 for 'none'
         colour = (l_diff diff + l_spec (spec fg[0] + fg[1])) visibility
+      occlusion 'ao' and 'screen' (PBRShader(occlusion_type='ao' | 'ssao'), shaders.py:92-104) take the map `visibility` [H,W] --
+      occlusion.face_ambient_occlusion through the face ids, or any map of the caller's -- and v = max(visibility, min_visibility):
+        'ao'      colour = l_diff diff v + l_spec (spec fg[0] + fg[1])            (the diffuse term alone)
+        'screen'  colour = (l_diff diff + l_spec (spec fg[0] + fg[1])) v
+      `visibility` is required for these two and refused for the others; it receives no gradient.  A map of ones gives the bits of
+      'none', forward and backward.  The reference spells the second mode 'ssao'; that name keeps raising ValueError here.
       Pixels with rast[..., 3] == 0 get colour 0 and no gradient anywhere -- a documented difference: the reference shades them from
       face 0 and hides them behind alpha 0.  A pixel with a non-finite position, normal or uv is treated the same way.
-      occlusion 'ao' / 'ssao' and TextureSG environments are not provided.
+      TextureSG environments are not provided.
       Gradients go to position, normal, uv, kd.data, ks.data, envmap.base and every envmap.levels[l]; every selection (texel, LUT
       cell, cube face, mip level, the ndv and visibility clamps, the bend) takes the derivative of the selected piece, 0 where a
       clamp is active.  The forward and the per-pixel gradients are bit-identical between runs; the texel gradients are sums of
@@ -50,7 +56,8 @@ from .shading import _make_env, get_fg_lut
 from .splitsum import TextureSplitSum
 
 _BOUNDARY = {"wrap": 0, "clamp": 1}
-_OCCLUSION = {"texture": 0, "none": 1}
+_OCCLUSION = {"texture": 0, "none": 1, "ao": 2, "screen": 3}
+_WITH_MAP = ("ao", "screen")
 
 
 class _Texture2DFn(torch.autograd.Function):
@@ -129,9 +136,14 @@ def _as_texture(t, name: str) -> Texture2D:
     raise L.GeoSplatHipError(f"{name} must be a Texture2D or a tensor [Ht,Wt,3]")
 
 
+def check_occlusion(occlusion: str) -> None:
+    if occlusion not in _OCCLUSION:
+        raise ValueError("occlusion must be 'texture', 'none', 'ao' or 'screen' (the reference's 'ssao' is spelled 'screen' here)")
+
+
 class _ShadePixels(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, position, normal, uv, rast, kd, ks, cam_pos, lut, base, cfg, *levels):
+    def forward(ctx, position, normal, uv, rast, kd, ks, cam_pos, lut, base, cfg, vis, *levels):
         position, normal, uv, rast = (t.detach().contiguous() for t in (position, normal, uv, rast))
         kd, ks, cam_pos, base = kd.detach().contiguous(), ks.detach().contiguous(), cam_pos.detach().contiguous(), base.detach().contiguous()
         levels = [l.detach().contiguous() for l in levels]
@@ -139,11 +151,17 @@ class _ShadePixels(torch.autograd.Function):
         H, W = rast.shape[:2]
         color = torch.empty(H, W, 3, dtype=torch.float32, device=rast.device)
         e = _make_env(lut, TextureSplitSum(base, levels, env_min_r, env_max_r))
-        L.check(L.lib().gs_meshshade_fwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
-                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
-                                         int(bend), L.ptr(color), L.stream()), "gs_meshshade_fwd")
+        if vis is None:
+            L.check(L.lib().gs_meshshade_fwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
+                                             ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
+                                             int(bend), L.ptr(color), L.stream()), "gs_meshshade_fwd")
+        else:
+            vis = vis.detach().contiguous()
+            L.check(L.lib().gs_meshshade_vis_fwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1],
+                                                 L.ptr(kd), ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion,
+                                                 min_visibility, int(bend), L.ptr(vis), L.ptr(color), L.stream()), "gs_meshshade_vis_fwd")
         ctx.save_for_backward(position, normal, uv, rast, kd, ks, cam_pos, lut, base, *levels)
-        ctx.cfg = cfg
+        ctx.cfg, ctx.vis = cfg, vis
         return color
 
     @staticmethod
@@ -160,24 +178,36 @@ class _ShadePixels(torch.autograd.Function):
         eg.base = d_base.data_ptr()
         for i, t in enumerate(d_levels):
             eg.levels[i] = t.data_ptr()
-        L.check(L.lib().gs_meshshade_bwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
-                                         ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
-                                         int(bend), L.ptr(g), L.ptr(d_position), L.ptr(d_normal), L.ptr(d_uv), L.ptr(d_kd), L.ptr(d_ks),
-                                         C.byref(eg), L.stream()), "gs_meshshade_bwd")
-        return (d_position, d_normal, d_uv, None, d_kd, d_ks, None, None, d_base, None, *d_levels)
+        if ctx.vis is None:
+            L.check(L.lib().gs_meshshade_bwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1], L.ptr(kd),
+                                             ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion, min_visibility,
+                                             int(bend), L.ptr(g), L.ptr(d_position), L.ptr(d_normal), L.ptr(d_uv), L.ptr(d_kd), L.ptr(d_ks),
+                                             C.byref(eg), L.stream()), "gs_meshshade_bwd")
+        else:
+            L.check(L.lib().gs_meshshade_vis_bwd(H, W, L.ptr(rast), L.ptr(position), L.ptr(normal), L.ptr(uv), kd.shape[0], kd.shape[1],
+                                                 L.ptr(kd), ks.shape[0], ks.shape[1], L.ptr(ks), L.ptr(cam_pos), C.byref(e), occlusion,
+                                                 min_visibility, int(bend), L.ptr(ctx.vis), L.ptr(g), L.ptr(d_position), L.ptr(d_normal),
+                                                 L.ptr(d_uv), L.ptr(d_kd), L.ptr(d_ks), C.byref(eg), L.stream()), "gs_meshshade_vis_bwd")
+        return (d_position, d_normal, d_uv, None, d_kd, d_ks, None, None, d_base, None, None, *d_levels)
 
 
 def shade_pixels(position: Tensor, normal: Tensor, uv: Tensor, rast: Tensor, kd, ks, camera_pos: Tensor, envmap: TextureSplitSum, *,
                  occlusion: str = "texture", min_visibility: float = 0.0, bend_back_normal: bool = False,
-                 fg_lut: Optional[Tensor] = None) -> Tensor:
+                 fg_lut: Optional[Tensor] = None, visibility: Optional[Tensor] = None) -> Tensor:
     """PBRShader.shade on a G-buffer -> colour [H,W,3] (module docstring).  `kd`, `ks`: Texture2D (or [Ht,Wt,3] tensors);
-    differentiable in position, normal, uv, kd.data, ks.data, envmap.base and envmap.levels."""
-    if occlusion not in _OCCLUSION:
-        raise ValueError("occlusion must be 'texture' or 'none' ('ao' and 'ssao' are not provided)")
+    differentiable in position, normal, uv, kd.data, ks.data, envmap.base and envmap.levels.  `visibility` [H,W]: the map of
+    occlusion 'ao' / 'screen' (required there, refused otherwise; no gradient)."""
+    check_occlusion(occlusion)
+    if (occlusion in _WITH_MAP) != (visibility is not None):
+        raise ValueError(f"occlusion={occlusion!r} needs a visibility map [H,W]" if visibility is None else
+                         f"visibility is taken by occlusion 'ao' and 'screen' only, not by {occlusion!r}")
+    if visibility is not None and (not isinstance(visibility, Tensor) or tuple(visibility.shape) != tuple(rast.shape[:2])):
+        raise ValueError(f"visibility must be a tensor [H,W] with rast's H and W, got "
+                         f"{tuple(visibility.shape) if isinstance(visibility, Tensor) else type(visibility).__name__}")
     if not isinstance(envmap, TextureSplitSum):
         raise L.GeoSplatHipError("envmap must be a TextureSplitSum")
     kd, ks = _as_texture(kd, "kd"), _as_texture(ks, "ks")
-    L.require_cuda(position, normal, uv, rast, kd.data, ks.data, camera_pos, envmap.base, *envmap.levels)
+    L.require_cuda(position, normal, uv, rast, kd.data, ks.data, camera_pos, envmap.base, *envmap.levels, visibility)
     if rast.ndim != 3 or rast.shape[2] != 4 or rast.shape[0] < 1 or rast.shape[1] < 1:
         raise L.GeoSplatHipError("rast must be [H,W,4]")
     H, W = rast.shape[:2]
@@ -190,4 +220,5 @@ def shade_pixels(position: Tensor, normal: Tensor, uv: Tensor, rast: Tensor, kd,
     lut = get_fg_lut(rast.device) if fg_lut is None else fg_lut.contiguous()
     cfg = (_OCCLUSION[occlusion], float(min_visibility), bool(bend_back_normal), float(envmap.min_roughness), float(envmap.max_roughness))
     return _ShadePixels.apply(position.float(), normal.float(), uv.float(), rast.float(), kd.data.float(), ks.data.float(),
-                              camera_pos.reshape(3).float(), lut, envmap.base, cfg, *envmap.levels)
+                              camera_pos.reshape(3).float(), lut, envmap.base, cfg,
+                              None if visibility is None else visibility.detach().float(), *envmap.levels)

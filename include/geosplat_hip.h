@@ -1011,6 +1011,27 @@ int gs_meshshade_bwd(int H, int W, const float* rast, const float* position, con
                      const GsEnv* env /*host*/, int occlusion, float min_visibility, int bend_back_normal, const float* d_color,
                      float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks, const GsEnvGrad* env_grad /*host*/,
                      void* stream);
+/* The same shader with a per-pixel visibility map vis [H,W] (PBRShader(occlusion_type='ao' | 'ssao'), shaders.py:92-104): the
+ * per-face values of gs_ray_ao below through the face ids, or any map the caller has.  With v = max(vis[p], min_visibility):
+ *     GS_OCC_AO      colour = l_diff diff v + l_spec (spec fg[0] + fg[1])          (the diffuse term alone)
+ *     GS_OCC_SCREEN  colour = (l_diff diff + l_spec (spec fg[0] + fg[1])) v
+ *   every product rounded once, in this order; ks[0] is not read.  The kernels are those of gs_meshshade_fwd / _bwd, instantiated
+ *   for the mode: a map of ones gives the bits of GS_OCC_NONE, forward and backward, in both modes, and GS_OCC_SCREEN's forward is
+ *   fl(colour of GS_OCC_NONE * v) to the last bit.  Backward: GS_OCC_SCREEN scales the chain by v.  GS_OCC_AO runs the backward of
+ *   GS_OCC_NONE (the same kernel) and a second launch adds the gradient of (v - 1) l_diff diff: to the base texels and the normal
+ *   through the diffuse lookup, to kd, to the metallic channel of ks, and to uv; a pixel with v = 1 adds nothing.  vis is a
+ *   constant: it receives no gradient, and the min_visibility clamp selects nothing that has one.  GS_EINVAL as above, for another mode or a null vis. */
+#define GS_OCC_AO        2
+#define GS_OCC_SCREEN    3
+int gs_meshshade_vis_fwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                         int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                         const GsEnv* env /*host*/, int occlusion, float min_visibility, int bend_back_normal, const float* vis /*[H,W]*/,
+                         float* color, void* stream);
+int gs_meshshade_vis_bwd(int H, int W, const float* rast, const float* position, const float* normal, const float* uv,
+                         int kd_h, int kd_w, const float* kd, int ks_h, int ks_w, const float* ks, const float* cam_pos,
+                         const GsEnv* env /*host*/, int occlusion, float min_visibility, int bend_back_normal, const float* vis /*[H,W]*/,
+                         const float* d_color, float* d_position, float* d_normal, float* d_uv, float* d_kd, float* d_ks,
+                         const GsEnvGrad* env_grad /*host*/, void* stream);
 
 /* ------------------------------------------------------------------ ray-mesh queries: LBVH, shadow and closest-hit rays ------ */
 /* What the reference's OptiX stages get from optix_build_bvh(ctx, vertices, indices, rebuild=1) and from the shadow test of
@@ -1059,6 +1080,35 @@ int gs_ray_occluded(int64_t V, int64_t F, const float* vertices, const int32_t* 
 int gs_ray_closest(int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh /* NULL: brute force */,
                    int64_t P, int S, const float* origins /*[P,3]*/, const float* dirs, int dirs_per_point, float tmin, float tmax,
                    float* t /*[P,S]*/, int32_t* face /*[P,S]*/, float* bary /*[P,S,2]*/, void* stream);
+
+/* ------------------------------------------------------------------ ambient occlusion: rays to targets ------------------------ */
+/* The per-face visibility of the reference's mesh shaders.  csrc/gs_ao.hip; tests/ao_ref.py restates it in float64.  Everything
+ * below is fp32 with contraction off, every operation rounded once, sums of three products as (a + b) + c.  No backward:
+ * TriangleMesh.compute_ambient_occlusion is no_grad and the map is piecewise constant in the geometry.
+ *
+ * gs_ray_ao: cosine-weighted visibility of P points towards S shared target points; what compute_ambient_occlusion
+ *   (rfstudio/graphics/_mesh/_triangle_mesh.py:616-678) computes per face, its cameras being the targets.  The mesh, `bvh` (NULL:
+ *   brute force, the same bits) and the segment test are those of gs_ray_occluded.  positions, normals [P,3]; targets [S,3],
+ *   1 <= S <= 4096.  Per point:
+ *     o = pos + n * offset
+ *     per target k:  d = e_k - o (not normalised);  c = ((n.x d.x + n.y d.y) + n.z d.z) / sqrt((d.x^2 + d.y^2) + d.z^2)
+ *       the target COUNTS iff c > 0 (a NaN does not), with weight w = max(c, 1e-4)
+ *       hit = the ray o + t d meets a face for 0 < t < 1 (gs_ray_occluded with tmin = 0, tmax = 1 on these o and d)
+ *       num += w unless hit;  den += w
+ *     vis[p] = num / max(den, 1e-6);  0 for a point with a non-finite position or normal, or without a counting target.
+ *   Sums: lanes_per_point = G in {1, 16, 64} (0 picks 64 for S >= 64, 16 for S >= 16, else 1) lanes share a point; lane l adds the
+ *   targets k = l, l + G, ... in ascending k, then the lanes are combined by v += shfl_xor(v, o) for o = G/2, ..., 1.  No atomics:
+ *   the same input and G give the same bits.  G changes the order of the sums only.
+ *   log_hit [P,S] uint8 and log_w [P,S] (both or neither; NULL: no log) receive hit and w of every target of a finite point; with
+ *   the log, hit is evaluated for the targets that do not count too (w = 0 there).  Rows of a non-finite point are not written.
+ *   Against the reference: no 1024^2 pixel quantisation of the test; its depth tolerance of 0.02 becomes `offset` along the normal;
+ *   back-facing targets are left out, where the reference counts them as occluded with weight 1e-4.
+ *
+ * GS_EINVAL before touching the device for S outside its range, sizes out of range, a non-finite offset or a null required
+ * pointer.  P == 0 is a no-op. */
+int gs_ray_ao(int64_t V, int64_t F, const float* vertices, const int32_t* faces, const void* bvh /* NULL: brute force */, int64_t P,
+              const float* positions /*[P,3]*/, const float* normals /*[P,3]*/, int S, const float* targets /*[S,3]*/, float offset,
+              int lanes_per_point, float* vis /*[P]*/, uint8_t* log_hit /*[P,S] or NULL*/, float* log_w /*[P,S] or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------ nearest neighbours: uniform grid, Chamfer backward ---------- */
 /* What the reference's geometry metrics get from its brute-force Chamfer kernel (rfstudio/loss/_chamfer) and from Points.k_nearest;
