@@ -83,6 +83,12 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              (rfstudio/model/geosplat_defer.py, rfstudio/trainer/geosplat_defer_trainer.py,
                                              tests/model/test_geosplat_defer.py:345-493): stage-3 training on a stage-2 export with
                                              deferred shading on the frozen mesh, and NVS / relighting / albedo PSNR
+  poisson.splat_to_grid / sample_grid / poisson_indicator / mesh_from_indicator / diff_poisson_surface_recon /
+  mesh_from_oriented_points / remesh_poisson
+                                          == point_rasterize, grid_interp, DPSR.forward, PSR2Mesh, diff_poisson_surface_recon
+                                             (rfstudio/graphics/_mesh/_dpsr/ops.py), TriangleMesh.from_diff_poisson_reconstruction
+                                             (_triangle_mesh.py:301-319) and the Mesh2Mesh task (tests/graphics/test_dpsr.py):
+                                             oriented points -> spectral Poisson indicator -> mesh, with the Shape-as-Points gradient
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -106,6 +112,8 @@ from .meshreg import (MeshRegTopology, laplacian_smooth_loss, mesh_edge_loss, me
 from .meshmc import render_mesh_mc  # noqa: F401
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .occlusion import ambient_occlusion, face_ambient_occlusion  # noqa: F401
+from .poisson import (diff_poisson_surface_recon, mesh_from_indicator, mesh_from_oriented_points, poisson_indicator,  # noqa: F401
+                      remesh_poisson, sample_grid, splat_to_grid)
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401
 from .raytrace import MeshBVH, shadow_visibility  # noqa: F401
 from .shading import RenderableAttrs, get_fg_lut, render_depth, render_rgb, render_rgba, shade, tone_map  # noqa: F401

@@ -1287,6 +1287,56 @@ int gs_meshreg_bwd(int V, int E, int P, int NL, const float* vertices, const int
                    const int32_t* pr, const int32_t* long_verts, float target_length, const float* lap_dir, const float* pair_grad,
                    const float* out_grad, float* grad, void* stream);
 
+/* ------------------------------------------------------------------ differentiable Poisson surface reconstruction -------------- */
+/* TriangleMesh.from_diff_poisson_reconstruction (rfstudio/graphics/_mesh/_triangle_mesh.py:301-319) through Shape-as-Points,
+ * rfstudio/graphics/_mesh/_dpsr/ops.py: point_rasterize, grid_interp, the Fourier-space step of DPSR.forward and the vertex normals
+ * PSR2Mesh returns; a restatement of the semantics.  csrc/gs_poisson.hip, weights in csrc/gs_gridinterp_dev.h.  The FFTs, the
+ * shift / scale step and the means stay with the caller (torch.fft is hipFFT).
+ *
+ * Grid: [C, R0, R1, R2] float, the LAST axis fastest; every side >= 4, R0 R1 R2 < 2^31; node i sits at i / R per axis of the unit
+ * cube and the grid is periodic.  C in [1, 4], N < 2^31.
+ * Row rule (splat, sample and both backward kernels): a row takes part iff its three coordinates are finite and |p| < 1024,
+ *   decided on the floats before any conversion to an integer.  Other rows add nothing to a grid, read 0 from one and get a zero
+ *   gradient.  A finite p outside [0, 1) wraps (the reference raises for p = 1.0).
+ * Weights, per axis and in this order: w = p - floor(p);  s = w R;  lo = floor(s) (R -> 0);  hi = (lo + 1) mod R;  f = s - floor(s)
+ *   (exact);  lower node 1 - f, upper node f;  corner k (bit 2: axis 0, bit 1: axis 1, bit 0: axis 2) has weight (w0 w1) w2.
+ *
+ * gs_grid_splat: grid[c, node] = sum over rows and corners of weight * values[n, c].  Bitwise reproducible: every addend
+ *   t = fp32(weight * value) enters a 64-bit integer accumulator as rint(t 2^e), e = 62 - exponent(N max|v|) with max|v| reduced
+ *   on the device over the rows that take part (no node sum can overflow; an addend is exact to 2^-e), and the node's float is the
+ *   sum times 2^-e, rounded once.  Integer sums do not depend on the order.  A NaN or inf VALUE in a row that takes part makes the
+ *   whole grid NaN.  ws: gs_grid_splat_ws_bytes = 16 + 8 C R0 R1 R2 (0: out of range); the call clears it.
+ * gs_grid_sample_fwd: out[n, c] = sum_k weight_k grid[c, node_k], k = 0..7 in order, fused multiply-adds.
+ * gs_grid_sample_bwd: g_points[n, a] = sum_k (d weight_k / d p_a) sum_c cot[n, c] grid[c, node_k]; d weight_k / d p_a = +-R_a times
+ *   the two other axes' weights.  A gather per point, no atomics.  The gradient of the sample to its grid is gs_grid_splat(points,
+ *   cot); the gradients of the splat are gs_grid_sample_fwd(g_grid, points) to the values and gs_grid_sample_bwd(g_grid, points,
+ *   values) to the points.
+ *
+ * gs_poisson_spectral_fwd: S [3, R0, R1, R2/2+1] complex64 (rfftn of the three splatted normal components) -> Phi [R0, R1, R2/2+1]:
+ *     k_a = i if i <= (R_a - 1) / 2 else i - R_a  on axes 0 and 1 (fftfreq: the Nyquist term of an even side is -R/2),  k_2 = i
+ *     (rfftfreq: +R/2);  omega_d = fp32(k_d) fp32(2 pi);  G = fp32(exp(-2 sigma^2 |k|^2)) evaluated in float64;
+ *     Phi = [sum_d (-i) (G S_d) omega_d] / (-(omega_0^2 + omega_1^2 + omega_2^2) + 1e-6),  d = 0, 1, 2 in order;  Phi(0,0,0) = 0.
+ *   IEEE division, no contraction.  _bwd is the adjoint torch's complex autograd expects of a linear map:
+ *     g_S_d = conj(c_d) g_Phi,  c_d = -i G omega_d / denominator  (0 at DC).
+ *
+ * gs_grid_pack_volume: volume[n] = (phi[n], 1): the interleaved volume of gs_tsdf_extract_* called with (R2, R1, R0), whose fastest
+ *   axis is then phi's last.  Its vertices come back as (axis 2, axis 1, axis 0); swapping them is a reflection, so the caller also
+ *   flips the winding.
+ * gs_grid_vertex_normals: vertices [V,3] in NODE units on grid edges (two integer coordinates).  The gradient at a node is the
+ *   periodic central difference 0.5 R_a (phi[i + e_a] - phi[i - e_a]); it is interpolated linearly between the edge's two nodes and
+ *   normalised (scaled by its largest component first).  A gradient of exactly 0, or a non-finite vertex, gives (0, 0, 0).  Every
+ *   index is wrapped: no vertex addresses outside phi. */
+size_t gs_grid_splat_ws_bytes(int C, int R0, int R1, int R2);
+int gs_grid_splat(int64_t N, int C, int R0, int R1, int R2, const float* points, const float* values, float* grid, void* ws,
+                  size_t ws_bytes, void* stream);
+int gs_grid_sample_fwd(int64_t N, int C, int R0, int R1, int R2, const float* grid, const float* points, float* out, void* stream);
+int gs_grid_sample_bwd(int64_t N, int C, int R0, int R1, int R2, const float* grid, const float* points, const float* cot,
+                       float* g_points, void* stream);
+int gs_poisson_spectral_fwd(int R0, int R1, int R2, double sigma, const float* S, float* Phi, void* stream);
+int gs_poisson_spectral_bwd(int R0, int R1, int R2, double sigma, const float* g_Phi, float* g_S, void* stream);
+int gs_grid_pack_volume(int R0, int R1, int R2, const float* phi, float* volume, void* stream);
+int gs_grid_vertex_normals(int R0, int R1, int R2, const float* phi, int64_t V, const float* vertices, float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
