@@ -18,6 +18,7 @@
 // Ray/Triangle Intersection" (JCGT 2013), restated from the paper; the box test is padded so that it never culls a box holding a
 // triangle which that test would accept (see ray_box).  The brute-force form runs the SAME device routine over every triangle.
 #include "gs_bvh_dev.h"
+#include "gs_ws.h"
 
 #define BVH_BLOCK 256
 #define BVH_MAX_FACES ((int64_t)1 << 30)       // node indices are int32: 2 F - 1 <= 2^31 - 1
@@ -26,28 +27,27 @@
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------
 struct BvhWs {
-    size_t off_bounds, off_count, off_parent, off_right, off_last, off_rsplit, off_keys, off_vals, off_skeys, off_svals, off_sort;
+    unsigned* bounds; int *count, *parent, *right, *last, *rsplit, *vals, *svals; unsigned long long *keys, *skeys; char* sort;
     size_t sort_bytes, total;
 };
-static size_t bvh_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static BvhWs bvh_ws_layout(int64_t F)
+static BvhWs bvh_ws_layout(int64_t F, void* base)
 {
+    GsWs w(base, 256);
     BvhWs L;
-    size_t p = 0;
     const size_t f = (size_t)F;
-    L.off_bounds = p; p += 256;                                    // 6 ordered-integer bounds
-    L.off_count = p;  p += bvh_align(f * 4);                       // arrival counter per internal node
-    L.off_parent = p; p += bvh_align((2 * f - 1) * 4);
-    L.off_right = p;  p += bvh_align(f * 4);                       // right child per internal node
-    L.off_last = p;   p += bvh_align(f * 4);                       // last leaf of the range per internal node
-    L.off_rsplit = p; p += bvh_align(f * 4);                       // right child of the internal node whose split is at leaf g
-    L.off_keys = p;   p += bvh_align(f * 8);
-    L.off_vals = p;   p += bvh_align(f * 4);
-    L.off_skeys = p;  p += bvh_align(f * 8);
-    L.off_svals = p;  p += bvh_align(f * 4);
-    L.off_sort = p;
+    L.bounds = w.take<unsigned>(64);               // 6 ordered-integer bounds
+    L.count = w.take<int>(f);                      // arrival counter per internal node
+    L.parent = w.take<int>(2 * f - 1);
+    L.right = w.take<int>(f);                      // right child per internal node
+    L.last = w.take<int>(f);                       // last leaf of the range per internal node
+    L.rsplit = w.take<int>(f);                     // right child of the internal node whose split is at leaf g
+    L.keys = w.take<unsigned long long>(f);
+    L.vals = w.take<int>(f);
+    L.skeys = w.take<unsigned long long>(f);
+    L.svals = w.take<int>(f);
     L.sort_bytes = gs_sort_ws_bytes(F, BVH_SORT_TILES, BVH_SORT_TILES);
-    L.total = p + bvh_align(L.sort_bytes);
+    L.sort = w.take<char>(L.sort_bytes);
+    L.total = w.bytes();
     return L;
 }
 
@@ -300,7 +300,7 @@ extern "C" size_t gs_bvh_bytes(int64_t F)
 extern "C" size_t gs_bvh_ws_bytes(int64_t F)
 {
     if (F < 1 || F > BVH_MAX_FACES) return 0;
-    return bvh_ws_layout(F).total;
+    return bvh_ws_layout(F, nullptr).total;
 }
 
 extern "C" int gs_bvh_build(int64_t V, int64_t F, const float* vertices, const int32_t* faces, void* bvh, size_t bvh_bytes, void* ws,
@@ -310,39 +310,28 @@ extern "C" int gs_bvh_build(int64_t V, int64_t F, const float* vertices, const i
     GS_CHECK_ARG(F <= BVH_MAX_FACES, "too many faces: at most 2^30");
     GS_CHECK_ARG(V >= 1 && V <= 2147483647ll, "bad vertex count");
     GS_CHECK_ARG(bvh_bytes >= gs_bvh_bytes(F), "node buffer too small");
-    const BvhWs L = bvh_ws_layout(F);
+    const BvhWs L = bvh_ws_layout(F, ws);
     GS_CHECK_ARG(ws_bytes >= L.total, "workspace too small");
     GS_CHECK_ARG(vertices != nullptr && faces != nullptr, "vertices and faces must not be NULL");
     GS_CHECK_ARG(bvh != nullptr && ws != nullptr, "node buffer and workspace must not be NULL");
     GS_CHECK_ARG(((uintptr_t)bvh & 15) == 0 && ((uintptr_t)ws & 15) == 0, "node buffer and workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)ws;
-    unsigned* bounds = (unsigned*)(w + L.off_bounds);
-    int* count = (int*)(w + L.off_count);
-    int* parent = (int*)(w + L.off_parent);
-    int* right = (int*)(w + L.off_right);
-    int* last = (int*)(w + L.off_last);
-    int* rsplit = (int*)(w + L.off_rsplit);
-    unsigned long long* keys = (unsigned long long*)(w + L.off_keys);
-    int* vals = (int*)(w + L.off_vals);
-    unsigned long long* skeys = (unsigned long long*)(w + L.off_skeys);
-    int* svals = (int*)(w + L.off_svals);
     BvhNode* nodes = (BvhNode*)bvh;
     const int blocks = gs_cdiv(F, BVH_BLOCK);
-    hipLaunchKernelGGL(bvh_init_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)F, bounds, count);
+    hipLaunchKernelGGL(bvh_init_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)F, L.bounds, L.count);
     GS_CHECK_LAUNCH();
     hipLaunchKernelGGL(bvh_bounds_kernel, dim3(blocks < 512 ? blocks : 512), dim3(BVH_BLOCK), 0, s, (long long)V, (long long)F, vertices,
-                       faces, bounds);
+                       faces, L.bounds);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bvh_morton_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)V, (long long)F, vertices, faces, bounds, keys, vals);
+    hipLaunchKernelGGL(bvh_morton_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)V, (long long)F, vertices, faces, L.bounds, L.keys, L.vals);
     GS_CHECK_LAUNCH();
-    const int rc = gs_isect_sort(F, (const int64_t*)keys, vals, (int64_t*)skeys, svals, BVH_SORT_TILES, BVH_SORT_TILES, w + L.off_sort,
+    const int rc = gs_isect_sort(F, (const int64_t*)L.keys, L.vals, (int64_t*)L.skeys, L.svals, BVH_SORT_TILES, BVH_SORT_TILES, L.sort,
                                  L.sort_bytes, stream);
     if (rc != GS_OK) return rc;
-    hipLaunchKernelGGL(bvh_karras_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)F, skeys, nodes, parent, right, last, rsplit);
+    hipLaunchKernelGGL(bvh_karras_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)F, L.skeys, nodes, L.parent, L.right, L.last, L.rsplit);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bvh_fit_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)V, (long long)F, vertices, faces, svals, parent, right,
-                       last, rsplit, count, nodes);
+    hipLaunchKernelGGL(bvh_fit_kernel, dim3(blocks), dim3(BVH_BLOCK), 0, s, (long long)V, (long long)F, vertices, faces, L.svals, L.parent,
+                       L.right, L.last, L.rsplit, L.count, nodes);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }

@@ -6,6 +6,7 @@
 // The refinement is a memory move: 59 parameter floats + 118 moment floats per Gaussian.  Classification and ranks read 7 floats
 // per Gaussian; the gather touches every attribute byte once on each side.  No LDS staging, no atomics, vector stores only.
 #include "gs_common.h"
+#include "gs_ws.h"
 
 #define DN_BLOCK 256
 #define DN_SCAN_THREADS 1024
@@ -14,22 +15,19 @@
 #define DN_SPLIT 2u
 #define DN_DUP 4u
 
-static inline size_t dn_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace: [ block counts / offsets u32[3 * nb] | class flags u8[N] | row map i32[N * max(S, 2)] ]
-struct DnLayout {
-    size_t off_blocks, off_flags, off_rowmap, total;
-    int nb;
-};
-static inline DnLayout dn_layout(int64_t N, int num_splits)
+struct DnLayout { unsigned* blocks; unsigned char* flags; int* rowmap; size_t total; int nb; };
+static inline DnLayout dn_layout(void* base, int64_t N, int num_splits)
 {
+    GsWs w(base, 256);
     DnLayout L;
     L.nb = gs_cdiv(N, DN_BLOCK);
     const int64_t per = num_splits > 2 ? num_splits : 2;           // a split row yields S rows, any other at most 2 (kept + copy)
-    L.off_blocks = 0;
-    L.off_flags = dn_align((size_t)3 * (size_t)L.nb * 4);
-    L.off_rowmap = L.off_flags + dn_align((size_t)N);
-    L.total = L.off_rowmap + dn_align((size_t)N * (size_t)per * 4);
+    L.blocks = w.take<unsigned>((size_t)3 * (size_t)L.nb);
+    L.flags = w.take<unsigned char>((size_t)N);
+    L.rowmap = w.take<int>((size_t)N * (size_t)per);
+    L.total = w.bytes();
     return L;
 }
 
@@ -350,7 +348,7 @@ int gs_densify_stats(int V, const int64_t* gaussian_ids, const float* v_means2d,
 size_t gs_densify_ws_bytes(int64_t N, int num_splits)
 {
     if (N <= 0 || N > GS_DENSIFY_MAX_N || num_splits < 0 || num_splits > GS_DENSIFY_MAX_SPLITS) return 0;
-    return dn_layout(N, num_splits).total;
+    return dn_layout(nullptr, N, num_splits).total;
 }
 
 int gs_densify_plan(int64_t N, const float* scales, const float* opacities, const float* xys_grad_norm, const float* vis_counts,
@@ -361,22 +359,19 @@ int gs_densify_plan(int64_t N, const float* scales, const float* opacities, cons
     GS_CHECK_ARG(mode == GS_DENSIFY_MODE_DENSIFY || mode == GS_DENSIFY_MODE_CULL, "mode must be 0 (densify_and_cull) or 1 (cull)");
     GS_CHECK_ARG(num_splits >= 0 && num_splits <= GS_DENSIFY_MAX_SPLITS, "num_splits must be in [0, 8]");
     GS_CHECK_ARG(mode == GS_DENSIFY_MODE_CULL || num_splits >= 1, "num_splits must be >= 1 for densify_and_cull");
-    const DnLayout L = dn_layout(N, num_splits);
+    const DnLayout L = dn_layout(ws, N, num_splits);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
     }
     GS_CHECK_ARG(scales && opacities && totals, "null pointer");
     GS_CHECK_ARG(mode == GS_DENSIFY_MODE_CULL || (xys_grad_norm && vis_counts), "densify_and_cull needs xys_grad_norm and vis_counts");
-    char* base = (char*)ws;
-    unsigned* blocks = (unsigned*)(base + L.off_blocks);
-    unsigned char* flags = (unsigned char*)(base + L.off_flags);
     DnThresholds t{half_extent, grad_thresh, size_thresh, alpha_thresh, scale_thresh, mode};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(densify_classify_kernel, dim3(L.nb), dim3(DN_BLOCK), 0, s, (long long)N, scales, opacities, xys_grad_norm,
-                       vis_counts, t, flags, blocks, L.nb);
+                       vis_counts, t, L.flags, L.blocks, L.nb);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(DN_SCAN_THREADS), 0, s, blocks, L.nb,
+    hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(DN_SCAN_THREADS), 0, s, L.blocks, L.nb,
                        mode == GS_DENSIFY_MODE_CULL ? 0 : num_splits, (long long*)totals);
     GS_CHECK_LAUNCH();
     return GS_OK;
@@ -391,7 +386,7 @@ int gs_densify_fill(int64_t N, int num_splits, void* ws, size_t ws_bytes, int64_
     GS_CHECK_ARG(n_selected >= 0 && n_split >= 0 && n_dup >= 0 && n_selected + n_split <= N && n_dup <= N, "totals out of range");
     GS_CHECK_ARG(n_tensors >= 0 && n_tensors <= GS_DENSIFY_MAX_TENSORS, "n_tensors must be in [0, 32]");
     GS_CHECK_ARG(n_tensors == 0 || table, "null table");
-    const DnLayout L = dn_layout(N, num_splits);
+    const DnLayout L = dn_layout(ws, N, num_splits);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
@@ -423,16 +418,12 @@ int gs_densify_fill(int64_t N, int num_splits, void* ws, size_t ws_bytes, int64_
         T.wide_load[k] = (((uintptr_t)e.src) & 15) == 0 && (e.floats_per_row % 4) == 0;
     }
     GS_CHECK_ARG(!(need_child && n_children > 0) || (quats && scales && randn), "child means need quats, scales and randn");
-    char* base = (char*)ws;
-    const unsigned* blocks = (const unsigned*)(base + L.off_blocks);
-    const unsigned char* flags = (const unsigned char*)(base + L.off_flags);
-    int* rowmap = (int*)(base + L.off_rowmap);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(densify_map_kernel, dim3(L.nb), dim3(DN_BLOCK), 0, s, (long long)N, num_splits, flags, blocks, L.nb,
-                       (long long)n_selected, (long long)n_split, (long long)N_out, rowmap, (long long*)indices);
+    hipLaunchKernelGGL(densify_map_kernel, dim3(L.nb), dim3(DN_BLOCK), 0, s, (long long)N, num_splits, L.flags, L.blocks, L.nb,
+                       (long long)n_selected, (long long)n_split, (long long)N_out, L.rowmap, (long long*)indices);
     GS_CHECK_LAUNCH();
     if (n_tensors == 0) return GS_OK;
-    DnRows R{(long long)N, (unsigned)n_selected, (unsigned)n_split, (unsigned)n_children, (unsigned)N_out, rowmap, quats, scales, randn};
+    DnRows R{(long long)N, (unsigned)n_selected, (unsigned)n_split, (unsigned)n_children, (unsigned)N_out, L.rowmap, quats, scales, randn};
     const int64_t want = (max_total / 4 + DN_BLOCK) / DN_BLOCK;
     const int gx = (int)(want < 16384 ? want : 16384);                               // grid-stride above 16 Mi floats per tensor
     hipLaunchKernelGGL(densify_gather_kernel, dim3(gx, n_tensors), dim3(DN_BLOCK), 0, s, T, R);

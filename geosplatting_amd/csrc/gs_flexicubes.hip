@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "gs_common.h"
+#include "gs_ws.h"
 
 #pragma clang fp contract(off)
 
@@ -674,22 +675,20 @@ struct FcWs {
     int nb_cube, nb_slot, nb_ent;
     size_t bytes;
 };
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 FcWs fc_ws(const FcGrid& g, void* base)
 {
     FcWs w;
     w.nb_cube = gs_cdiv(g.C, FC_BLOCK); w.nb_slot = gs_cdiv(3 * (int64_t)g.Vg, FC_BLOCK); w.nb_ent = gs_cdiv(3 * (int64_t)g.Vg, 256);
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += al256(n); return (char*)base + o; };
-    w.hdr = (int*)take(sizeof(int) * H_INTS);
-    w.case8 = (uint8_t*)take((size_t)g.C);
-    w.vd_base = (int*)take(sizeof(int) * (size_t)g.C);
-    w.k_base = (int*)take(sizeof(int) * (size_t)g.C);
-    w.quad_id = (int*)take(sizeof(int) * 3 * (size_t)g.Vg);
-    w.blk_cube = (int*)take(sizeof(int) * NCC * (size_t)w.nb_cube);
-    w.blk_slot = (int*)take(sizeof(int) * NCE * (size_t)w.nb_slot);
-    w.partial = (double*)take(sizeof(double) * (size_t)w.nb_ent);
-    w.bytes = off;
+    GsWs t(base, 256);
+    w.hdr = t.take<int>(H_INTS);
+    w.case8 = t.take<uint8_t>((size_t)g.C);
+    w.vd_base = t.take<int>((size_t)g.C);
+    w.k_base = t.take<int>((size_t)g.C);
+    w.quad_id = t.take<int>(3 * (size_t)g.Vg);
+    w.blk_cube = t.take<int>(NCC * (size_t)w.nb_cube);
+    w.blk_slot = t.take<int>(NCE * (size_t)w.nb_slot);
+    w.partial = t.take<double>((size_t)w.nb_ent);
+    w.bytes = t.bytes();
     return w;
 }
 

@@ -335,7 +335,7 @@ front_setup_kernel(unsigned* __restrict__ ws, int ws_words, unsigned long long* 
 #define GS_FRONT_HIST_MAX 8192               // tiles whose counters fit a block's LDS histogram (32 KB); gs_isect_bin_front agrees
 // ticket + error flag (16 bytes), then four u64 rows of one word per chunk of GS_FRONT_CHUNK Gaussians (gs_project_dev.h)
 static int front_chunks(int N) { return N > 0 ? (N + GS_FRONT_CHUNK - 1) / GS_FRONT_CHUNK : 1; }
-extern "C" size_t gs_front_ws_bytes(int N) { return (16 + 4 * (size_t)front_chunks(N) * sizeof(u64) + 15) & ~(size_t)15; }
+extern "C" size_t gs_front_ws_bytes(int N) { return scan_ws(nullptr, (size_t)front_chunks(N)).bytes; }
 
 extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const float* scales, const float* opacities,
                             const float* normals, const float* kd, const float* ks, const float* viewmat, const float* K,
@@ -354,13 +354,14 @@ extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const
     EnvDev e;
     if (vis_records != nullptr) GS_CHECK_ARG(env_to_dev(env, e) == 0, "bad GsEnv");
     else memset(&e, 0, sizeof(e));                            // geometry only: nothing is shaded
-    if (ws_bytes < gs_front_ws_bytes(N)) { gs_set_error("gs_front_fwd: workspace too small"); return GS_ENOSPC; }
+    const ScanWs w = scan_ws(ws, (size_t)front_chunks(N));
+    if (ws_bytes < w.bytes) { gs_set_error("gs_front_fwd: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
     const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
     GS_CHECK_ARG(tile_w < 65536 && tile_h < 65536, "tile grid too large");
     const int n_tiles = tile_w * tile_h;
     const bool hist = tile_counts != nullptr && n_tiles <= GS_FRONT_HIST_MAX;          // more tiles: the binning derives the offsets itself
-    const int ws_words = (int)(gs_front_ws_bytes(N) / 4);
+    const int ws_words = (int)(w.bytes / 4);
     hipLaunchKernelGGL(front_setup_kernel, dim3(gs_cdiv(ws_words > n_tiles ? ws_words : n_tiles, 256) < 64 ? gs_cdiv(ws_words > n_tiles ? ws_words : n_tiles, 256) : 64),
                        dim3(256), 0, s, (unsigned*)ws, ws_words, (unsigned long long*)counts4, tile_counts, tile_counts ? n_tiles : 0);
     GS_CHECK_LAUNCH();
@@ -369,7 +370,7 @@ extern "C" int gs_front_fwd(int N, const float* means, const float* quats, const
     hipLaunchKernelGGL(front_fwd_kernel, dim3(n_chunks), dim3(GS_FRONT_BLOCK), hist ? (size_t)n_tiles * sizeof(unsigned) : 0, s, N, means, quats, scales, opacities, normals, kd, ks,
                        viewmat, K, cam_pos, min_roughness, max_metallic, mode, e, W, H, tile_size, tile_w, tile_h, eps2d, near_plane,
                        far_plane, radius_clip, key_bits == 24 ? key_base : 0u, key_bits == 24 ? (1u << 24) : 0u, (float4*)vis_records,
-                       depth_keys, (uint2*)tile_rects, (unsigned*)ws, (u64*)((char*)ws + 16), n_chunks, (unsigned long long*)counts4,
+                       depth_keys, (uint2*)tile_rects, w.ctrl, w.desc, n_chunks, (unsigned long long*)counts4,
                        (long long*)status4, hist ? tile_counts : (unsigned*)nullptr, packed_index, tight_tiles);
     GS_CHECK_LAUNCH();
     return GS_OK;

@@ -14,6 +14,7 @@
 // Without a workspace: per-point kernel with fp32 atomics (the F = 2 features of a corner committed by two ADJACENT
 // lanes of one instruction = one memory-side request), 2.6x slower at 2 M points.
 #include "gs_common.h"
+#include "gs_ws.h"
 
 #pragma clang fp contract(off)   // cell indices must round exactly like the reference (x * 0.5 + 0.5, then * scaling)
 
@@ -559,13 +560,26 @@ hashgrid_bwd_slabfx_kernel(int N, int L, unsigned log2_T, HgLevels lv, int slabs
     }
 }
 
+// workspace of the fixed-point path: the level-major copy of v_out (gs_hashgrid_bwd_ws_bytes), a point counter per (level, slab),
+// 256 bytes for the per-level maxima of |v_out| (cleared together with the counters), a queue of point indices per (level, slab)
+struct HgFixedWs { float* v_lm; int* q_counts; unsigned* gmax; int* queues; size_t bytes; };
+static HgFixedWs hg_fixed_ws(void* base, int N, int L, int F, int log2_T)
+{
+    const size_t slabs = ((size_t)1 << log2_T) / HG_FX_ROWS, n = (size_t)(N > 0 ? N : 1);
+    GsWs w(base, 256);
+    HgFixedWs r;
+    r.v_lm = w.take<float>(gs_hashgrid_bwd_ws_bytes(N, L, F) / sizeof(float));
+    r.q_counts = w.take<int>(L * slabs);
+    r.gmax = w.take<unsigned>(64);
+    r.queues = w.tail<int>(L * slabs * n);
+    r.bytes = w.bytes();
+    return r;
+}
 extern "C" size_t gs_hashgrid_bwd_fixed_ws_bytes(int N, int L, int F, int log2_T)
 {
     const size_t T = (size_t)1 << log2_T;
     if (T < (size_t)HG_FX_ROWS * 4 || T > (size_t)HG_FX_ROWS * 64) return 0;       // 4..64 slabs per level
-    const size_t slabs = T / HG_FX_ROWS, n = (size_t)(N > 0 ? N : 1);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return al(gs_hashgrid_bwd_ws_bytes(N, L, F)) + al(sizeof(int) * L * slabs) + 256 + sizeof(int) * L * slabs * n;
+    return hg_fixed_ws(nullptr, N, L, F, log2_T).bytes;
 }
 
 // Table gradient in 64-bit fixed point over binned points (deterministic); v_x as gs_hashgrid_bwd.  gmax: DEVICE pointer to
@@ -576,9 +590,9 @@ extern "C" int gs_hashgrid_bwd_fixed(int N, int L, int F, int log2_T, const floa
 {
     const int rc = hg_check(N, L, F, log2_T);
     if (rc != GS_OK) return rc;
-    const size_t need = gs_hashgrid_bwd_fixed_ws_bytes(N, L, F, log2_T);
-    GS_CHECK_ARG(need > 0, "table size outside the fixed-point path (2^15 .. 2^19 rows per level)");
-    GS_CHECK_ARG(ws != nullptr && ws_bytes >= need, "workspace too small");
+    GS_CHECK_ARG(gs_hashgrid_bwd_fixed_ws_bytes(N, L, F, log2_T) > 0, "table size outside the fixed-point path (2^15 .. 2^19 rows per level)");
+    const HgFixedWs w = hg_fixed_ws(ws, N, L, F, log2_T);
+    GS_CHECK_ARG(ws != nullptr && ws_bytes >= w.bytes, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)L * ((size_t)1 << log2_T) * F;
     HgLevels lv;
@@ -587,26 +601,21 @@ extern "C" int gs_hashgrid_bwd_fixed(int N, int L, int F, int log2_T, const floa
         if (!accumulate) GS_CHECK_HIP(gs_zero_async(v_table, sizeof(float) * n, s));
         return GS_OK;
     }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const int slabs = (int)(((size_t)1 << log2_T) / HG_FX_ROWS);
-    float* v_lm = (float*)ws;
-    int* q_counts = (int*)((char*)ws + al(gs_hashgrid_bwd_ws_bytes(N, L, F)));
-    unsigned* gmax = (unsigned*)((char*)q_counts + al(sizeof(int) * L * slabs));
-    int* queues = (int*)((char*)gmax + 256);
-    hipLaunchKernelGGL(hashgrid_transpose_kernel, dim3(gs_cdiv((int64_t)N * L, 256)), dim3(256), 0, s, N, L * F, v_out, v_lm);
-    GS_CHECK_HIP(gs_zero_async(q_counts, al(sizeof(int) * L * slabs) + 256, s));            // counters and maxima
-    hipLaunchKernelGGL(hashgrid_level_max_kernel, dim3(min(64, gs_cdiv(2 * (int64_t)N, 4096)), L), dim3(1024), 0, s, N, v_lm, gmax);
+    hipLaunchKernelGGL(hashgrid_transpose_kernel, dim3(gs_cdiv((int64_t)N * L, 256)), dim3(256), 0, s, N, L * F, v_out, w.v_lm);
+    GS_CHECK_HIP(gs_zero_async(w.q_counts, (size_t)((char*)w.queues - (char*)w.q_counts), s));     // counters and maxima
+    hipLaunchKernelGGL(hashgrid_level_max_kernel, dim3(min(64, gs_cdiv(2 * (int64_t)N, 4096)), L), dim3(1024), 0, s, N, w.v_lm, w.gmax);
     int rows_shift = 0;
     while ((1 << rows_shift) < HG_FX_ROWS) ++rows_shift;
     const size_t bin_lds = sizeof(int) * (size_t)L * slabs * (1 + HG_BIN_BLOCK / 64);
     GS_CHECK_ARG(bin_lds <= 160 * 1024, "too many (level, slab) pairs for the binning pass");
     GS_CHECK_HIP(hipFuncSetAttribute((const void*)hashgrid_bin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
     hipLaunchKernelGGL(hashgrid_bin_kernel, dim3(gs_cdiv(N, HG_BIN_BLOCK)), dim3(HG_BIN_BLOCK), bin_lds, s, N, L, (unsigned)log2_T, lv,
-                       slabs, rows_shift, x, q_counts, queues);
+                       slabs, rows_shift, x, w.q_counts, w.queues);
     const size_t lds = sizeof(unsigned long long) * 2 * (size_t)HG_FX_ROWS;
     GS_CHECK_HIP(hipFuncSetAttribute((const void*)hashgrid_bwd_slabfx_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(hashgrid_bwd_slabfx_kernel, dim3(L * slabs), dim3(1024), lds, s, N, L, (unsigned)log2_T, lv, slabs, x, v_lm, gmax,
-                       table_grad_scale, v_table, accumulate, q_counts, queues);
+    hipLaunchKernelGGL(hashgrid_bwd_slabfx_kernel, dim3(L * slabs), dim3(1024), lds, s, N, L, (unsigned)log2_T, lv, slabs, x, w.v_lm, w.gmax,
+                       table_grad_scale, v_table, accumulate, w.q_counts, w.queues);
     if (v_x) hipLaunchKernelGGL(hashgrid_bwd_x_kernel<2>, dim3(gs_cdiv(N, 256)), dim3(256), 0, s, N, L, (unsigned)log2_T, lv, x, table,
                                 v_out, v_x);
     GS_CHECK_LAUNCH();

@@ -13,6 +13,7 @@
 // order or on rounding; only the weight is fp32, from the unsnapped positions (the convention of mr_values).
 #include "gs_meshraster_dev.h"
 #include "gs_meshclip_dev.h"
+#include "gs_ws.h"
 
 #define AA_EMPTY 0xffffffffffffffffull
 
@@ -29,7 +30,7 @@ static inline AaLayout aa_layout(int64_t F)
     L.off_head = L.slots * 8;
     L.off_slot = L.off_head + L.slots * 4;
     L.off_next = L.off_slot + (size_t)(3 * F) * 4;
-    L.total = ((L.off_next + (size_t)(3 * F) * 4) + 15) & ~(size_t)15;
+    L.total = gs_align_up(L.off_next + (size_t)(3 * F) * 4, 16);
     return L;
 }
 

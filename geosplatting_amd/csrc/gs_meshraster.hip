@@ -15,6 +15,7 @@
 // Every kernel is bounded: no workgroup waits on another.  Coverage is decided in 64-bit integers on 1/256 px coordinates, so a pixel
 // on an edge shared by two triangles is covered exactly once (top-left rule) whatever the launch order.
 #include "gs_common.h"
+#include "gs_ws.h"
 #include "gs_meshraster_dev.h"
 #include "gs_meshclip_dev.h"
 
@@ -390,17 +391,16 @@ static __global__ void __launch_bounds__(MR_BLOCK) mi_bwd_kernel(long long P, in
 // ------------------------------------------------------------------------------------------------ entry points
 // workspace: [ keys u64[H W] | big-triangle count u32, crossing-face count u32 (16 bytes) | big-triangle list u32[F] ]
 // and, with near_clip (gs_meshclip_*), [ ... | crossing-face list u32[F] ]
-struct MrLayout {
-    size_t off_count, off_big, off_cross, total;
-};
-static inline size_t mr_align(size_t x) { return (x + 15) & ~(size_t)15; }
-static inline MrLayout mr_layout(int64_t F, int H, int W, bool clip = false)
+struct MrLayout { unsigned long long* keys; unsigned *n_big, *big, *cross; size_t total; };
+static inline MrLayout mr_layout(const void* base, int64_t F, int H, int W, bool clip = false)
 {
+    GsWs w((void*)base, 16);
     MrLayout L;
-    L.off_count = mr_align((size_t)H * (size_t)W * 8);
-    L.off_big = L.off_count + 16;
-    L.off_cross = L.off_big + mr_align((size_t)(F > 0 ? F : 1) * 4);
-    L.total = L.off_cross + (clip ? mr_align((size_t)(F > 0 ? F : 1) * 4) : 0);
+    L.keys = w.take<unsigned long long>((size_t)H * (size_t)W);
+    L.n_big = w.take<unsigned>(4);
+    L.big = w.take<unsigned>((size_t)(F > 0 ? F : 1));
+    L.cross = clip ? w.take<unsigned>((size_t)(F > 0 ? F : 1)) : nullptr;
+    L.total = w.bytes();
     return L;
 }
 static bool mr_dims_ok(int64_t V, int64_t F, int H, int W)
@@ -415,7 +415,7 @@ extern "C" {
 size_t gs_meshraster_ws_bytes(int64_t F, int H, int W)
 {
     if (!mr_dims_ok(0, F, H, W)) return 0;
-    return mr_layout(F, H, W).total;
+    return mr_layout(nullptr, F, H, W).total;
 }
 
 int gs_meshraster_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
@@ -424,29 +424,25 @@ int gs_meshraster_fwd(int64_t V, int64_t F, const float* vc, const int32_t* face
     GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
     GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
     GS_CHECK_ARG(cull == 0 || cull == 1, "cull must be 0 (none) or 1 (back)");
-    const MrLayout L = mr_layout(F, H, W);
+    const MrLayout L = mr_layout(ws, F, H, W);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
     }
     GS_CHECK_ARG(F == 0 || (vc && faces), "null pointer");
-    char* base = (char*)ws;
-    unsigned long long* keys = (unsigned long long*)base;
-    unsigned* n_big = (unsigned*)(base + L.off_count);
-    unsigned* big = (unsigned*)(base + L.off_big);
     hipStream_t s = (hipStream_t)stream;
     const size_t n_keys = (size_t)H * (size_t)W;
-    hipLaunchKernelGGL(mr_fill_kernel<false>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, keys, n_keys,
-                       n_big);
+    hipLaunchKernelGGL(mr_fill_kernel<false>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, L.keys, n_keys,
+                       L.n_big);
     GS_CHECK_LAUNCH();
     if (F == 0) return GS_OK;
     MrCam cam{fx, fy, cx, cy, near, H, W};
     hipLaunchKernelGGL(mr_small_kernel<false>, dim3(gs_cdiv(F, MR_BLOCK)), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam,
-                       cull, keys, n_big, big, (unsigned*)nullptr, (unsigned long long*)stats);
+                       cull, L.keys, L.n_big, L.big, (unsigned*)nullptr, (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
     const int want = gs_cdiv(F, MR_BLOCK / GS_WAVE);
     hipLaunchKernelGGL(mr_big_kernel, dim3(want < MR_MAX_BIG_BLOCKS ? want : MR_MAX_BIG_BLOCKS), dim3(MR_BLOCK), 0, s, (long long)V,
-                       (long long)F, vc, faces, cam, keys, n_big, big, (unsigned long long*)stats);
+                       (long long)F, vc, faces, cam, L.keys, L.n_big, L.big, (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -456,7 +452,7 @@ int gs_meshraster_resolve(int64_t V, int64_t F, const float* vc, const int32_t* 
 {
     GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
     GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
-    const MrLayout L = mr_layout(F, H, W);
+    const MrLayout L = mr_layout(ws, F, H, W);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
@@ -464,7 +460,7 @@ int gs_meshraster_resolve(int64_t V, int64_t F, const float* vc, const int32_t* 
     GS_CHECK_ARG(rast && (F == 0 || (vc && faces)), "null pointer");
     MrCam cam{fx, fy, cx, cy, near, H, W};
     hipLaunchKernelGGL(mr_resolve_kernel<false>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream,
-                       (long long)V, (long long)F, vc, faces, cam, (const unsigned long long*)ws, (float4*)rast);
+                       (long long)V, (long long)F, vc, faces, cam, L.keys, (float4*)rast);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -490,7 +486,7 @@ int gs_meshraster_bwd(int64_t V, int64_t F, const float* vc, const int32_t* face
 size_t gs_meshclip_ws_bytes(int64_t F, int H, int W)
 {
     if (!mr_dims_ok(0, F, H, W)) return 0;
-    return mr_layout(F, H, W, true).total;
+    return mr_layout(nullptr, F, H, W, true).total;
 }
 
 int gs_meshclip_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces, float fx, float fy, float cx, float cy, int H, int W,
@@ -499,34 +495,29 @@ int gs_meshclip_fwd(int64_t V, int64_t F, const float* vc, const int32_t* faces,
     GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
     GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
     GS_CHECK_ARG(cull == 0 || cull == 1, "cull must be 0 (none) or 1 (back)");
-    const MrLayout L = mr_layout(F, H, W, true);
+    const MrLayout L = mr_layout(ws, F, H, W, true);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
     }
     GS_CHECK_ARG(F == 0 || (vc && faces), "null pointer");
-    char* base = (char*)ws;
-    unsigned long long* keys = (unsigned long long*)base;
-    unsigned* n_big = (unsigned*)(base + L.off_count);
-    unsigned* big = (unsigned*)(base + L.off_big);
-    unsigned* cross = (unsigned*)(base + L.off_cross);
     hipStream_t s = (hipStream_t)stream;
     const size_t n_keys = (size_t)H * (size_t)W;
-    hipLaunchKernelGGL(mr_fill_kernel<true>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, keys, n_keys,
-                       n_big);
+    hipLaunchKernelGGL(mr_fill_kernel<true>, dim3(gs_cdiv((int64_t)((n_keys + 1) / 2), MR_BLOCK)), dim3(MR_BLOCK), 0, s, L.keys, n_keys,
+                       L.n_big);
     GS_CHECK_LAUNCH();
     if (F == 0) return GS_OK;
     MrCam cam{fx, fy, cx, cy, near, H, W};
     hipLaunchKernelGGL(mr_small_kernel<true>, dim3(gs_cdiv(F, MR_BLOCK)), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam,
-                       cull, keys, n_big, big, cross, (unsigned long long*)stats);
+                       cull, L.keys, L.n_big, L.big, L.cross, (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
     const int want = gs_cdiv(F, MR_BLOCK / GS_WAVE);
     const int blocks = want < MR_MAX_BIG_BLOCKS ? want : MR_MAX_BIG_BLOCKS;
-    hipLaunchKernelGGL(mr_big_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, keys, n_big, big,
+    hipLaunchKernelGGL(mr_big_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, L.keys, L.n_big, L.big,
                        (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mr_cross_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, cull, keys,
-                       n_big + 1, cross, (unsigned long long*)stats);
+    hipLaunchKernelGGL(mr_cross_kernel, dim3(blocks), dim3(MR_BLOCK), 0, s, (long long)V, (long long)F, vc, faces, cam, cull, L.keys,
+                       L.n_big + 1, L.cross, (unsigned long long*)stats);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -536,7 +527,7 @@ int gs_meshclip_resolve(int64_t V, int64_t F, const float* vc, const int32_t* fa
 {
     GS_CHECK_ARG(mr_dims_ok(V, F, H, W), "need V < 2^31, F <= 2^24, H, W >= 1 and H W < 2^31");
     GS_CHECK_ARG(mr_cam_ok(fx, fy, near), "fx, fy and near must be > 0");
-    const MrLayout L = mr_layout(F, H, W, true);
+    const MrLayout L = mr_layout(ws, F, H, W, true);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
@@ -544,7 +535,7 @@ int gs_meshclip_resolve(int64_t V, int64_t F, const float* vc, const int32_t* fa
     GS_CHECK_ARG(rast && (F == 0 || (vc && faces)), "null pointer");
     MrCam cam{fx, fy, cx, cy, near, H, W};
     hipLaunchKernelGGL(mr_resolve_kernel<true>, dim3(gs_cdiv((int64_t)H * W, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream,
-                       (long long)V, (long long)F, vc, faces, cam, (const unsigned long long*)ws, (float4*)rast);
+                       (long long)V, (long long)F, vc, faces, cam, L.keys, (float4*)rast);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }

@@ -21,6 +21,7 @@
 // a fixed-size sorted list with one kernel instantiation per k.  The brute-force form runs the SAME distance routine over every point
 // through LDS tiles.
 #include "gs_common.h"
+#include "gs_ws.h"
 
 #define NN_BLOCK 256
 #define NN_MAX_POINTS ((int64_t)1 << 30)
@@ -40,34 +41,35 @@ struct NnHeader {                              // the first 256 bytes of the gri
     double h[3];                               // 1 / (double)inv_h: the cell size the bound uses
     double ext[3];                             // box maximum - box minimum in fp64
 };
-static size_t nn_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t nn_max_cells(int64_t M)
 {
     const int64_t t = M / 4;
     return t < 1 ? 1 : (t > NN_MAX_CELLS ? NN_MAX_CELLS : t);
 }
-struct NnGrid { size_t off_start, off_rec, total; };
-static NnGrid nn_grid_layout(int64_t M)
+struct NnGrid { NnHeader* hdr; int* cell_start; float4* rec; size_t total; };
+static NnGrid nn_grid_layout(int64_t M, const void* base)
 {
+    GsWs w((void*)base, 256);
     NnGrid G;
-    G.off_start = 256;                                                   // cell_start[ncells + 1], sized for the most cells
-    G.off_rec = G.off_start + nn_align((size_t)(nn_max_cells(M) + 1) * 4);
-    G.total = G.off_rec + nn_align((size_t)M * 16);
+    G.hdr = (NnHeader*)w.take<char>(256);
+    G.cell_start = w.take<int>((size_t)(nn_max_cells(M) + 1));           // cell_start[ncells + 1], sized for the most cells
+    G.rec = w.take<float4>((size_t)M);
+    G.total = w.bytes();
     return G;
 }
-struct NnWs { size_t off_keys, off_vals, off_skeys, off_svals, off_sort, sort_bytes, total; };
-static NnWs nn_ws_layout(int64_t M)
+struct NnWs { unsigned long long *keys, *skeys; int *vals, *svals; char* sort; size_t sort_bytes, total; };
+static NnWs nn_ws_layout(int64_t M, void* base)
 {
+    GsWs w(base, 256);
     NnWs L;
-    size_t p = 0;
     const size_t m = (size_t)M;
-    L.off_keys = p;  p += nn_align(m * 8);
-    L.off_vals = p;  p += nn_align(m * 4);
-    L.off_skeys = p; p += nn_align(m * 8);
-    L.off_svals = p; p += nn_align(m * 4);
-    L.off_sort = p;
+    L.keys = w.take<unsigned long long>(m);
+    L.vals = w.take<int>(m);
+    L.skeys = w.take<unsigned long long>(m);
+    L.svals = w.take<int>(m);
     L.sort_bytes = gs_sort_ws_bytes(M, NN_SORT_TILES, NN_SORT_TILES);
-    L.total = p + nn_align(L.sort_bytes);
+    L.sort = w.take<char>(L.sort_bytes);
+    L.total = w.bytes();
     return L;
 }
 
@@ -441,52 +443,43 @@ static __global__ void __launch_bounds__(NN_BLOCK) chamfer_bwd_scatter_kernel(lo
 extern "C" size_t gs_nn_grid_bytes(int64_t M)
 {
     if (M < 1 || M > NN_MAX_POINTS) return 0;
-    return nn_grid_layout(M).total;
+    return nn_grid_layout(M, nullptr).total;
 }
 
 extern "C" size_t gs_nn_ws_bytes(int64_t M)
 {
     if (M < 1 || M > NN_MAX_POINTS) return 0;
-    return nn_ws_layout(M).total;
+    return nn_ws_layout(M, nullptr).total;
 }
 
 extern "C" int gs_nn_build(int64_t M, const float* points, void* grid, size_t grid_bytes, void* ws, size_t ws_bytes, void* stream)
 {
     GS_CHECK_ARG(M >= 1, "empty set: M must be at least 1");
     GS_CHECK_ARG(M <= NN_MAX_POINTS, "too many points: at most 2^30");
-    const NnGrid G = nn_grid_layout(M);
-    const NnWs L = nn_ws_layout(M);
+    const NnGrid G = nn_grid_layout(M, grid);
+    const NnWs L = nn_ws_layout(M, ws);
     GS_CHECK_ARG(grid_bytes >= G.total, "grid buffer too small");
     GS_CHECK_ARG(ws_bytes >= L.total, "workspace too small");
     GS_CHECK_ARG(points != nullptr, "points must not be NULL");
     GS_CHECK_ARG(grid != nullptr && ws != nullptr, "grid buffer and workspace must not be NULL");
     GS_CHECK_ARG(((uintptr_t)grid & 15) == 0 && ((uintptr_t)ws & 15) == 0, "grid buffer and workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    char* g = (char*)grid;
-    char* w = (char*)ws;
-    NnHeader* hdr = (NnHeader*)g;
-    int* cell_start = (int*)(g + G.off_start);
-    float4* rec = (float4*)(g + G.off_rec);
-    unsigned long long* keys = (unsigned long long*)(w + L.off_keys);
-    int* vals = (int*)(w + L.off_vals);
-    unsigned long long* skeys = (unsigned long long*)(w + L.off_skeys);
-    int* svals = (int*)(w + L.off_svals);
     const int max_cells = (int)nn_max_cells(M);
     const int blocks = gs_cdiv(M, NN_BLOCK);
-    hipLaunchKernelGGL(nn_init_kernel, dim3(1), dim3(64), 0, s, hdr);
+    hipLaunchKernelGGL(nn_init_kernel, dim3(1), dim3(64), 0, s, G.hdr);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nn_bounds_kernel, dim3(blocks < 512 ? blocks : 512), dim3(NN_BLOCK), 0, s, (long long)M, points, hdr);
+    hipLaunchKernelGGL(nn_bounds_kernel, dim3(blocks < 512 ? blocks : 512), dim3(NN_BLOCK), 0, s, (long long)M, points, G.hdr);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nn_layout_kernel, dim3(1), dim3(64), 0, s, max_cells, hdr);
+    hipLaunchKernelGGL(nn_layout_kernel, dim3(1), dim3(64), 0, s, max_cells, G.hdr);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nn_keys_kernel, dim3(blocks), dim3(NN_BLOCK), 0, s, (long long)M, points, hdr, keys, vals);
+    hipLaunchKernelGGL(nn_keys_kernel, dim3(blocks), dim3(NN_BLOCK), 0, s, (long long)M, points, G.hdr, L.keys, L.vals);
     GS_CHECK_LAUNCH();
-    const int rc = gs_isect_sort(M, (const int64_t*)keys, vals, (int64_t*)skeys, svals, NN_SORT_TILES, NN_SORT_TILES, w + L.off_sort,
+    const int rc = gs_isect_sort(M, (const int64_t*)L.keys, L.vals, (int64_t*)L.skeys, L.svals, NN_SORT_TILES, NN_SORT_TILES, L.sort,
                                  L.sort_bytes, stream);
     if (rc != GS_OK) return rc;
-    hipLaunchKernelGGL(nn_gather_kernel, dim3(blocks), dim3(NN_BLOCK), 0, s, (long long)M, points, svals, rec);
+    hipLaunchKernelGGL(nn_gather_kernel, dim3(blocks), dim3(NN_BLOCK), 0, s, (long long)M, points, L.svals, G.rec);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nn_cellstart_kernel, dim3(gs_cdiv(max_cells + 1, NN_BLOCK)), dim3(NN_BLOCK), 0, s, (long long)M, skeys, hdr, cell_start);
+    hipLaunchKernelGGL(nn_cellstart_kernel, dim3(gs_cdiv(max_cells + 1, NN_BLOCK)), dim3(NN_BLOCK), 0, s, (long long)M, L.skeys, G.hdr, G.cell_start);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -497,10 +490,9 @@ static void nn_launch_query(int64_t M, const float* points, const void* grid, in
 {
     const dim3 blocks(gs_cdiv(N, NN_BLOCK)), block(NN_BLOCK);
     if (grid != nullptr) {
-        const NnGrid G = nn_grid_layout(M);
-        const char* g = (const char*)grid;
-        hipLaunchKernelGGL(nn_grid_query_kernel<K>, blocks, block, 0, s, (long long)M, (const NnHeader*)g, (const int*)(g + G.off_start),
-                           (const float4*)(g + G.off_rec), (long long)N, queries, dist, index);
+        const NnGrid G = nn_grid_layout(M, grid);
+        hipLaunchKernelGGL(nn_grid_query_kernel<K>, blocks, block, 0, s, (long long)M, (const NnHeader*)G.hdr, (const int*)G.cell_start,
+                           (const float4*)G.rec, (long long)N, queries, dist, index);
     } else {
         hipLaunchKernelGGL(nn_brute_query_kernel<K>, blocks, block, 0, s, (long long)M, points, (long long)N, queries, dist, index);
     }

@@ -8,6 +8,7 @@
 //   gs_grid_vertex_normals      normalise(grad phi) at vertices that lie on grid edges
 // The FFTs are the caller's (hipFFT through torch.fft).  The weights come from csrc/gs_gridinterp_dev.h in all four directions.
 #include "gs_gridinterp_dev.h"
+#include "gs_ws.h"
 
 #define PS_BLOCK 256
 
@@ -16,7 +17,6 @@ static bool ps_res_ok(int R0, int R1, int R2)
     return R0 >= 4 && R1 >= 4 && R2 >= 4 && (int64_t)R0 * R1 * R2 < ((int64_t)1 << 31);
 }
 
-static inline size_t ps_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // ------------------------------------------------------------------------------------------------ splat
 // workspace: [ max |v| bits u32, padded to 16 bytes | C * R0 R1 R2 fixed-point accumulators i64 ]
@@ -322,7 +322,7 @@ extern "C" {
 size_t gs_grid_splat_ws_bytes(int C, int R0, int R1, int R2)
 {
     if (!ps_res_ok(R0, R1, R2) || C < 1 || C > 4) return 0;
-    return PS_HEAD + ps_align((size_t)C * (size_t)R0 * R1 * R2 * 8);
+    return PS_HEAD + gs_align_up((size_t)C * (size_t)R0 * R1 * R2 * 8, 16);
 }
 
 int gs_grid_splat(int64_t N, int C, int R0, int R1, int R2, const float* points, const float* values, float* grid, void* ws,

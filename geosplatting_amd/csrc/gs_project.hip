@@ -76,12 +76,12 @@ project_fwd_ex_kernel(int N, const float* __restrict__ means, const float* __res
 #include "gs_project_fwd_body.inc"
 }
 
-extern "C" size_t gs_project_ws_bytes(int N)
+static ScanWs project_ws(void* base, int N)
 {
-    size_t n_chunks = (size_t)((N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK);
-    if (n_chunks == 0) n_chunks = 1;
-    return 16 + 4 * n_chunks * sizeof(u64);
+    const size_t n_chunks = (size_t)((N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK);
+    return scan_ws(base, n_chunks ? n_chunks : 1);
 }
+extern "C" size_t gs_project_ws_bytes(int N) { return project_ws(nullptr, N).bytes; }
 
 extern "C" int gs_project_fwd(int N, const float* means, const float* quats, const float* scales,
                               const float* opacities, const float* colors, int D, const float* viewmat,
@@ -110,19 +110,18 @@ extern "C" int gs_project_fwd_vis(int N, const float* means, const float* quats,
     GS_CHECK_ARG(N >= 0 && W > 0 && H > 0 && tile_size > 0, "bad sizes");
     GS_CHECK_ARG(counts != nullptr && ws != nullptr, "counts/ws must not be NULL");
     GS_CHECK_ARG((colors == nullptr) == (colors_packed == nullptr), "colors and colors_packed go together");
-    if (ws_bytes < gs_project_ws_bytes(N)) { gs_set_error("gs_project_fwd: workspace too small"); return GS_ENOSPC; }
+    const ScanWs w = project_ws(ws, N);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_project_fwd: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
-    GS_CHECK_HIP(gs_zero_async(ws, gs_project_ws_bytes(N), s));
+    GS_CHECK_HIP(gs_zero_async(ws, w.bytes, s));
     GS_CHECK_HIP(gs_zero_async(counts, 2 * sizeof(int64_t), s));
     if (N == 0) return GS_OK;
     const int n_chunks = (N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK;
     const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
-    unsigned* ctrl = (unsigned*)ws;
-    u64* desc = (u64*)((char*)ws + 16);
     hipLaunchKernelGGL(project_fwd_kernel, dim3(n_chunks), dim3(GS_PROJ_BLOCK), 0, s, N, means, quats, scales,
                        opacities, colors, D, viewmat, K, W, H, tile_size, tile_w, tile_h, eps2d, near_plane,
                        far_plane, radius_clip, gaussian_ids, radii, means2d, depths, conics, compensations,
-                       opacities_packed, colors_packed, tiles_per_gauss, cum_tiles, packed_index, ctrl, desc,
+                       opacities_packed, colors_packed, tiles_per_gauss, cum_tiles, packed_index, w.ctrl, w.desc,
                        n_chunks, counts, (float4*)vis_records);
     GS_CHECK_LAUNCH();
     return GS_OK;
@@ -366,20 +365,19 @@ extern "C" int gs_project_fwd_vis_ex(int N, const float* means, const float* qua
     GS_CHECK_ARG(counts != nullptr && ws != nullptr, "counts/ws must not be NULL");
     if (sh) GS_CHECK_ARG(colors_packed != nullptr, "SH colours need colors_packed [N,3]");
     else    GS_CHECK_ARG((colors == nullptr) == (colors_packed == nullptr), "colors and colors_packed go together");
-    if (ws_bytes < gs_project_ws_bytes(N)) { gs_set_error("gs_project_fwd_vis_ex: workspace too small"); return GS_ENOSPC; }
+    const ScanWs w = project_ws(ws, N);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_project_fwd_vis_ex: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
-    GS_CHECK_HIP(gs_zero_async(ws, gs_project_ws_bytes(N), s));
+    GS_CHECK_HIP(gs_zero_async(ws, w.bytes, s));
     GS_CHECK_HIP(gs_zero_async(counts, 2 * sizeof(int64_t), s));
     if (N == 0) return GS_OK;
     const int n_chunks = (N + GS_PROJ_BLOCK - 1) / GS_PROJ_BLOCK;
     const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
-    unsigned* ctrl = (unsigned*)ws;
-    u64* desc = (u64*)((char*)ws + 16);
     auto kern = sh ? (classic ? project_fwd_ex_kernel<true, true> : project_fwd_ex_kernel<true, false>) : project_fwd_ex_kernel<false, true>;
     hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(GS_PROJ_BLOCK), 0, s, N, means, quats, scales, opacities, colors, D, sh_coeffs,
                        sh_K, sh_degree, viewmat, K, W, H, tile_size, tile_w, tile_h, eps2d, near_plane, far_plane, radius_clip,
                        gaussian_ids, radii, means2d, depths, conics, compensations, opacities_packed, colors_packed, tiles_per_gauss,
-                       cum_tiles, packed_index, ctrl, desc, n_chunks, counts, (float4*)vis_records);
+                       cum_tiles, packed_index, w.ctrl, w.desc, n_chunks, counts, (float4*)vis_records);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }

@@ -4,6 +4,7 @@
 // of ONE Gaussian.  Semantics: gsplat 1.4 fully_fused_projection(packed) as reached from rfstudio/model/gsplat.py:334-355.
 #pragma once
 #include "gs_common.h"
+#include "gs_ws.h"
 
 // ---------------------------------------------------------------------------------------------------
 struct GsCam {
@@ -159,6 +160,18 @@ __device__ __forceinline__ void tile_range_exact(float mx, float my, int radius,
 #define GS_SPIN_LIMIT (1 << 22)
 
 typedef unsigned long long u64;
+
+// the scan's state in the caller's workspace: ticket + error flag (16 bytes), then the four descriptor rows of one word per chunk
+struct ScanWs { unsigned* ctrl; u64* desc; size_t bytes; };
+static inline ScanWs scan_ws(void* base, size_t n_chunks)
+{
+    GsWs w(base, 16);
+    ScanWs r;
+    r.ctrl = w.take<unsigned>(4);
+    r.desc = w.take<u64>(4 * n_chunks);
+    r.bytes = w.bytes();
+    return r;
+}
 
 __device__ __forceinline__ void desc_store(u64* p, u64 v)
 {

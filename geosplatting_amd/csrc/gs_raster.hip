@@ -20,6 +20,7 @@
 // Both kernels are FP32-VALU / transcendental bound (one v_exp_f32 per evaluated pair), not HBM bound.
 #include "gs_common.h"
 #include "gs_tone.h"
+#include "gs_ws.h"
 #include <stdlib.h>
 
 #pragma clang fp contract(off)   // sigma / compositing are spelled with explicit fmaf (bit-exact vs oracle)
@@ -1647,39 +1648,36 @@ static size_t gs_raster_lds(size_t natural)
     if ((size_t)(gs_raster_blocks_per_cu() + 1) * (natural + 512) > (size_t)160 * 1024) return natural;
     return pad;
 }
-// workspace layout: [rec0 | rec1 | rec2 | tile_order], every segment 256-byte aligned
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-extern "C" size_t gs_raster_ws_bytes(int64_t n_isects, int V, int W, int H, int tile_size)
-{
-    if (tile_size <= 0) return 0;
-    const size_t tiles = (size_t)((W + tile_size - 1) / tile_size) * (size_t)((H + tile_size - 1) / tile_size);
-    const size_t n = n_isects > 0 ? (size_t)n_isects : 1;
-    const size_t v = V > 0 ? (size_t)V : 1;
-    return 3 * align256(n * sizeof(float4)) + align256(tiles * sizeof(int32_t)) + align256(64 * sizeof(int32_t)) +
-           align256(64 * tiles * sizeof(int32_t)) + align256(4 * v * sizeof(float4));
-}
-
+// workspace layout, every segment 256-byte aligned: written once, for the size (base == nullptr) and for the pointers
 struct RasterWs {
     float4 *rec0, *rec1, *rec2;
     int32_t* order;
     BwdOrder bo;
     float4* vis;                    // scratch of the forward only: 64-byte per-visible records
+    int tiles; size_t bytes;
 };
-static RasterWs carve(void* ws, int64_t n_isects, int V, int tiles)
+static RasterWs raster_ws(void* base, int64_t n_isects, int V, int W, int H, int tile_size)
 {
-    const size_t n = n_isects > 0 ? (size_t)n_isects : 1;
-    const size_t v = V > 0 ? (size_t)V : 1;
-    char* p = (char*)ws;
+    const size_t n = n_isects > 0 ? (size_t)n_isects : 1, v = V > 0 ? (size_t)V : 1;
+    const size_t tiles = (size_t)((W + tile_size - 1) / tile_size) * (size_t)((H + tile_size - 1) / tile_size);
+    GsWs w(base, 256);
     RasterWs r;
-    r.rec0 = (float4*)p; p += align256(n * sizeof(float4));
-    r.rec1 = (float4*)p; p += align256(n * sizeof(float4));
-    r.rec2 = (float4*)p; p += align256(n * sizeof(float4));
-    r.order = (int32_t*)p; p += align256((size_t)tiles * sizeof(int32_t));
-    r.bo.bcount = (int32_t*)p; p += align256(64 * sizeof(int32_t));
-    r.bo.blist = (int32_t*)p; p += align256(64 * (size_t)tiles * sizeof(int32_t));
-    r.vis = (float4*)p;
+    r.rec0 = w.take<float4>(n);
+    r.rec1 = w.take<float4>(n);
+    r.rec2 = w.take<float4>(n);
+    r.order = w.take<int32_t>(tiles);
+    r.bo.bcount = w.take<int32_t>(64);
+    r.bo.blist = w.take<int32_t>(64 * tiles);
+    r.vis = w.take<float4>(4 * v);
+    r.tiles = (int)tiles;
+    r.bytes = w.bytes();
     return r;
+}
+
+extern "C" size_t gs_raster_ws_bytes(int64_t n_isects, int V, int W, int H, int tile_size)
+{
+    if (tile_size <= 0) return 0;
+    return raster_ws(nullptr, n_isects, V, W, H, tile_size).bytes;
 }
 
 // What a compositor launch takes besides its plain arguments, all zero by default:
@@ -1724,7 +1722,7 @@ static int launch_fwd(int W, int H, int D, const RasterWs& ws, const float* colo
 }
 
 static int raster_check(const char* who, int W, int H, int tile_size, int D, int V, int64_t n_isects, const void* ws,
-                        size_t ws_bytes)
+                        size_t ws_bytes, RasterWs& r)
 {
     GS_CHECK_ARG(W > 0 && H > 0, "bad image size");
     GS_CHECK_ARG(tile_size == GS_TILE, "only tile_size=16 is built (rfstudio/model/gsplat.py:30)");
@@ -1732,7 +1730,8 @@ static int raster_check(const char* who, int W, int H, int tile_size, int D, int
     GS_CHECK_ARG(n_isects >= 0 && n_isects < (1ll << 31), "n_isects must fit int32");
     GS_CHECK_ARG(ws != nullptr, "workspace must not be NULL");
     GS_CHECK_ARG(V >= 0, "bad V");
-    if (ws_bytes < gs_raster_ws_bytes(n_isects, V, W, H, tile_size)) { gs_set_error("%s: workspace too small", who); return GS_ENOSPC; }
+    r = raster_ws((void*)ws, n_isects, V, W, H, tile_size);
+    if (ws_bytes < r.bytes) { gs_set_error("%s: workspace too small", who); return GS_ENOSPC; }
     return GS_OK;
 }
 
@@ -1743,11 +1742,10 @@ static int raster_prepare_impl(int W, int H, int tile_size, int D, int V, const 
                                const int32_t* offsets, const int32_t* flatten_ids, void* ws, size_t ws_bytes, void* stream,
                                const RasterOpts& o)
 {
-    const int rc = raster_check("gs_raster_prepare", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
+    RasterWs r;
+    const int rc = raster_check("gs_raster_prepare", W, H, tile_size, D, V, n_isects, ws, ws_bytes, r);
     if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
-    const RasterWs r = carve(ws, n_isects, V, tiles);
     if (n_isects > 0 && V > 0) {
         const float4* vis = (const float4*)vis_records;
         if (!vis) {                                          // per-visible records not supplied by the projection: build them here
@@ -1760,7 +1758,7 @@ static int raster_prepare_impl(int W, int H, int tile_size, int D, int V, const 
                            vis, r.rec0, r.rec1, r.rec2);
         GS_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, tiles, isect_count(n_isects, o), offsets, r.order, r.bo);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, r.tiles, isect_count(n_isects, o), offsets, r.order, r.bo);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -1770,11 +1768,10 @@ static int raster_composite_impl(int W, int H, int tile_size, int D, int V, cons
                                  int64_t n_isects, const int32_t* offsets, float* render, float* alphas, int32_t* last_ids,
                                  const void* ws, size_t ws_bytes, void* stream, const RasterOpts& o)
 {
-    const int rc = raster_check("gs_raster_composite", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
+    RasterWs r;
+    const int rc = raster_check("gs_raster_composite", W, H, tile_size, D, V, n_isects, ws, ws_bytes, r);
     if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
-    const RasterWs r = carve((void*)ws, n_isects, V, tiles);
 #define GS_FWD(CD) return launch_fwd<CD>(W, H, D, r, colors, background, n_isects, offsets, render, alphas, last_ids, s, o)
     if (D <= 3) GS_FWD(3);
     if (D <= 4) GS_FWD(4);
@@ -1826,14 +1823,13 @@ static int raster_bwd_impl(int W, int H, int tile_size, int D, int V, const floa
                            const float* v_render, const float* v_alphas, float* v_packed, const void* ws,
                            size_t ws_bytes, void* stream, bool zero, const RasterOpts& o)
 {
-    const int rc = raster_check("gs_raster_bwd", W, H, tile_size, D, V, n_isects, ws, ws_bytes);
+    RasterWs r;
+    const int rc = raster_check("gs_raster_bwd", W, H, tile_size, D, V, n_isects, ws, ws_bytes, r);
     if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int rec_stride = gs_raster_grad_stride(D);
     if (V > 0 && zero) GS_CHECK_HIP(gs_zero_async(v_packed, sizeof(float) * (size_t)rec_stride * (size_t)V, s));
     if (n_isects == 0 || V == 0) return GS_OK;
-    const int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
-    const RasterWs r = carve((void*)ws, n_isects, V, tiles);
 #define GS_BWD(CD) return launch_bwd<CD>(W, H, D, r, colors, background, n_isects, offsets, alphas, last_ids, v_render, v_alphas, v_packed, rec_stride, s, o)
     if (D <= 3) GS_BWD(3);
     if (D <= 4) GS_BWD(4);
@@ -1844,22 +1840,23 @@ static int raster_bwd_impl(int W, int H, int tile_size, int D, int V, const floa
 }
 
 // ---- cull log (forward -> backward), see struct CullLog -----------------------------------------------------------------------
-static CullLog carve_log(const void* log_ws, int64_t n_isects)
+struct CullLogWs { CullLog log; size_t bytes; };
+static CullLogWs cull_log_ws(const void* base, int64_t n_isects, int W, int H, int tile_size)
 {
     const size_t n = n_isects > 0 ? (size_t)n_isects : 1;
-    char* p = (char*)log_ws;
-    CullLog l;
-    l.mask = (unsigned long long*)p; p += align256(4 * n * sizeof(unsigned long long));
-    l.idx = (int32_t*)p; p += align256(4 * n * sizeof(int32_t));
-    l.count = (int32_t*)p;
+    const size_t tiles = (size_t)((W + tile_size - 1) / tile_size) * (size_t)((H + tile_size - 1) / tile_size);
+    GsWs w((void*)base, 256);
+    CullLogWs l;
+    l.log.mask = w.take<unsigned long long>(4 * n);
+    l.log.idx = w.take<int32_t>(4 * n);
+    l.log.count = w.take<int32_t>(4 * tiles);
+    l.bytes = w.bytes();
     return l;
 }
 extern "C" size_t gs_raster_log_ws_bytes(int64_t n_isects, int W, int H, int tile_size)
 {
     if (tile_size <= 0) return 0;
-    const size_t n = n_isects > 0 ? (size_t)n_isects : 1;
-    const size_t tiles = (size_t)((W + tile_size - 1) / tile_size) * (size_t)((H + tile_size - 1) / tile_size);
-    return align256(4 * n * sizeof(unsigned long long)) + align256(4 * n * sizeof(int32_t)) + align256(4 * tiles * sizeof(int32_t));
+    return cull_log_ws(nullptr, n_isects, W, H, tile_size).bytes;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2007,12 +2004,13 @@ extern "C" int gs_raster_composite_tone_log(int W, int H, int tile_size, int V, 
                                             size_t ws_bytes, void* log_ws, size_t log_bytes, void* stream)
 {
     GS_CHECK_ARG(log_ws != nullptr && tile_size == GS_TILE, "log_ws must not be NULL");
-    if (log_bytes < gs_raster_log_ws_bytes(n_isects, W, H, tile_size)) { gs_set_error("gs_raster_composite_tone_log: log workspace too small"); return GS_ENOSPC; }
+    const CullLogWs l = cull_log_ws(log_ws, n_isects, W, H, tile_size);
+    if (log_bytes < l.bytes) { gs_set_error("gs_raster_composite_tone_log: log workspace too small"); return GS_ENOSPC; }
     GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && image != nullptr, "bad tone mode / exposure / image");
     RasterOpts o;
     o.counts = counts_dev;
     o.tone_fwd = ToneFwd{ tone_mode, exposure, (float4*)image };
-    o.log = carve_log(log_ws, n_isects);
+    o.log = l.log;
     return raster_composite_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, render, alphas, last_ids, ws, ws_bytes,
                                  stream, o);
 }
@@ -2024,13 +2022,14 @@ extern "C" int gs_raster_bwd_tone_log_acc(int W, int H, int tile_size, int V, co
                                           size_t log_bytes, void* stream)
 {
     GS_CHECK_ARG(log_ws != nullptr && tile_size == GS_TILE, "log_ws must not be NULL");
-    if (log_bytes < gs_raster_log_ws_bytes(n_isects, W, H, tile_size)) { gs_set_error("gs_raster_bwd_tone_log_acc: log workspace too small"); return GS_ENOSPC; }
+    const CullLogWs l = cull_log_ws(log_ws, n_isects, W, H, tile_size);
+    if (log_bytes < l.bytes) { gs_set_error("gs_raster_bwd_tone_log_acc: log workspace too small"); return GS_ENOSPC; }
     GS_CHECK_ARG(tone_mode >= 0 && tone_mode <= 2 && exposure != nullptr && v_image != nullptr && render != nullptr && v_exposure != nullptr,
                  "bad tone mode / exposure / v_image / render / v_exposure");
     RasterOpts o;
     o.counts = counts_dev;
     o.tone_bwd = ToneBwd{ tone_mode, exposure, render, (const float4*)v_image, v_exposure };
-    o.log = carve_log(log_ws, n_isects);
+    o.log = l.log;
     return raster_bwd_impl(W, H, tile_size, 3, V, colors, nullptr, n_isects, offsets, alphas, last_ids, nullptr, nullptr, v_packed, ws,
                            ws_bytes, stream, false, o);
 }

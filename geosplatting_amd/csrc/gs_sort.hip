@@ -26,6 +26,7 @@
 // counter in LDS -- no sorting network, no atomics.
 #include "gs_common.h"
 #include "gs_segsort_dev.h"
+#include "gs_ws.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -257,15 +258,29 @@ static int radix_pass(GsCount nc, In in, Digit digit, Out out, int nbits, unsign
     return GS_OK;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t table_bytes(int64_t n) { return align256(((size_t)256 * (size_t)((n + RS_TILE - 1) / RS_TILE + 1) + 512) * sizeof(unsigned)); }
+// Workspaces (gs_ws.h): one function per layout gives the size (base == nullptr) and the pointers.  Every layout here ends in 256
+// bytes that are no segment: nothing in this file addresses them, they stay because callers allocate and cache by these sizes.
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }       // the tile-first path of gs_isect_bin_front still rounds by hand
+static size_t table_words(int64_t n) { return (size_t)256 * (size_t)((n + RS_TILE - 1) / RS_TILE + 1) + 512; }   // [digit][block] + the row totals
 
 // ---- gs_isect_sort: the upstream call shape ---------------------------------------------------------------------
+struct SortWs { unsigned* table; u64* keys; int32_t* vals; size_t bytes; };
+static SortWs sort_ws(void* base, int64_t n_isects)
+{
+    GsWs w(base, 256);
+    SortWs r;
+    r.table = w.take<unsigned>(table_words(n_isects));
+    r.keys = w.take<u64>((size_t)n_isects);
+    r.vals = w.take<int32_t>((size_t)n_isects);
+    w.pad(256);
+    r.bytes = w.bytes();
+    return r;
+}
 extern "C" size_t gs_sort_ws_bytes(int64_t n_isects, int tile_w, int tile_h)
 {
     if (n_isects <= 0) return 0;
     (void)tile_w; (void)tile_h;
-    return table_bytes(n_isects) + align256((size_t)n_isects * 8) + align256((size_t)n_isects * 4) + 256;
+    return sort_ws(nullptr, n_isects).bytes;
 }
 
 extern "C" int gs_isect_sort(int64_t n_isects, const int64_t* isect_ids, const int32_t* flatten_ids,
@@ -275,12 +290,9 @@ extern "C" int gs_isect_sort(int64_t n_isects, const int64_t* isect_ids, const i
     GS_CHECK_ARG(n_isects >= 0 && tile_w > 0 && tile_h > 0, "bad sizes");
     if (n_isects == 0) return GS_OK;
     GS_CHECK_ARG(ws != nullptr, "workspace must not be NULL");
-    if (ws_bytes < gs_sort_ws_bytes(n_isects, tile_w, tile_h)) { gs_set_error("gs_isect_sort: workspace too small"); return GS_ENOSPC; }
+    const SortWs w = sort_ws(ws, n_isects);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_isect_sort: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
-    char* p = (char*)ws;
-    unsigned* table = (unsigned*)p; p += table_bytes(n_isects);
-    u64* tk = (u64*)p; p += align256((size_t)n_isects * 8);
-    int32_t* tv = (int32_t*)p;
     const int end_bit = 32 + tile_bits(tile_w, tile_h);
     const int npass = (end_bit + 7) / 8;
     // ping-pong so that the LAST pass lands in the caller's output: pass parity decides where the first one goes
@@ -289,9 +301,9 @@ extern "C" int gs_isect_sort(int64_t n_isects, const int64_t* isect_ids, const i
         const int shift = pass * 8;
         const int nbits = (end_bit - shift) < 8 ? (end_bit - shift) : 8;
         const bool to_out = ((npass - 1 - pass) % 2) == 0;
-        u64* dk = to_out ? (u64*)isect_ids_sorted : tk;
-        int32_t* dv = to_out ? flatten_ids_sorted : tv;
-        const int rc = radix_pass<PairItem>(GsCount{ n_isects, nullptr }, PairIn{ src_k, src_v }, PairDigit{ shift, (1u << nbits) - 1u }, PairOut{ dk, dv }, nbits, table, s);
+        u64* dk = to_out ? (u64*)isect_ids_sorted : w.keys;
+        int32_t* dv = to_out ? flatten_ids_sorted : w.vals;
+        const int rc = radix_pass<PairItem>(GsCount{ n_isects, nullptr }, PairIn{ src_k, src_v }, PairDigit{ shift, (1u << nbits) - 1u }, PairOut{ dk, dv }, nbits, w.table, s);
         if (rc != GS_OK) return rc;
         src_k = dk; src_v = dv;
     }
@@ -341,14 +353,33 @@ __device__ __forceinline__ unsigned rect_count(uint2 q)
     return (w > 0 && h > 0) ? (unsigned)(w * h) : 0u;
 }
 
-static size_t bf_state_bytes(int V) { return align256(16 + 2 * (size_t)((V + EM_TILE - 1) / EM_TILE + 1) * sizeof(u64)); }
+// scratch of the radix machinery (gs_isect_bin and the radix path of gs_isect_bin_front): the pass table, the (key, index) items of
+// the depth order, the emission's look-back state, the (tile, index) items of the tile split; `rect` only where the rectangles are
+// computed here, `tile_ids` only where the tile offsets are derived from the sorted ids
+struct RadixWs { unsigned* table; uint2 *da, *db, *rect; unsigned* state; uint2 *ia, *ib; int32_t* tile_ids; int n_state_words; size_t bytes; };
+static RadixWs radix_ws(void* base, size_t v, size_t n, bool rect, bool tile_ids)
+{
+    GsWs w(base, 256);
+    RadixWs r;
+    r.table = w.take<unsigned>(table_words((int64_t)(v > n ? v : n)));
+    r.da = w.take<uint2>(v);
+    r.db = w.take<uint2>(v);
+    r.rect = rect ? w.take<uint2>(v) : nullptr;
+    // ticket + error flag (16 bytes), then two u64 rows of one word per emission block + 1
+    r.n_state_words = (int)(gs_align_up(16 + 2 * (size_t)(((int)v + EM_TILE - 1) / EM_TILE + 1) * sizeof(u64), 256) / 4);
+    r.state = w.take<unsigned>((size_t)r.n_state_words);
+    r.ia = w.take<uint2>(n);
+    r.ib = w.take<uint2>(n);
+    r.tile_ids = tile_ids ? w.take<int32_t>(n) : nullptr;
+    w.pad(256);
+    r.bytes = w.bytes();
+    return r;
+}
 
 extern "C" size_t gs_isect_bin_ws_bytes(int V, int64_t n_isects, int tile_w, int tile_h)
 {
     (void)tile_w; (void)tile_h;
-    const size_t v = V > 0 ? (size_t)V : 1, n = n_isects > 0 ? (size_t)n_isects : 1;
-    const size_t tb = table_bytes((int64_t)(v > n ? v : n));
-    return tb + 3 * align256(v * 8) + bf_state_bytes((int)v) + 2 * align256(n * 8) + 256;
+    return radix_ws(nullptr, V > 0 ? (size_t)V : 1, n_isects > 0 ? (size_t)n_isects : 1, true, false).bytes;
 }
 
 // status word of the capacity protocol: {code, required n_isects}; written only on overflow (the caller zeroes it once)
@@ -361,46 +392,6 @@ __global__ void capacity_check_kernel(const long long* __restrict__ counts, long
         if (I > status[1]) status[1] = I;
         if (V > status[2]) status[2] = V;
     }
-}
-
-static int isect_bin_impl(int V, const float* means2d, const int32_t* radii, const float* depths, int64_t n_isects,
-                          const long long* counts_dev, int tile_size, int tile_w, int tile_h, int64_t* isect_ids_sorted,
-                          int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, void* stream, int32_t* tile_ids_sorted);
-
-extern "C" int gs_isect_bin(int V, const float* means2d, const int32_t* radii, const float* depths,
-                            const int32_t* tiles_per_gauss, int64_t n_isects, int tile_size, int tile_w, int tile_h,
-                            int64_t* isect_ids_sorted, int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, void* stream)
-{
-    (void)tiles_per_gauss;                                  // the counts are re-derived from the rectangles (same arithmetic as gs_project_fwd)
-    return isect_bin_impl(V, means2d, radii, depths, n_isects, nullptr, tile_size, tile_w, tile_h, isect_ids_sorted, flatten_ids_sorted,
-                          ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int gs_isect_bin_cap(int V_cap, const float* means2d, const int32_t* radii, const float* depths, const int64_t* counts_dev,
-                                int64_t n_isects_cap, int tile_size, int tile_w, int tile_h, int64_t* isect_ids_sorted,
-                                int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, int64_t* status_dev, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr && status_dev != nullptr, "counts_dev / status_dev must not be NULL");
-    hipLaunchKernelGGL(capacity_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const long long*)counts_dev, (long long)V_cap,
-                       (long long)n_isects_cap, (long long*)status_dev);
-    GS_CHECK_LAUNCH();
-    return isect_bin_impl(V_cap, means2d, radii, depths, n_isects_cap, (const long long*)counts_dev, tile_size, tile_w, tile_h,
-                          isect_ids_sorted, flatten_ids_sorted, ws, ws_bytes, stream, nullptr);
-}
-
-// The same without the 64-bit `isect_ids`: a caller that only composites (the step engine: `meta` is never returned) needs the sorted
-// flatten ids and the tile offsets; the last pass then writes 8 bytes per intersection instead of 12 and does not gather the depths
-// (gs_isect_offsets_tiles_cap takes the int32 tile ids).
-extern "C" int gs_isect_bin_tiles_cap(int V_cap, const float* means2d, const int32_t* radii, const float* depths, const int64_t* counts_dev,
-                                      int64_t n_isects_cap, int tile_size, int tile_w, int tile_h, int32_t* tile_ids_sorted,
-                                      int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, int64_t* status_dev, void* stream)
-{
-    GS_CHECK_ARG(counts_dev != nullptr && status_dev != nullptr && tile_ids_sorted != nullptr, "counts_dev / status_dev / tile_ids_sorted must not be NULL");
-    hipLaunchKernelGGL(capacity_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const long long*)counts_dev, (long long)V_cap,
-                       (long long)n_isects_cap, (long long*)status_dev);
-    GS_CHECK_LAUNCH();
-    return isect_bin_impl(V_cap, means2d, radii, depths, n_isects_cap, (const long long*)counts_dev, tile_size, tile_w, tile_h,
-                          nullptr, flatten_ids_sorted, ws, ws_bytes, stream, tile_ids_sorted);
 }
 
 // ---- gs_isect_bin_front: binning of the engine's fused front ---------------------------------------------------------------------
@@ -799,15 +790,64 @@ bin_offsets_tiles_kernel(GsCount nc, const int32_t* __restrict__ tiles, int n_ti
 }
 
 
+// ---- the three steps of the radix machinery, as gs_isect_bin and the radix path of gs_isect_bin_front run them ---------------------
+// 1. depth order of the Gaussians: npass stable 8-bit passes over (key, index) items, da -> db -> da ...; the first reads `first`
+template <typename In>
+static int depth_order(GsCount vc, In first, int npass, const RadixWs& w, hipStream_t s, const uint2** order)
+{
+    uint2* src = w.da; uint2* dst = w.db;
+    int rc = radix_pass<uint2>(vc, first, XDigit{ 0, 255u }, U2Out{ src }, 8, w.table, s);
+    for (int pass = 1; pass < npass && rc == GS_OK; ++pass) {
+        rc = radix_pass<uint2>(vc, U2In{ src }, XDigit{ 8 * pass, 255u }, U2Out{ dst }, 8, w.table, s);
+        uint2* t = src; src = dst; dst = t;
+    }
+    *order = src;
+    return rc;
+}
+
+// 2. emission in depth order: the look-back state is cleared (the same launch checks the view against its capacity where `cap` names
+//    the counts), then the positions come from a chained scan inside the launch
+struct CapCheck { const long long* counts; long long v_cap, i_cap; long long* status; };
+static int emit_in_depth_order(const RadixWs& w, GsCount vc, const uint2* order, const uint2* rect, int tile_w, int64_t n_isects,
+                               const CapCheck& cap, hipStream_t s)
+{
+    const int eblocks = ((int)vc.n + EM_TILE - 1) / EM_TILE;
+    hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(w.n_state_words, 256) < 64 ? gs_cdiv(w.n_state_words, 256) : 64), dim3(256), 0, s,
+                       w.state, w.n_state_words, cap.counts, cap.v_cap, cap.i_cap, cap.status);
+    GS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(emit_chained_kernel, dim3(eblocks), dim3(EM_THREADS), 0, s, vc, order, rect, w.state, (u64*)(w.state + 4),
+                       eblocks + 1, tile_w, w.ia, (unsigned)n_isects, cap.status);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}
+
+// 3. stable split by tile id: npass digits of `width` bits over the emitted (tile, index) items, ia -> ib -> ia ...; the last pass
+//    writes through `final`
+template <typename Final>
+static int split_by_tile(GsCount ic, int n_tiles, const RadixWs& w, Final final, hipStream_t s)
+{
+    int tb = 0;
+    while ((1 << tb) < n_tiles) ++tb;
+    if (tb < 1) tb = 1;
+    const int npass = (tb + 7) / 8, width = (tb + npass - 1) / npass;
+    uint2* src = w.ia; uint2* dst = w.ib;
+    for (int pass = 0; pass < npass; ++pass) {
+        const int shift = pass * width;
+        const int nbits = (tb - shift) < width ? (tb - shift) : width;
+        const XDigit digit{ shift, (1u << nbits) - 1u };
+        const int rc = pass == npass - 1 ? radix_pass<uint2>(ic, U2In{ src }, digit, final, nbits, w.table, s)
+                                         : radix_pass<uint2>(ic, U2In{ src }, digit, U2Out{ dst }, nbits, w.table, s);
+        if (rc != GS_OK) return rc;
+        uint2* t = src; src = dst; dst = t;
+    }
+    return GS_OK;
+}
+
 // scratch of the two paths.  Tile first: the per-tile cursors + the class counters, the class lists, the items.
 static size_t tf_state_words(int n_tiles) { return (size_t)n_tiles + SEG_CLASSES; }
 static size_t tf_ws_bytes(int64_t n_isects, int n_tiles)
 {
     return align256(tf_state_words(n_tiles) * 4) + align256((size_t)SEG_CLASSES * n_tiles * 4) + align256((size_t)n_isects * 8) + 256;
-}
-static size_t bf_radix_ws_bytes(size_t v, size_t n)
-{
-    return table_bytes((int64_t)(v > n ? v : n)) + 2 * align256(v * 8) + 2 * align256(n * 8) + bf_state_bytes((int)v) + align256(n * 4) + 256;
 }
 
 // What gs_isect_bin_front needs for these sizes when it is given tile_counts (it always needs that much; a caller that passes no
@@ -817,7 +857,7 @@ extern "C" size_t gs_isect_bin_front_ws_bytes(int V, int64_t n_isects, int tile_
     const size_t v = V > 0 ? (size_t)V : 1, n = n_isects > 0 ? (size_t)n_isects : 1;
     const int64_t n_tiles = (int64_t)tile_w * tile_h;
     if (n_tiles > 0 && n_tiles <= BF_HIST_MAX) return tf_ws_bytes((int64_t)n, (int)n_tiles);
-    return bf_radix_ws_bytes(v, n);
+    return radix_ws(nullptr, v, n, false, true).bytes;
 }
 
 static int bin_front_tile_first(int V, const uint32_t* depth_keys, const uint32_t* tile_rects, const uint32_t* tile_counts,
@@ -881,58 +921,18 @@ extern "C" int gs_isect_bin_front(int V_cap, const uint32_t* depth_keys, const u
                                     isect_offsets, ws, status_dev, s);
     }
     // radix path: the offsets come from the sorted tile ids
-    if (ws_bytes < bf_radix_ws_bytes((size_t)V, (size_t)n_isects)) { gs_set_error("gs_isect_bin_front: workspace too small for the radix path (no tile_counts)"); return GS_ENOSPC; }
+    const RadixWs w = radix_ws(ws, (size_t)V, (size_t)n_isects, false, true);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_isect_bin_front: workspace too small for the radix path (no tile_counts)"); return GS_ENOSPC; }
     const GsCount vc{ (long long)V, (const long long*)counts_dev }, ic{ (long long)n_isects, counts_dev ? (const long long*)counts_dev + 1 : nullptr };
-    char* p = (char*)ws;
-    unsigned* table = (unsigned*)p; p += table_bytes((int64_t)V > n_isects ? (int64_t)V : n_isects);
-    uint2* da = (uint2*)p; p += align256((size_t)V * 8);
-    uint2* db = (uint2*)p; p += align256((size_t)V * 8);
-    uint2* ia = (uint2*)p; p += align256((size_t)n_isects * 8);
-    uint2* ib = (uint2*)p; p += align256((size_t)n_isects * 8);
-    unsigned* state = (unsigned*)p; p += bf_state_bytes(V);
-    int32_t* tile_ids = (int32_t*)p;
-    const int eblocks = (V + EM_TILE - 1) / EM_TILE;
-    const int n_state_words = (int)(bf_state_bytes(V) / 4);
-    // 0. clear the emission's look-back state; capacity check
-    hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(n_state_words, 256) < 64 ? gs_cdiv(n_state_words, 256) : 64),
-                       dim3(256), 0, s, state, n_state_words, (const long long*)counts_dev,
-                       (long long)V_cap, (long long)n_isects_cap, (long long*)status_dev);
-    GS_CHECK_LAUNCH();
-    // 1. depth order of the Gaussians: key_bits / 8 stable 8-bit passes over (key, index); the first reads the key array
-    int rc = radix_pass<uint2>(vc, KeyIn{ depth_keys }, XDigit{ 0, 255u }, U2Out{ da }, 8, table, s);
+    const uint2* order;
+    int rc = depth_order(vc, KeyIn{ depth_keys }, key_bits / 8, w, s, &order);
     if (rc != GS_OK) return rc;
-    rc = radix_pass<uint2>(vc, U2In{ da }, XDigit{ 8, 255u }, U2Out{ db }, 8, table, s);
+    rc = emit_in_depth_order(w, vc, order, (const uint2*)tile_rects, tile_w, n_isects,
+                             CapCheck{ (const long long*)counts_dev, (long long)V_cap, (long long)n_isects_cap, (long long*)status_dev }, s);
     if (rc != GS_OK) return rc;
-    rc = radix_pass<uint2>(vc, U2In{ db }, XDigit{ 16, 255u }, U2Out{ da }, 8, table, s);
+    rc = split_by_tile(ic, n_tiles, w, FinalTiles{ w.tile_ids, flatten_ids_sorted }, s);
     if (rc != GS_OK) return rc;
-    const uint2* order = da;
-    if (key_bits == 32) {
-        rc = radix_pass<uint2>(vc, U2In{ da }, XDigit{ 24, 255u }, U2Out{ db }, 8, table, s);
-        if (rc != GS_OK) return rc;
-        order = db;
-    }
-    // 2. emission in depth order (chained scan inside the launch)
-    unsigned* ctrl = state; u64* desc = (u64*)((char*)state + 16);
-    hipLaunchKernelGGL(emit_chained_kernel, dim3(eblocks), dim3(EM_THREADS), 0, s, vc, order, (const uint2*)tile_rects, ctrl, desc,
-                       eblocks + 1, tile_w, ia, (unsigned)n_isects, (long long*)status_dev);
-    GS_CHECK_LAUNCH();
-    // 3. stable split by tile id: npass digits of `width` bits, the last one writes the sorted tile ids and flatten ids
-    int tb = 0;
-    while ((1 << tb) < n_tiles) ++tb;
-    if (tb < 1) tb = 1;
-    const int npass = (tb + 7) / 8, width = (tb + npass - 1) / npass;
-    uint2* src = ia; uint2* dst = ib;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int shift = pass * width;
-        const int nbits = (tb - shift) < width ? (tb - shift) : width;
-        if (pass == npass - 1)
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, FinalTiles{ tile_ids, flatten_ids_sorted }, nbits, table, s);
-        else
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, U2Out{ dst }, nbits, table, s);
-        if (rc != GS_OK) return rc;
-        uint2* t = src; src = dst; dst = t;
-    }
-    hipLaunchKernelGGL(bin_offsets_tiles_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, ic, tile_ids, n_tiles, isect_offsets);
+    hipLaunchKernelGGL(bin_offsets_tiles_kernel, dim3(gs_cdiv(n_isects, 256)), dim3(256), 0, s, ic, w.tile_ids, n_tiles, isect_offsets);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -948,59 +948,54 @@ static int isect_bin_impl(int V, const float* means2d, const int32_t* radii, con
     GS_CHECK_ARG((int64_t)tile_w * tile_h < (1ll << 24), "more than 2^24 tiles");
     if (V == 0 || n_isects == 0) return GS_OK;
     GS_CHECK_ARG(ws != nullptr, "workspace must not be NULL");
-    if (ws_bytes < gs_isect_bin_ws_bytes(V, n_isects, tile_w, tile_h)) { gs_set_error("gs_isect_bin: workspace too small"); return GS_ENOSPC; }
+    const RadixWs w = radix_ws(ws, (size_t)V, (size_t)n_isects, true, false);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_isect_bin: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
-    char* p = (char*)ws;
-    unsigned* table = (unsigned*)p; p += table_bytes((int64_t)V > n_isects ? (int64_t)V : n_isects);
-    uint2* da = (uint2*)p; p += align256((size_t)V * 8);
-    uint2* db = (uint2*)p; p += align256((size_t)V * 8);
-    uint2* rect = (uint2*)p; p += align256((size_t)V * 8);
-    const int eblocks = (V + EM_TILE - 1) / EM_TILE;
-    unsigned* state = (unsigned*)p; p += bf_state_bytes(V);     // look-back state of the emission
-    uint2* ia = (uint2*)p; p += align256((size_t)n_isects * 8);
-    uint2* ib = (uint2*)p; p += align256((size_t)n_isects * 8);
-    int tb = 0;
-    while ((1 << tb) < tile_w * tile_h) ++tb;
-    if (tb < 1) tb = 1;
-    const int npass = (tb + 7) / 8, width = (tb + npass - 1) / npass;
-    int rc = GS_OK;
-    // 1. depth order of the Gaussians: four stable 8-bit passes over (depth bits, index); the first reads the depth array
-    rc = radix_pass<uint2>(vc, DepthIn{ depths }, XDigit{ 0, 255u }, U2Out{ da }, 8, table, s);
+    const uint2* order;
+    int rc = depth_order(vc, DepthIn{ depths }, 4, w, s, &order);
     if (rc != GS_OK) return rc;
-    rc = radix_pass<uint2>(vc, U2In{ da }, XDigit{ 8, 255u }, U2Out{ db }, 8, table, s);
-    if (rc != GS_OK) return rc;
-    rc = radix_pass<uint2>(vc, U2In{ db }, XDigit{ 16, 255u }, U2Out{ da }, 8, table, s);
-    if (rc != GS_OK) return rc;
-    rc = radix_pass<uint2>(vc, U2In{ da }, XDigit{ 24, 255u }, U2Out{ db }, 8, table, s);
-    if (rc != GS_OK) return rc;
-    // 2. emission in depth order: positions from a chained scan inside the launch (emit_chained_kernel, as gs_isect_bin_front)
     GS_CHECK_ARG(tile_w < 65536 && tile_h < 65536, "tile grid too large");
-    hipLaunchKernelGGL(tile_rect_kernel, dim3(gs_cdiv(V, 256)), dim3(256), 0, s, vc, means2d, radii, tile_size, tile_w, tile_h, rect);
+    hipLaunchKernelGGL(tile_rect_kernel, dim3(gs_cdiv(V, 256)), dim3(256), 0, s, vc, means2d, radii, tile_size, tile_w, tile_h, w.rect);
     GS_CHECK_LAUNCH();
-    {
-        const int n_state_words = (int)(bf_state_bytes(V) / 4);
-        hipLaunchKernelGGL(bin_setup_kernel, dim3(gs_cdiv(n_state_words, 256) < 64 ? gs_cdiv(n_state_words, 256) : 64), dim3(256), 0, s, state,
-                           n_state_words, (const long long*)nullptr, 0ll, 0ll, (long long*)nullptr);
-        GS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(emit_chained_kernel, dim3(eblocks), dim3(EM_THREADS), 0, s, vc, (const uint2*)db, (const uint2*)rect, state,
-                           (u64*)((char*)state + 16), eblocks + 1, tile_w, ia, (unsigned)n_isects, (long long*)nullptr);
-        GS_CHECK_LAUNCH();
-    }
-    // 3. stable split by tile id: npass digits of `width` bits, the last one writes the sorted meta arrays
-    uint2* src = ia; uint2* dst = ib;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int shift = pass * width;
-        const int nbits = (tb - shift) < width ? (tb - shift) : width;
-        if (pass == npass - 1 && tile_ids_sorted != nullptr)
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u },
-                                   FinalTiles{ tile_ids_sorted, flatten_ids_sorted }, nbits, table, s);
-        else if (pass == npass - 1)
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u },
-                                   FinalOut{ (u64*)isect_ids_sorted, flatten_ids_sorted, depths }, nbits, table, s);
-        else
-            rc = radix_pass<uint2>(ic, U2In{ src }, XDigit{ shift, (1u << nbits) - 1u }, U2Out{ dst }, nbits, table, s);
-        if (rc != GS_OK) return rc;
-        uint2* t = src; src = dst; dst = t;
-    }
-    return GS_OK;
+    rc = emit_in_depth_order(w, vc, order, w.rect, tile_w, n_isects, CapCheck{ nullptr, 0ll, 0ll, nullptr }, s);
+    if (rc != GS_OK) return rc;
+    // the last tile pass writes the sorted meta arrays
+    if (tile_ids_sorted != nullptr) return split_by_tile(ic, tile_w * tile_h, w, FinalTiles{ tile_ids_sorted, flatten_ids_sorted }, s);
+    return split_by_tile(ic, tile_w * tile_h, w, FinalOut{ (u64*)isect_ids_sorted, flatten_ids_sorted, depths }, s);
+}
+
+extern "C" int gs_isect_bin(int V, const float* means2d, const int32_t* radii, const float* depths,
+                            const int32_t* tiles_per_gauss, int64_t n_isects, int tile_size, int tile_w, int tile_h,
+                            int64_t* isect_ids_sorted, int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, void* stream)
+{
+    (void)tiles_per_gauss;                                  // the counts are re-derived from the rectangles (same arithmetic as gs_project_fwd)
+    return isect_bin_impl(V, means2d, radii, depths, n_isects, nullptr, tile_size, tile_w, tile_h, isect_ids_sorted, flatten_ids_sorted,
+                          ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int gs_isect_bin_cap(int V_cap, const float* means2d, const int32_t* radii, const float* depths, const int64_t* counts_dev,
+                                int64_t n_isects_cap, int tile_size, int tile_w, int tile_h, int64_t* isect_ids_sorted,
+                                int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, int64_t* status_dev, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr && status_dev != nullptr, "counts_dev / status_dev must not be NULL");
+    hipLaunchKernelGGL(capacity_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const long long*)counts_dev, (long long)V_cap,
+                       (long long)n_isects_cap, (long long*)status_dev);
+    GS_CHECK_LAUNCH();
+    return isect_bin_impl(V_cap, means2d, radii, depths, n_isects_cap, (const long long*)counts_dev, tile_size, tile_w, tile_h,
+                          isect_ids_sorted, flatten_ids_sorted, ws, ws_bytes, stream, nullptr);
+}
+
+// The same without the 64-bit `isect_ids`: a caller that only composites (the step engine: `meta` is never returned) needs the sorted
+// flatten ids and the tile offsets; the last pass then writes 8 bytes per intersection instead of 12 and does not gather the depths
+// (gs_isect_offsets_tiles_cap takes the int32 tile ids).
+extern "C" int gs_isect_bin_tiles_cap(int V_cap, const float* means2d, const int32_t* radii, const float* depths, const int64_t* counts_dev,
+                                      int64_t n_isects_cap, int tile_size, int tile_w, int tile_h, int32_t* tile_ids_sorted,
+                                      int32_t* flatten_ids_sorted, void* ws, size_t ws_bytes, int64_t* status_dev, void* stream)
+{
+    GS_CHECK_ARG(counts_dev != nullptr && status_dev != nullptr && tile_ids_sorted != nullptr, "counts_dev / status_dev / tile_ids_sorted must not be NULL");
+    hipLaunchKernelGGL(capacity_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const long long*)counts_dev, (long long)V_cap,
+                       (long long)n_isects_cap, (long long*)status_dev);
+    GS_CHECK_LAUNCH();
+    return isect_bin_impl(V_cap, means2d, radii, depths, n_isects_cap, (const long long*)counts_dev, tile_size, tile_w, tile_h,
+                          nullptr, flatten_ids_sorted, ws, ws_bytes, stream, tile_ids_sorted);
 }

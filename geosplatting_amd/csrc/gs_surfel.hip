@@ -8,6 +8,7 @@
 // Binning, sort and tile offsets are gs_isect_bin / gs_isect_offsets on (means2d, radii, depths), unchanged.
 // Semantics: gsplat 1.4 rasterization_2dgs(packed=True), one camera, as restated in tests/surfel_ref.py.  All arithmetic fp32.
 #include "gs_common.h"
+#include "gs_ws.h"
 #include "gs_project_dev.h"
 #include "gs_sh_dev.h"
 
@@ -217,11 +218,20 @@ surfel_write_kernel(int N, const float* __restrict__ means, const float* __restr
     if (depth_channel) colors_packed[slot * C + Dc] = p.depth;
 }
 
-extern "C" size_t gs_surfel_project_ws_bytes(int N)
+// projection workspace: the tile count of every Gaussian, then per block of SF_BLOCK the visible and the intersection counts
+struct SurfelProjWs { int32_t* tiles; int32_t* block_v; long long* block_i; size_t bytes; };
+static SurfelProjWs surfel_project_ws(void* base, int N)
 {
     const size_t n = N > 0 ? (size_t)N : 1, nb = (n + SF_BLOCK - 1) / SF_BLOCK;
-    return ((n * 4 + 255) / 256) * 256 + ((nb * 4 + 255) / 256) * 256 + nb * 8;
+    GsWs w(base, 256);
+    SurfelProjWs r;
+    r.tiles = w.take<int32_t>(n);
+    r.block_v = w.take<int32_t>(nb);
+    r.block_i = w.tail<long long>(nb);
+    r.bytes = w.bytes();
+    return r;
 }
+extern "C" size_t gs_surfel_project_ws_bytes(int N) { return surfel_project_ws(nullptr, N).bytes; }
 
 extern "C" int gs_surfel_project_fwd(int N, const float* means, const float* quats, const float* scales, const float* opacities,
                                      const float* colors, int Dc, const float* sh_coeffs, int sh_K, int sh_degree, int depth_channel,
@@ -240,26 +250,24 @@ extern "C" int gs_surfel_project_fwd(int N, const float* means, const float* qua
     GS_CHECK_ARG(sh || Dc == 0 || colors != nullptr, "colors is NULL");
     GS_CHECK_ARG(Dc >= 0 && Dc + depth_channel >= 1 && Dc + depth_channel <= 4, "1..4 composited channels");
     GS_CHECK_ARG(colors_packed != nullptr, "colors_packed is NULL");
-    if (ws_bytes < gs_surfel_project_ws_bytes(N)) { gs_set_error("gs_surfel_project_fwd: workspace too small"); return GS_ENOSPC; }
+    const SurfelProjWs w = surfel_project_ws(ws, N);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_surfel_project_fwd: workspace too small"); return GS_ENOSPC; }
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) { GS_CHECK_HIP(gs_zero_async(counts, 2 * sizeof(int64_t), s)); return GS_OK; }
     const int nb = (N + SF_BLOCK - 1) / SF_BLOCK;
     const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
-    int32_t* tiles = (int32_t*)ws;
-    int32_t* block_v = (int32_t*)((char*)ws + (((size_t)N * 4 + 255) / 256) * 256);
-    long long* block_i = (long long*)((char*)block_v + (((size_t)nb * 4 + 255) / 256) * 256);
     hipLaunchKernelGGL(surfel_count_kernel, dim3(nb), dim3(SF_BLOCK), 0, s, N, means, quats, scales, viewmat, K, W, H, tile_size, tile_w,
-                       tile_h, near_plane, far_plane, radius_clip, tiles, block_v, block_i);
+                       tile_h, near_plane, far_plane, radius_clip, w.tiles, w.block_v, w.block_i);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(surfel_scan_kernel, dim3(1), dim3(SF_BLOCK), 0, s, nb, block_v, block_i, (long long*)counts);
+    hipLaunchKernelGGL(surfel_scan_kernel, dim3(1), dim3(SF_BLOCK), 0, s, nb, w.block_v, w.block_i, (long long*)counts);
     GS_CHECK_LAUNCH();
     if (sh)
         hipLaunchKernelGGL(surfel_write_kernel<true>, dim3(nb), dim3(SF_BLOCK), 0, s, N, means, quats, scales, opacities, colors, Dc, sh_coeffs,
-                           sh_K, sh_degree, depth_channel, viewmat, K, W, H, near_plane, far_plane, radius_clip, tiles, block_v, gaussian_ids,
+                           sh_K, sh_degree, depth_channel, viewmat, K, W, H, near_plane, far_plane, radius_clip, w.tiles, w.block_v, gaussian_ids,
                            radii, means2d, depths, ray_transforms, normals, opacities_packed, colors_packed, tiles_per_gauss);
     else
         hipLaunchKernelGGL(surfel_write_kernel<false>, dim3(nb), dim3(SF_BLOCK), 0, s, N, means, quats, scales, opacities, colors, Dc, sh_coeffs,
-                           sh_K, sh_degree, depth_channel, viewmat, K, W, H, near_plane, far_plane, radius_clip, tiles, block_v, gaussian_ids,
+                           sh_K, sh_degree, depth_channel, viewmat, K, W, H, near_plane, far_plane, radius_clip, w.tiles, w.block_v, gaussian_ids,
                            radii, means2d, depths, ray_transforms, normals, opacities_packed, colors_packed, tiles_per_gauss);
     GS_CHECK_LAUNCH();
     return GS_OK;

@@ -6,6 +6,7 @@
 //   gs_tsdf_extract_fill   : vertices and faces, after the caller has read the totals and allocated
 // Every scan step is its own launch; no workgroup waits on another.  The triangle table is csrc/gs_mc_table.h (generated).
 #include "gs_common.h"
+#include "gs_ws.h"
 #include "gs_mc_table.h"
 
 #define TS_BX 8
@@ -97,25 +98,22 @@ static __global__ void __launch_bounds__(TS_BLOCK) tsdf_integrate_kernel(TsGrid 
 }
 
 // ------------------------------------------------------------------------------------------------ extraction
-static inline size_t ts_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // workspace: [ vertex base u32[N] | cube info u16[N] | edge flags u8[N] | block sums / offsets u32[4 * nb] ]
 //   cube info  : bits 0..7 the case (bit k: corner k inside), bit 8 valid; 0 for a voxel that is no cube's lower corner
 //   edge flags : bit a: the edge from this voxel along axis a carries a vertex
 //   block runs : vertices, triangles, valid cubes, surface cubes per 256 voxels; the scan turns them into exclusive offsets
-struct TsLayout {
-    size_t off_vbase, off_info, off_eflag, off_blocks, total;
-    int nb;
-};
-static inline TsLayout ts_layout(int64_t N)
+struct TsLayout { unsigned* vbase; unsigned short* info; unsigned char* eflag; unsigned* blocks; size_t total; int nb; };
+static inline TsLayout ts_layout(int64_t N, void* base)
 {
+    GsWs w(base, 16);
     TsLayout L;
     L.nb = gs_cdiv(N, TS_BLOCK);
-    L.off_vbase = 0;
-    L.off_info = ts_align((size_t)N * 4);
-    L.off_eflag = L.off_info + ts_align((size_t)N * 2);
-    L.off_blocks = L.off_eflag + ts_align((size_t)N);
-    L.total = L.off_blocks + ts_align((size_t)4 * (size_t)L.nb * 4);
+    L.vbase = w.take<unsigned>((size_t)N);
+    L.info = w.take<unsigned short>((size_t)N);
+    L.eflag = w.take<unsigned char>((size_t)N);
+    L.blocks = w.take<unsigned>((size_t)4 * (size_t)L.nb);
+    L.total = w.bytes();
     return L;
 }
 
@@ -371,33 +369,28 @@ int gs_tsdf_integrate(int R0, int R1, int R2, float origin_x, float origin_y, fl
 size_t gs_tsdf_extract_ws_bytes(int R0, int R1, int R2)
 {
     if (!ts_dims_ok(R0, R1, R2)) return 0;
-    return ts_layout((int64_t)R0 * R1 * R2).total;
+    return ts_layout((int64_t)R0 * R1 * R2, nullptr).total;
 }
 
 int gs_tsdf_extract_count(int R0, int R1, int R2, const float* volume, void* ws, size_t ws_bytes, int64_t* counts, void* stream)
 {
     GS_CHECK_ARG(ts_dims_ok(R0, R1, R2), "resolution must be >= 1 per axis with fewer than 2^31 voxels");
     const int64_t N = (int64_t)R0 * R1 * R2;
-    const TsLayout L = ts_layout(N);
+    const TsLayout L = ts_layout(N, ws);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
     }
     GS_CHECK_ARG(volume && counts, "null pointer");
-    char* base = (char*)ws;
-    unsigned* vbase = (unsigned*)(base + L.off_vbase);
-    unsigned short* info = (unsigned short*)(base + L.off_info);
-    unsigned char* eflag = (unsigned char*)(base + L.off_eflag);
-    unsigned* blocks = (unsigned*)(base + L.off_blocks);
     TsDims D{R0, R1, R2, (long long)N};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(tsdf_cubes_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, (const float2*)volume, info, blocks, L.nb);
+    hipLaunchKernelGGL(tsdf_cubes_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, (const float2*)volume, L.info, L.blocks, L.nb);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tsdf_edges_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, (const float2*)volume, info, eflag, blocks);
+    hipLaunchKernelGGL(tsdf_edges_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, (const float2*)volume, L.info, L.eflag, L.blocks);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TS_SCAN_THREADS), 0, s, blocks, L.nb, (long long*)counts);
+    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TS_SCAN_THREADS), 0, s, L.blocks, L.nb, (long long*)counts);
     GS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tsdf_vbase_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, (long long)N, eflag, blocks, vbase);
+    hipLaunchKernelGGL(tsdf_vbase_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, (long long)N, L.eflag, L.blocks, L.vbase);
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
@@ -410,7 +403,7 @@ int gs_tsdf_extract_fill(int R0, int R1, int R2, float origin_x, float origin_y,
     GS_CHECK_ARG(n_vertices >= 0 && n_triangles >= 0, "totals out of range");
     GS_CHECK_ARG(n_vertices < ((int64_t)1 << 31) && n_triangles < ((int64_t)1 << 31), "more than 2^31 vertices or triangles");
     const int64_t N = (int64_t)R0 * R1 * R2;
-    const TsLayout L = ts_layout(N);
+    const TsLayout L = ts_layout(N, ws);
     if (!ws || ws_bytes < L.total) {
         gs_set_error("%s: workspace too small (%zu < %zu)", __func__, ws ? ws_bytes : (size_t)0, L.total);
         return ws ? GS_ENOSPC : GS_EINVAL;
@@ -418,21 +411,16 @@ int gs_tsdf_extract_fill(int R0, int R1, int R2, float origin_x, float origin_y,
     if (n_vertices == 0 && n_triangles == 0) return GS_OK;
     GS_CHECK_ARG(volume, "null pointer");
     GS_CHECK_ARG((n_vertices == 0 || vertices) && (n_triangles == 0 || faces), "null output");
-    char* base = (char*)ws;
-    const unsigned* vbase = (const unsigned*)(base + L.off_vbase);
-    const unsigned short* info = (const unsigned short*)(base + L.off_info);
-    const unsigned char* eflag = (const unsigned char*)(base + L.off_eflag);
-    const unsigned* blocks = (const unsigned*)(base + L.off_blocks);
     TsDims D{R0, R1, R2, (long long)N};
     TsOrigin O{{origin_x, origin_y, origin_z}, voxel_size};
     hipStream_t s = (hipStream_t)stream;
     if (n_vertices > 0) {
-        hipLaunchKernelGGL(tsdf_vertices_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, O, (const float2*)volume, eflag, vbase,
+        hipLaunchKernelGGL(tsdf_vertices_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, O, (const float2*)volume, L.eflag, L.vbase,
                            (long long)n_vertices, vertices);
         GS_CHECK_LAUNCH();
     }
     if (n_triangles > 0) {
-        hipLaunchKernelGGL(tsdf_faces_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, info, eflag, vbase, blocks, L.nb,
+        hipLaunchKernelGGL(tsdf_faces_kernel, dim3(L.nb), dim3(TS_BLOCK), 0, s, D, L.info, L.eflag, L.vbase, L.blocks, L.nb,
                            (long long)n_triangles, (long long*)faces);
         GS_CHECK_LAUNCH();
     }
