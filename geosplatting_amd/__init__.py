@@ -89,6 +89,11 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                              (rfstudio/graphics/_mesh/_dpsr/ops.py), TriangleMesh.from_diff_poisson_reconstruction
                                              (_triangle_mesh.py:301-319) and the Mesh2Mesh task (tests/graphics/test_dpsr.py):
                                              oriented points -> spectral Poisson indicator -> mesh, with the Shape-as-Points gradient
+  meshsimplify.mesh_components / keep_components / simplify_mesh / edge_collapse_costs, GSplatModel.extract_mesh(target_faces=,
+  min_component_faces=)
+                                          == the "cropping and simplifying" the reference's README asks of outside tools before the
+                                             prior flow: connected components by min-label hooking, and quadric-error decimation run
+                                             as rounds of independent edge collapses (no attributes, no gradient, no hole filling)
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -110,6 +115,7 @@ from .meshrender import (EdgeTopology, antialias, interpolate, mesh_edge_topolog
 from .meshreg import (MeshRegTopology, laplacian_smooth_loss, mesh_edge_loss, mesh_normal_consistency,  # noqa: F401
                       mesh_regularizers)
 from .meshmc import render_mesh_mc  # noqa: F401
+from .meshsimplify import edge_collapse_costs, keep_components, mesh_components, simplify_mesh  # noqa: F401
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .occlusion import ambient_occlusion, face_ambient_occlusion  # noqa: F401
 from .poisson import (diff_poisson_surface_recon, mesh_from_indicator, mesh_from_oriented_points, poisson_indicator,  # noqa: F401

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgeosplat_hip.so")
-SOURCES = ["gs_project.hip", "gs_sort.hip", "gs_raster.hip", "gs_shade.hip", "gs_front.hip", "gs_splitsum.hip", "gs_splitsum_tiles.hip", "gs_mesh.hip", "gs_loss.hip", "gs_smooth.hip", "gs_hashgrid.hip", "gs_flexicubes.hip", "gs_densify.hip", "gs_surfel.hip", "gs_tsdf.hip", "gs_meshraster.hip", "gs_meshaa.hip", "gs_meshshade.hip", "gs_bvh.hip", "gs_envshade.hip", "gs_denoise.hip", "gs_envmap.hip", "gs_nn.hip", "gs_meshreg.hip", "gs_ao.hip", "gs_poisson.hip"]
+SOURCES = ["gs_project.hip", "gs_sort.hip", "gs_raster.hip", "gs_shade.hip", "gs_front.hip", "gs_splitsum.hip", "gs_splitsum_tiles.hip", "gs_mesh.hip", "gs_loss.hip", "gs_smooth.hip", "gs_hashgrid.hip", "gs_flexicubes.hip", "gs_densify.hip", "gs_surfel.hip", "gs_tsdf.hip", "gs_meshraster.hip", "gs_meshaa.hip", "gs_meshshade.hip", "gs_bvh.hip", "gs_envshade.hip", "gs_denoise.hip", "gs_envmap.hip", "gs_nn.hip", "gs_meshreg.hip", "gs_ao.hip", "gs_poisson.hip", "gs_simplify.hip"]
 HEADERS = ["gs_bvh_dev.h", "gs_common.h", "gs_cube.h", "gs_gridinterp_dev.h", "gs_mc_table.h", "gs_meshclip_dev.h", "gs_meshraster_dev.h", "gs_project_dev.h", "gs_project_fwd_body.inc", "gs_project_bwd_body.inc", "gs_segsort_dev.h", "gs_sh_dev.h", "gs_shade_dev.h", "gs_splitsum_math.h", "gs_tex2d_dev.h", "gs_tone.h", "gs_ws.h", os.path.join("..", "..", "include", "geosplat_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-ffp-contract=fast-honor-pragmas", "-Wno-unused-result",

@@ -456,11 +456,14 @@ class GSplatModel:
     @torch.no_grad()
     def extract_mesh(self, resolution: int = 512, fusing_alpha_threshold: float = 0.5, num_views: int = 100, radius: float = 3.0,
                      image_size: int = 800, up: Sequence[float] = (0.0, 0.0, 1.0),
-                     bounds=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), generator: Optional[torch.Generator] = None) -> Tuple[Tensor, Tensor]:
+                     bounds=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), generator: Optional[torch.Generator] = None,
+                     target_faces: Optional[int] = None, min_component_faces: Optional[int] = None) -> Tuple[Tensor, Tensor]:
         """The MeshExport task (tests/model/test_gsplat.py:169-202) -> (vertices [V,3], faces [F,3] int64): depth from `num_views`
         cameras on a sphere of `radius` around the centre of `bounds`, fused into a dense TSDF of `resolution` voxels along the longest
         side (voxel_size = extent / resolution, sdf_trunc = 5 voxel_size: the task's 2 / 512 and 10 / 512), marching cubes.  Renders
-        in eval mode, at most 16 views in flight."""
+        in eval mode, at most 16 views in flight.  min_component_faces drops the connected components with fewer faces (TSDF
+        floaters) and target_faces decimates what is left (meshsimplify.keep_components, then simplify_mesh); with both None the
+        marching-cubes mesh is returned as it is."""
         from .cameras import sphere_cameras
         from .fusion import MAX_VIEWS, TSDFVolume
         lo, hi = bounds
@@ -475,7 +478,14 @@ class GSplatModel:
                 volume.integrate([self.render_depth(c) for c in batch], batch, alpha_trunc=fusing_alpha_threshold)
         finally:
             self.train(was_training)
-        return volume.extract_mesh()
+        vertices, faces = volume.extract_mesh()
+        if min_component_faces is not None or target_faces is not None:
+            from .meshsimplify import keep_components, simplify_mesh
+            if min_component_faces is not None:
+                vertices, faces, _ = keep_components(vertices, faces, min_faces=min_component_faces)
+            if target_faces is not None:
+                vertices, faces, _ = simplify_mesh(vertices, faces, target_faces)
+        return vertices, faces
 
     def render_mesh(self, cameras, vertices: Tensor, faces: Tensor, **kw):
         """A mesh of this model (what extract_mesh returned) seen from `cameras` (a Camera or a sequence): meshrender.render_mesh per

@@ -1337,6 +1337,51 @@ int gs_poisson_spectral_bwd(int R0, int R1, int R2, double sigma, const float* g
 int gs_grid_pack_volume(int R0, int R1, int R2, const float* phi, float* volume, void* stream);
 int gs_grid_vertex_normals(int R0, int R1, int R2, const float* phi, int64_t V, const float* vertices, float* normals, void* stream);
 
+/* ------------------------------------------------------------------ mesh decimation and connected components ------------------- */
+/* Garland-Heckbert quadric error metrics run as rounds of independent edge collapses, and the component filter that goes with it:
+ * the "cropping and simplifying" the reference leaves to outside tools before its prior flow.  csrc/gs_simplify.hip; the caller
+ * (geosplatting_amd/meshsimplify.py) rebuilds the index arrays of a round with sorts, tests/simplify_ref.py restates the rule in
+ * float64 numpy.  V, F and E are at most 2^30; every index must be inside its array: the kernels do not check.
+ *
+ * Index arrays of a round (all int32 unless noted):
+ *   faces [F,3]; edges [E,2] the unique undirected sides (lo, hi), ascending by lo V + hi -- the position is the edge index i;
+ *   edge_faces [E] the number k of faces of an edge; edge_opp [E,2] the vertices opposite to the edge in its first two faces (-1: none);
+ *   nbr_off [V+1], nbr [2E] the neighbours of a vertex, ascending; vf_off [V+1], vf [3F] the faces of a vertex, ascending;
+ *   side_boundary [3F] uint8: side j of face f (corner j to corner j + 1) belongs to an edge with one face;
+ *   boundary [V] uint8: the vertex is on such an edge.
+ *
+ * gs_simplify_quadrics  quadrics [V,10] float64 overwritten: the upper triangle, row-major, of the symmetric 4 x 4
+ *     Q_v = sum over the faces of v of area (n, d)(n, d)^T  +  sum over its one-face sides of boundary_weight |e|^2 (m, d)(m, d)^T,
+ *   n the face's unit normal, d = -n . p0, m the unit vector in the face's plane perpendicular to the side, d = -m . pa.  A zero-area
+ *   face adds nothing.  A gather per vertex in list order: no float atomics.
+ * gs_simplify_edge_costs  per edge (u, v) = (lo, hi), in float64 without contraction:  Q = Q_u + Q_v, A its upper 3 x 3, b = -Q[:3,3];
+ *   p = A^-1 b (adjugate / determinant) is taken when |det A| > 1e-6 (tr A / 3)^3 and |p - mid| <= 2 |e|, otherwise the cheapest of
+ *   u, v, fp32(mid) (the first on a tie);  position = fp32(p);  cost = fp32(max(h^T Q h, 0)), h = (position, 1);
+ *   key = (bits of cost) << 32 | (i 0x9E3779B1 mod 2^32).
+ *   valid: k in {1, 2};  |N(u) n N(v)| = k;  not (k = 2 and both endpoints on the boundary);  no face of u holds both opposite
+ *   vertices;  every face with exactly one of u, v keeps a non-zero normal with n_old . n_new > min_normal_dot |n_old| |n_new| when
+ *   that vertex moves to position;  cost and position finite.
+ * gs_simplify_select  claim [V] uint64 (scratch, overwritten): every valid edge takes the 64-bit atomic minimum of its key into
+ *   claim[w] for every w of {u, v} + N(u) + N(v);  winner [E] uint8 = valid and claim[u] == key and claim[v] == key.  Keys are unique,
+ *   so the winners do not depend on the launch order, and no endpoint of a winner lies in the closed neighbourhood of another's.
+ * gs_simplify_apply  for each of the n selected winners (edge indices, int64):  remap[v] = u,  vertices[u] = position,  Q_u += Q_v.
+ *   The caller passes remap as the identity and maps the faces through it.
+ * gs_components_step  one hook + compress pass of min-label components over `edges`: parent [V] (the caller starts it as the identity)
+ *   keeps parent[x] <= x; an edge whose endpoints have different roots takes the 32-bit atomic minimum of the smaller root into the
+ *   larger root's parent and sets *changed (cleared first); then every vertex points at its root.  Repeat until *changed stays 0:
+ *   parent[x] is then the smallest vertex index of x's component.  No kernel waits for another workgroup. */
+int gs_simplify_quadrics(int V, int F, const float* vertices, const int32_t* faces, const int32_t* vf_off, const int32_t* vf,
+                         const uint8_t* side_boundary, double boundary_weight, double* quadrics, void* stream);
+int gs_simplify_edge_costs(int V, int E, const float* vertices, const double* quadrics, const int32_t* faces, const int32_t* edges,
+                           const int32_t* edge_faces, const int32_t* edge_opp, const int32_t* nbr_off, const int32_t* nbr,
+                           const int32_t* vf_off, const int32_t* vf, const uint8_t* boundary, double min_normal_dot, float* position,
+                           float* cost, uint8_t* valid, int64_t* key, void* stream);
+int gs_simplify_select(int V, int E, const int32_t* edges, const uint8_t* valid, const int64_t* key, const int32_t* nbr_off,
+                       const int32_t* nbr, uint64_t* claim, uint8_t* winner, void* stream);
+int gs_simplify_apply(int V, int E, int n, const int64_t* selected, const int32_t* edges, const float* position, float* vertices,
+                      double* quadrics, int64_t* remap, void* stream);
+int gs_components_step(int V, int E, const int32_t* edges, int32_t* parent, int32_t* changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
