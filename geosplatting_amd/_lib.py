@@ -154,6 +154,15 @@ def require_cuda(*tensors: torch.Tensor) -> None:
             raise GeoSplatHipError("geosplatting_amd ops run on the GPU only (tensor on %s); there is no CPU path" % t.device)
 
 
+_alloc_workspace = torch.empty               # the one allocator of caller-side scratch; tests swap it to hand out poisoned, guarded blocks
+
+
+def workspace(nbytes: int, device) -> torch.Tensor:
+    """Scratch for a `ws` argument of the C ABI: a 1-D uint8 device tensor of max(nbytes, 1) bytes with UNDEFINED contents -- every
+    entry point writes each segment of its workspace before it reads it (or states the cross-call contract in its header comment)."""
+    return _alloc_workspace(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 _shared_streams = {}
 
 

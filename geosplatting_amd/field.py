@@ -66,13 +66,13 @@ class _HashGrid(torch.autograd.Function):
             if fixed_bytes > budget_bytes:
                 fixed_bytes = 0
         if fixed_bytes:
-            ws = torch.empty(fixed_bytes, dtype=torch.uint8, device=xd.device)
+            ws = _lib.workspace(fixed_bytes, xd.device)
             _lib.check(lib.gs_hashgrid_bwd_fixed(N, L, F, log2_T, sc, _lib.ptr(xd), _lib.ptr(td), _lib.ptr(vo),
                                                  tgs, _lib.ptr(v_table), 0, _lib.ptr(v_x), _lib.ptr(ws),
                                                  fixed_bytes, _lib.stream()), "gs_hashgrid_bwd_fixed")
             return v_x, v_table, None, None, None
         nbytes = lib.gs_hashgrid_bwd_ws_bytes(N, L, F) if mode != "0" else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=xd.device) if nbytes else None
+        ws = _lib.workspace(nbytes, xd.device) if nbytes else None
         _lib.check(lib.gs_hashgrid_bwd(N, L, F, log2_T, sc, _lib.ptr(xd), _lib.ptr(td), _lib.ptr(vo),
                                        tgs, _lib.ptr(v_table), 0, _lib.ptr(v_x), _lib.ptr(ws), nbytes,
                                        _lib.stream()), "gs_hashgrid_bwd")
@@ -107,7 +107,7 @@ class _Linear(torch.autograd.Function):
             N, O, I = xc.shape[0], w.shape[0], w.shape[1]
             gw = torch.empty(O, I, device=w.device)
             nbytes = lib.gs_mlp_wgrad_ws_bytes(N)
-            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=w.device)
+            ws = _lib.workspace(max(nbytes, 4), w.device)
             _lib.check(lib.gs_mlp_wgrad(N, O, I, _lib.ptr(gyc), _lib.ptr(xc), 1.0, _lib.ptr(gw), 0, _lib.ptr(ws),
                                         nbytes, _lib.stream()), "gs_mlp_wgrad")
         return gx, gw

@@ -47,7 +47,7 @@ class _Extract(torch.autograd.Function):
         ws_bytes = lib.gs_flexicubes_ws_bytes(R0, R1, R2)
         if ws_bytes == 0:
             raise _lib.GeoSplatHipError("resolution out of range")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         counts = torch.empty(8, dtype=torch.int64, device=dev)
         _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),
                                            _lib.stream()), "gs_flexicubes_count")
@@ -97,7 +97,7 @@ class _Entropy(torch.autograd.Function):
         if s.numel() != (R0 + 1) * (R1 + 1) * (R2 + 1):
             raise _lib.GeoSplatHipError("sdf_values do not match the grid")
         ws_bytes = lib.gs_flexicubes_ws_bytes(R0, R1, R2)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
+        ws = _lib.workspace(ws_bytes, s.device)
         counts = torch.empty(8, dtype=torch.int64, device=s.device)
         out = torch.empty(1, device=s.device)
         _lib.check(lib.gs_flexicubes_count(R0, R1, R2, _lib.ptr(s), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),

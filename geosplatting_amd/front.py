@@ -62,7 +62,7 @@ def front_stage(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
     fr.tile_counts = torch.empty(tw * th, dtype=torch.int32, device=dev) if (binning and tw * th <= 8192) else None
     fr.packed_index = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if want_packed_index else None
     ws_bytes = lib.gs_front_ws_bytes(N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = L.workspace(ws_bytes, dev)
     L.check(lib.gs_front_fwd(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(normals), L.ptr(kd), L.ptr(ks), L.ptr(viewmat),
                              L.ptr(K), L.ptr(cam_pos), min_roughness, max_metallic, mode, C.byref(env_struct) if env_struct is not None else None, W,
                              H, tile_size, eps2d, near, far, radius_clip, int(key_base) & 0xffffffff, int(key_bits), L.ptr(fr.vis), L.ptr(fr.keys),
@@ -129,14 +129,14 @@ def bin_stage(fr: Front, i_cap: Optional[int], status: Optional[Tensor], prepare
         flat = torch.empty(max(I, 1), dtype=torch.int32, device=dev)
         offsets = torch.empty(th * tw, dtype=torch.int32, device=dev)
         bin_bytes = lib.gs_isect_bin_front_ws_bytes(V, I, tw, th)
-        bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
+        bin_ws = L.workspace(max(bin_bytes, 1), dev)
         L.check(lib.gs_isect_bin_front(V, L.ptr(fr.keys), L.ptr(fr.rects), L.ptr(fr.tile_counts), L.ptr(counts), I, fr.key_bits, tw, th,
                                        L.ptr(flat), L.ptr(offsets), L.ptr(bin_ws), bin_bytes, L.ptr(status) if counts is not None else None,
                                        st), "gs_isect_bin_front")
     if not prepare:
         return dict(flatten_ids=flat, isect_offsets=offsets, counts=counts, keys=fr.keys, rects=fr.rects, tile_counts=fr.tile_counts), V, I
     rws_bytes = lib.gs_raster_ws_bytes(I, V, W, H, tile_size)
-    rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+    rws = L.workspace(rws_bytes, dev)
     if counts is None:
         L.check(lib.gs_raster_prepare_vis(W, H, tile_size, 3, V, L.ptr(fr.vis), I, L.ptr(offsets), L.ptr(flat), L.ptr(rws),
                                           rws_bytes, st), "gs_raster_prepare_vis")
@@ -267,7 +267,7 @@ def texel_grads(env, flat: Optional[Tensor] = None):
 
 def log_ws(I: int, W: int, H: int, dev: torch.device) -> Tensor:
     """The compositor's cull log of one view (what composite_fwd leaves for composite_bwd), on the current stream."""
-    return torch.empty(L.lib().gs_raster_log_ws_bytes(I, W, H, 16), dtype=torch.uint8, device=dev)
+    return L.workspace(L.lib().gs_raster_log_ws_bytes(I, W, H, 16), dev)
 
 
 def composite_fwd(state, V: int, I: int, W: int, H: int, tone: int, exposure: Tensor, log: Tensor):

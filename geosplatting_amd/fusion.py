@@ -121,7 +121,7 @@ class TSDFVolume:
         ws_bytes = lib.gs_tsdf_extract_ws_bytes(R0, R1, R2)
         if ws_bytes == 0:
             raise _lib.GeoSplatHipError("resolution out of range")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        ws = _lib.workspace(ws_bytes, self.device)
         counts = torch.empty(4, dtype=torch.int64, device=self.device)
         _lib.check(lib.gs_tsdf_extract_count(R0, R1, R2, _lib.ptr(self.volume), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),
                                              _lib.stream()), "gs_tsdf_extract_count")

@@ -46,7 +46,7 @@ class PointGrid:
             raise _lib.GeoSplatHipError(f"at most 2^30 points, got {M}")
         dev = self.points.device
         self.grid = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        self._ws = _lib.workspace(ws_bytes, dev)
         self._build()
 
     @property

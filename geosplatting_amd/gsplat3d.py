@@ -240,7 +240,7 @@ class GaussianSet:
         nbytes = lib.gs_densify_ws_bytes(n, int(num_splits))
         if nbytes == 0:
             raise _lib.GeoSplatHipError(f"densify: N={n} / num_splits={num_splits} outside the supported range")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(nbytes, dev)
         totals = torch.empty(4, dtype=torch.int64, device=dev)
         src = {name: getattr(self, name).detach().contiguous() for name in FIELDS}
         opac = src["opacities"].view(-1)

@@ -25,7 +25,7 @@ def _photo_loss_raw(rgb: Tensor, alpha: Tensor, gt_rgba: Tensor, train_bg: Tenso
     v_rgb = torch.empty_like(rgb) if want_grad else None
     v_alpha = torch.empty_like(alpha) if want_grad else None
     nbytes = _lib.lib().gs_photo_loss_ws_bytes(W, H)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=rgb.device)
+    ws = _lib.workspace(nbytes, rgb.device)
     _lib.check(_lib.lib().gs_photo_loss(W, H, _lib.ptr(rgb), _lib.ptr(alpha), _lib.ptr(gt_rgba), int(bool(gt_is_srgb)),
                                         _lib.ptr(train_bg), _lib.ptr(mb), ssim_lambda, mask_weight, grad_scale,
                                         _lib.ptr(out), _lib.ptr(v_rgb), _lib.ptr(v_alpha), _lib.ptr(ws), nbytes,
@@ -129,7 +129,7 @@ def smooth_loss_and_grad(img: Tensor, gt_rgb: Optional[Tensor], kinds, weights, 
         v_img = torch.empty_like(img)
     l = _lib.lib()
     nbytes = l.gs_smooth_loss_ws_bytes(W, H)
-    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=img.device)
+    ws = _lib.workspace(max(nbytes, 4), img.device)
     k = (C.c_int * 3)(*[int(x) for x in kinds])
     w = (C.c_float * 3)(*[float(x) for x in weights])
     _lib.check(l.gs_smooth_loss(W, H, _lib.ptr(img), _lib.ptr(gt), k, w, _lib.ptr(out), _lib.ptr(v_img), _lib.ptr(ws),

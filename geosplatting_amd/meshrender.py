@@ -148,7 +148,7 @@ def rasterize_raw(verts_cam: Tensor, faces32: Tensor, intr, *, cull: str = "none
     ws_bytes = _entry("meshraster_ws_bytes", near_clip)[0](faces32.shape[0], H, W)
     if ws_bytes == 0:
         raise _lib.GeoSplatHipError("mesh or image size out of range (at most 2^24 faces, H W < 2^31)")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=verts_cam.device)
+    ws = _lib.workspace(ws_bytes, verts_cam.device)
     rast = torch.empty(H, W, 4, device=verts_cam.device)
     head = _mesh_head(verts_cam, faces32, intr, near)
     fwd, fwd_name = _entry("meshraster_fwd", near_clip)

@@ -57,7 +57,7 @@ def _splat(points: Tensor, values: Tensor, res: Tuple[int, int, int]) -> Tensor:
     ws_bytes = lib.gs_grid_splat_ws_bytes(C, res[0], res[1], res[2])
     if ws_bytes == 0:
         raise _lib.GeoSplatHipError("resolution or channel count out of range")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=points.device)
+    ws = _lib.workspace(ws_bytes, points.device)
     grid = torch.empty(C, *res, device=points.device)
     _lib.check(lib.gs_grid_splat(N, C, res[0], res[1], res[2], _lib.ptr(points), _lib.ptr(values), _lib.ptr(grid), _lib.ptr(ws), ws_bytes,
                                  _lib.stream()), "gs_grid_splat")
@@ -197,7 +197,7 @@ class _MeshFn(torch.autograd.Function):
         ws_bytes = lib.gs_tsdf_extract_ws_bytes(R2, R1, R0)
         if ws_bytes == 0:
             raise _lib.GeoSplatHipError("resolution out of range")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         counts = torch.empty(4, dtype=torch.int64, device=dev)
         _lib.check(lib.gs_tsdf_extract_count(R2, R1, R0, _lib.ptr(volume), _lib.ptr(ws), ws_bytes, _lib.ptr(counts), _lib.stream()),
                    "gs_tsdf_extract_count")

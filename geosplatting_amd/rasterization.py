@@ -51,7 +51,7 @@ def _project_stage(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tens
     colors_p = torch.empty(N, D, dtype=f32, device=dev) if D > 0 else None
     tpg = torch.empty(N, dtype=i32, device=dev); cum = torch.empty(N, dtype=torch.int64, device=dev)
     ws_bytes = lib.gs_project_ws_bytes(N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = L.workspace(ws_bytes, dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     # the compositor's 64-byte per-visible records come straight out of the projection (colours ride along for D <= 3)
     vis = torch.empty(N, 16, dtype=f32, device=dev) if (0 < D <= 3 and N > 0) else None
@@ -113,12 +113,12 @@ def _bin_stage(pr: _Projected, depth_channel: bool = False):
         L.check(lib.gs_isect_emit(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(cum), tile_size, tw, th,
                                   L.ptr(ids), L.ptr(flat), st), "gs_isect_emit")
         sort_bytes = lib.gs_sort_ws_bytes(I, tw, th)
-        sort_ws = torch.empty(max(sort_bytes, 1), dtype=torch.uint8, device=dev)
+        sort_ws = L.workspace(max(sort_bytes, 1), dev)
         L.check(lib.gs_isect_sort(I, L.ptr(ids), L.ptr(flat), L.ptr(ids_s), L.ptr(flat_s), tw, th, L.ptr(sort_ws),
                                   sort_bytes, st), "gs_isect_sort")
     else:                                                                        # depth-major binning (csrc/gs_sort.hip)
         bin_bytes = lib.gs_isect_bin_ws_bytes(V, I, tw, th)
-        bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
+        bin_ws = L.workspace(max(bin_bytes, 1), dev)
         L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), I, tile_size, tw, th,
                                  L.ptr(ids_s), L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, st), "gs_isect_bin")
     offsets = torch.empty(th * tw, dtype=i32, device=dev)
@@ -136,7 +136,7 @@ def _prepare_stage(state, V: int, I: int, D: int, whs):
     lib = L.lib()
     W, H, tile_size = whs
     rws_bytes = lib.gs_raster_ws_bytes(I, V, W, H, tile_size)
-    rws = torch.empty(rws_bytes, dtype=torch.uint8, device=state["means2d"].device)   # written here, read by fwd AND bwd
+    rws = L.workspace(rws_bytes, state["means2d"].device)   # written here, read by fwd AND bwd
     vis = state.get("vis_records")
     if vis is not None:
         L.check(lib.gs_raster_prepare_vis(W, H, tile_size, D, V, L.ptr(vis), I, L.ptr(state["isect_offsets"]),
@@ -181,7 +181,7 @@ def _bin_stage_cap(pr: _Projected, I_cap: int, status: Tensor, want_ids: bool = 
     st = L.stream()
     flat_s = torch.empty(I_cap, dtype=torch.int32, device=dev)
     bin_bytes = lib.gs_isect_bin_ws_bytes(N, I_cap, tw, th)
-    bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
+    bin_ws = L.workspace(max(bin_bytes, 1), dev)
     offsets = torch.empty(th * tw, dtype=torch.int32, device=dev)
     if want_ids:
         ids_s = torch.empty(I_cap, dtype=torch.int64, device=dev)
@@ -206,7 +206,7 @@ def _prepare_stage_cap(state, V_cap: int, I_cap: int, D: int, whs):
     lib = L.lib()
     W, H, tile_size = whs
     rws_bytes = lib.gs_raster_ws_bytes(I_cap, V_cap, W, H, tile_size)
-    rws = torch.empty(rws_bytes, dtype=torch.uint8, device=state["means2d"].device)
+    rws = L.workspace(rws_bytes, state["means2d"].device)
     L.check(lib.gs_raster_prepare_vis_cap(W, H, tile_size, D, V_cap, L.ptr(state["vis_records"]), I_cap, L.ptr(state["counts"]),
                                           L.ptr(state["isect_offsets"]), L.ptr(state["flatten_ids"]), L.ptr(rws), rws_bytes,
                                           L.stream()), "gs_raster_prepare_vis_cap")

@@ -60,7 +60,7 @@ class MeshBVH:
             raise _lib.GeoSplatHipError(f"at most 2^30 faces, got {F}")
         dev = self.vertices.device
         self.nodes = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        self._ws = _lib.workspace(ws_bytes, dev)
         self._build()
 
     @property

@@ -45,7 +45,7 @@ def specular_bounds(res: int, roughness: float, cutoff: float, device: torch.dev
         b = torch.empty(6, res, res, 24, dtype=torch.float32, device=device)
         # (gs_specular_bounds is the kernel shaped like the reference's SpecularBoundsKernel, 0.2 s at 512^2; tests compare the two)
         nbytes = L.lib().gs_specular_bounds_ws_bytes(res)
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+        ws = L.workspace(max(int(nbytes), 1), device)
         L.check(L.lib().gs_specular_bounds_fast(res, ct, L.ptr(dir_table(res, device)), L.ptr(b), L.ptr(ws), nbytes,
                                                 L.stream()), "gs_specular_bounds_fast")
         _bounds_cache[key] = (ct, b)

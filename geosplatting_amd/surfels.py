@@ -52,7 +52,7 @@ def _project_bin(means, quats, scales, opacities, colors, viewmat, K, W, H, tile
     opac_p = torch.empty(N, dtype=f32, device=dev); colors_p = torch.empty(N, Cn, dtype=f32, device=dev)
     tpg = torch.empty(N, dtype=i32, device=dev)
     ws_bytes = lib.gs_surfel_project_ws_bytes(N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = L.workspace(ws_bytes, dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     st = L.stream()
     L.check(lib.gs_surfel_project_fwd(N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), None if sh else L.ptr(colors), Dc,
@@ -69,7 +69,7 @@ def _project_bin(means, quats, scales, opacities, colors, viewmat, K, W, H, tile
     tw, th = (W + tile_size - 1) // tile_size, (H + tile_size - 1) // tile_size
     ids_s = torch.empty(I, dtype=torch.int64, device=dev); flat_s = torch.empty(I, dtype=i32, device=dev)
     bin_bytes = lib.gs_isect_bin_ws_bytes(V, I, tw, th)
-    bin_ws = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
+    bin_ws = L.workspace(max(bin_bytes, 1), dev)
     L.check(lib.gs_isect_bin(V, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(tpg), I, tile_size, tw, th, L.ptr(ids_s),
                              L.ptr(flat_s), L.ptr(bin_ws), bin_bytes, st), "gs_isect_bin")
     offsets = torch.empty(th * tw, dtype=i32, device=dev)
