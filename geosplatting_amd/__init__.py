@@ -94,6 +94,10 @@ Public surface (mirrors the reference's two call boundaries, SURVEY.md section 8
                                           == the "cropping and simplifying" the reference's README asks of outside tools before the
                                              prior flow: connected components by min-label hooking, and quadric-error decimation run
                                              as rounds of independent edge collapses (no attributes, no gradient, no hole filling)
+  viewmats.requires_grad_() on rasterization / rasterization_3dgs, poseopt.CameraPoseDeltas, GSplatTrainer(pose_opt=True)
+                                          == v_viewmats of gsplat's projection backward and its CameraOptModule (as remembered, not
+                                             pinned): the gradient of the view matrix, summed over the Gaussians in fp64 in a fixed
+                                             order, and camera-pose refinement on it (not for 2DGS, the fused splat() path or Ks)
 Every op calls hand-written HIP kernels in libgeosplat_hip.so through the C-ABI of include/geosplat_hip.h and
 raises if that library is missing -- there is no CPU or PyTorch fallback path.
 """
@@ -118,6 +122,7 @@ from .meshmc import render_mesh_mc  # noqa: F401
 from .meshsimplify import edge_collapse_costs, keep_components, mesh_components, simplify_mesh  # noqa: F401
 from .meshshade import Texture2D, shade_pixels, texture2d  # noqa: F401
 from .occlusion import ambient_occlusion, face_ambient_occlusion  # noqa: F401
+from .poseopt import CameraPoseDeltas, rot6d  # noqa: F401
 from .poisson import (diff_poisson_surface_recon, mesh_from_indicator, mesh_from_oriented_points, poisson_indicator,  # noqa: F401
                       remesh_poisson, sample_grid, splat_to_grid)
 from .rasterization import rasterization, rasterization_3dgs  # noqa: F401

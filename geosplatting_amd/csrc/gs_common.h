@@ -129,6 +129,28 @@ __device__ __forceinline__ unsigned long long gs_wave_sum_u64(unsigned long long
                    c = gs_wave_sum_u32((unsigned)(v >> 42));
     return (unsigned long long)a + ((unsigned long long)b << 21) + ((unsigned long long)c << 42);
 }
+// ... of doubles, in one fixed order (the same tree as gs_wave_sum; a DPP move is 32 bits wide, so the halves travel separately and
+// lanes without a source add +0.0).  Every lane must be active.  Bitwise reproducible: nothing here depends on timing.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double gs_dpp_add_f64(double v)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    return v + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double gs_wave_sum_f64(double v)
+{
+    v = gs_dpp_add_f64<0xB1, 0xf>(v);     // quad_perm [1,0,3,2]
+    v = gs_dpp_add_f64<0x4E, 0xf>(v);     // quad_perm [2,3,0,1]
+    v = gs_dpp_add_f64<0x141, 0xf>(v);    // row_half_mirror
+    v = gs_dpp_add_f64<0x140, 0xf>(v);    // row_mirror
+    v = gs_dpp_add_f64<0x142, 0xa>(v);    // row_bcast:15
+    v = gs_dpp_add_f64<0x143, 0xc>(v);    // row_bcast:31
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 
 // ---- butterfly reduce-scatter over a wave --------------------------------------------------------------
 // Sums NV per-lane values over the 64 lanes in ~3*NV/2 + 6 VALU ops instead of 6*NV: at every stage a lane

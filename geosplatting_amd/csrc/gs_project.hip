@@ -405,3 +405,228 @@ extern "C" int gs_project_bwd_ex(int N, int V, int D, const float* means, const 
     GS_CHECK_LAUNCH();
     return GS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// A7 with the gradient of the view matrix (include/geosplat_hip.h: gs_project_bwd_view).  The per-Gaussian statements are those of
+// gs_project_bwd_body.inc -- same thread-per-input-Gaussian mapping, same calls -- written out here because no lane may leave before
+// the sum.  Every lane of the workgroup carries twelve numbers, row-major [3][4] = (c_R | c_t), zero unless its Gaussian is visible:
+//     c_t = v_mc                       c_R = v_mc m^T + (v_Cc + v_Cc^T) R cov             (mc = R m + t, Cc = R cov R^T)
+//     SH, degree >= 1 (dir = m + R^T t):   c_t += R v_dir,   c_R[i][j] += t[i] v_dir[j]
+// They come from view_terms_one, an evaluation of the chain OF ITS OWN behind a call that is not inlined: the parameter gradients
+// must be the bits of gs_project_bwd_ex, and those depend on how the compiler pairs and contracts the operations of project_bwd_one
+// (SLP packing into v_pk_* and the multiply-adds it then can or cannot fuse).  A first version that took v_mc, v_Cc and R cov out of
+// the one evaluation changed that pairing and with it the last bits of v_means .. v_scales on the MI355X; behind the call the
+// statements below see exactly the operations the other kernels see.  The price is the first two thirds of the chain twice.
+// The sum over N is a store-and-sum: fp64 from the wave level up in one fixed tree (gs_wave_sum_f64, then the four waves through LDS
+// in wave order), one row of twelve doubles per workgroup in the caller's workspace, and project_view_sum_kernel adds the rows in a
+// fixed order and rounds ONCE to fp32.  No float atomics, no arrival order: the same bits every time.
+#define GS_VIEW_BLOCK 256
+#define GS_VIEW_WAVES (GS_VIEW_BLOCK / 64)
+#define GS_VIEW_SUM_LANES 64          // row lanes of the sum kernel: 12 columns x 64 = 768 threads
+#define GS_VIEW_SUM_UNROLL 8
+
+struct ViewWs { double* partial; size_t rows, bytes; };
+static ViewWs view_ws(void* base, int N)
+{
+    GsWs w(base, 16);
+    ViewWs r;
+    r.rows = (size_t)((N + GS_VIEW_BLOCK - 1) / GS_VIEW_BLOCK);
+    r.partial = w.take<double>(12 * (r.rows ? r.rows : 1));
+    r.bytes = w.bytes();
+    return r;
+}
+extern "C" size_t gs_project_bwd_view_ws_bytes(int N) { return N < 0 ? 0 : view_ws(nullptr, N).bytes; }
+
+struct ViewTerms { float c[12]; };
+
+template <bool SH, bool CLASSIC>
+__device__ __noinline__ ViewTerms view_terms_one(const float* __restrict__ viewmat, const float* __restrict__ K, const float* __restrict__ means,
+                                                 const float* __restrict__ quats, const float* __restrict__ scales,
+                                                 const float* __restrict__ opacities, const float* __restrict__ conics,
+                                                 const float* __restrict__ compensations, const float* __restrict__ rec, float v_depth,
+                                                 const float* __restrict__ sh_row, int sh_K, int sh_degree, int n, int v, int W, int H,
+                                                 float eps2d)
+{
+#pragma clang fp contract(fast)
+    const GsCam cam = load_cam(viewmat, K);
+    const float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
+    const float4 q4 = *reinterpret_cast<const float4*>(quats + 4 * (size_t)n);
+    const float scale[3] = { scales[3 * (size_t)n], scales[3 * (size_t)n + 1], scales[3 * (size_t)n + 2] };
+    ProjGrad unused;
+    ProjViewTerms vt;
+    project_bwd_one<true>(cam, mean, q4, scale, CLASSIC ? 0.0f : opacities[n], (float)W, (float)H, eps2d, conics[3 * (size_t)v],
+                          conics[3 * (size_t)v + 1], conics[3 * (size_t)v + 2], CLASSIC ? 1.0f : compensations[v], rec[0], rec[1], rec[2],
+                          rec[3], rec[4], rec[5], v_depth, unused, &vt);
+    ViewTerms o;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float s0 = vt.v_Cc[i * 3 + 0] + vt.v_Cc[0 * 3 + i], s1 = vt.v_Cc[i * 3 + 1] + vt.v_Cc[1 * 3 + i],
+                    s2 = vt.v_Cc[i * 3 + 2] + vt.v_Cc[2 * 3 + i];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            o.c[i * 4 + j] = vt.v_mc[i] * mean[j] + (s0 * vt.T1[0 * 3 + j] + s1 * vt.T1[1 * 3 + j] + s2 * vt.T1[2 * 3 + j]);
+        o.c[i * 4 + 3] = vt.v_mc[i];
+    }
+    if constexpr (SH) {
+        const float v_rgb[3] = { rec[6], rec[7], rec[8] };
+        float vd[3];
+        sh_dir_term(cam, mean, sh_row, sh_K, sh_degree, v_rgb, vd);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) o.c[i * 4 + j] += cam.t[i] * vd[j];
+            o.c[i * 4 + 3] += cam.R[i * 3 + 0] * vd[0] + cam.R[i * 3 + 1] * vd[1] + cam.R[i * 3 + 2] * vd[2];
+        }
+    }
+    return o;
+}
+
+template <bool SH, bool CLASSIC>
+__global__ void __launch_bounds__(GS_VIEW_BLOCK)
+project_bwd_view_kernel(int N, GsCount vc, int D, const float* __restrict__ means, const float* __restrict__ quats,
+                        const float* __restrict__ scales, const float* __restrict__ opacities,
+                        const float* __restrict__ viewmat, const float* __restrict__ K, int W, int H, float eps2d,
+                        const int32_t* __restrict__ gaussian_ids, const float* __restrict__ conics,
+                        const float* __restrict__ compensations, const float* __restrict__ v_packed, int rec_stride,
+                        const float* __restrict__ v_depths, const float* __restrict__ sh_coeffs, int sh_K, int sh_degree,
+                        float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
+                        float* __restrict__ v_opacities, float* __restrict__ v_colors, float* __restrict__ g_sh_coeffs, int accumulate,
+                        double* __restrict__ partial)
+{
+    __shared__ double wave_part[GS_VIEW_WAVES][12];
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    float c[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = 0.0f;
+    if (n < N) {
+        const int V = (int)gs_count(vc);
+        const int v = find_slot(gaussian_ids, V, N, n);
+        float g_mean[3] = { 0, 0, 0 }, g_quat[4] = { 0, 0, 0, 0 }, g_scale[3] = { 0, 0, 0 }, g_op = 0.0f;
+        if (v >= 0) {
+            const GsCam cam = load_cam(viewmat, K);
+            const float mean[3] = { means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2] };
+            const float4 q4 = *reinterpret_cast<const float4*>(quats + 4 * (size_t)n);
+            const float scale[3] = { scales[3 * (size_t)n], scales[3 * (size_t)n + 1], scales[3 * (size_t)n + 2] };
+            const float* __restrict__ rec = v_packed + (size_t)v * rec_stride;   // {xy(2), conic(3), opacity, colors(D)}
+            ProjGrad pg;
+            project_bwd_one(cam, mean, q4, scale, CLASSIC ? 0.0f : opacities[n], (float)W, (float)H, eps2d, conics[3 * (size_t)v],
+                            conics[3 * (size_t)v + 1], conics[3 * (size_t)v + 2], CLASSIC ? 1.0f : compensations[v], rec[0], rec[1], rec[2],
+                            rec[3], rec[4], rec[5], v_depths ? v_depths[v] : 0.0f, pg);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { g_mean[k] = pg.mean[k]; g_scale[k] = pg.scale[k]; }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g_quat[k] = pg.quat[k];
+            g_op = pg.op;
+            if constexpr (SH) {
+                const float v_rgb[3] = { rec[6], rec[7], rec[8] };
+                sh_color_bwd(cam, mean, sh_coeffs + (size_t)n * sh_K * 3, sh_K, sh_degree, true, v_rgb,
+                             g_sh_coeffs + (size_t)n * sh_K * 3, g_mean);
+            }
+        } else if constexpr (SH) {
+            const GsCam cam = load_cam(viewmat, K);
+            const float v_rgb[3] = { 0.f, 0.f, 0.f };
+            sh_color_bwd(cam, nullptr, sh_coeffs + (size_t)n * sh_K * 3, sh_K, sh_degree, false, v_rgb, g_sh_coeffs + (size_t)n * sh_K * 3,
+                         g_mean);
+        }
+        if (accumulate) {
+            if (v >= 0) {
+                v_means[3 * (size_t)n] += g_mean[0]; v_means[3 * (size_t)n + 1] += g_mean[1]; v_means[3 * (size_t)n + 2] += g_mean[2];
+                float4 q = *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n);
+                q.x += g_quat[0]; q.y += g_quat[1]; q.z += g_quat[2]; q.w += g_quat[3];
+                *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n) = q;
+                v_scales[3 * (size_t)n] += g_scale[0]; v_scales[3 * (size_t)n + 1] += g_scale[1]; v_scales[3 * (size_t)n + 2] += g_scale[2];
+                v_opacities[n] += g_op;
+            }
+        } else {
+            v_means[3 * (size_t)n] = g_mean[0]; v_means[3 * (size_t)n + 1] = g_mean[1]; v_means[3 * (size_t)n + 2] = g_mean[2];
+            *reinterpret_cast<float4*>(v_quats + 4 * (size_t)n) = make_float4(g_quat[0], g_quat[1], g_quat[2], g_quat[3]);
+            v_scales[3 * (size_t)n] = g_scale[0]; v_scales[3 * (size_t)n + 1] = g_scale[1]; v_scales[3 * (size_t)n + 2] = g_scale[2];
+            v_opacities[n] = g_op;
+        }
+        if constexpr (!SH) {
+            if (v_colors) {
+                for (int k = 0; k < D; ++k) v_colors[(size_t)n * D + k] = (v >= 0) ? v_packed[(size_t)v * rec_stride + 6 + k] : 0.0f;
+            }
+        }
+        if (v >= 0) {          // after every store of the parameter gradients: nothing of this reaches the statements above
+            const ViewTerms vt = view_terms_one<SH, CLASSIC>(viewmat, K, means, quats, scales, opacities, conics, compensations,
+                                                             v_packed + (size_t)v * rec_stride, v_depths ? v_depths[v] : 0.0f,
+                                                             SH ? sh_coeffs + (size_t)n * sh_K * 3 : nullptr, sh_K, sh_degree, n, v, W, H,
+                                                             eps2d);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) c[k] = vt.c[k];
+        }
+    }
+    // every lane of the workgroup is here (culled and out-of-range lanes carry zeros)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const double s = gs_wave_sum_f64((double)c[k]);
+        if (lane == 0) wave_part[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double s = wave_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < GS_VIEW_WAVES; ++w) s += wave_part[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * 12 + threadIdx.x] = s;
+    }
+}
+
+// One workgroup of 12 x GS_VIEW_SUM_LANES threads: thread (r, k) adds column k of the rows r, r + 64, r + 128, ... in that order
+// (GS_VIEW_SUM_UNROLL independent loads in flight), the 64 row lanes of a column meet in LDS and are added in lane order, and the
+// total is rounded once.  The order depends on `rows` alone.  The last row of the 4 x 4 is written as zeros.
+__global__ void __launch_bounds__(12 * GS_VIEW_SUM_LANES)
+project_view_sum_kernel(const double* __restrict__ partial, long long rows, float* __restrict__ v_viewmat)
+{
+    __shared__ double lane_part[GS_VIEW_SUM_LANES][12];
+    const int k = threadIdx.x % 12, r0 = threadIdx.x / 12;
+    double acc = 0.0;
+    long long r = r0;
+    for (; r + (long long)(GS_VIEW_SUM_UNROLL - 1) * GS_VIEW_SUM_LANES < rows; r += (long long)GS_VIEW_SUM_UNROLL * GS_VIEW_SUM_LANES) {
+        double x[GS_VIEW_SUM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GS_VIEW_SUM_UNROLL; ++u) x[u] = partial[(size_t)(r + (long long)u * GS_VIEW_SUM_LANES) * 12 + k];
+#pragma unroll
+        for (int u = 0; u < GS_VIEW_SUM_UNROLL; ++u) acc += x[u];
+    }
+    for (; r < rows; r += GS_VIEW_SUM_LANES) acc += partial[(size_t)r * 12 + k];
+    lane_part[r0][k] = acc;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double s = 0.0;
+        if (threadIdx.x < 12)
+            for (int l = 0; l < GS_VIEW_SUM_LANES; ++l) s += lane_part[l][threadIdx.x];
+        v_viewmat[threadIdx.x] = (float)s;
+    }
+}
+
+extern "C" int gs_project_bwd_view(int N, int V, int D, const float* means, const float* quats, const float* scales,
+                                   const float* opacities, const float* viewmat, const float* K, int W, int H, float eps2d,
+                                   const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                                   const float* v_packed, int rec_stride, const float* v_depths, const float* sh_coeffs, int sh_K,
+                                   int sh_degree, int flags, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                                   float* v_colors, float* g_sh_coeffs, int accumulate, float* v_viewmat, void* ws, size_t ws_bytes,
+                                   void* stream)
+{
+    if (int rc = check_sh_args(D, nullptr, sh_coeffs, sh_K, sh_degree, flags)) return rc;
+    const bool sh = sh_degree >= 0, classic = (flags & GS_PROJ_CLASSIC) != 0;
+    GS_CHECK_ARG(N >= 0 && V >= 0 && V <= N, "bad sizes");
+    GS_CHECK_ARG(v_viewmat != nullptr && ws != nullptr, "v_viewmat/ws must not be NULL");
+    if (sh) GS_CHECK_ARG(g_sh_coeffs != nullptr && v_colors == nullptr, "SH colours: g_sh_coeffs given, v_colors NULL");
+    const ViewWs w = view_ws(ws, N);
+    if (ws_bytes < w.bytes) { gs_set_error("gs_project_bwd_view: workspace too small"); return GS_ENOSPC; }
+    hipStream_t s = (hipStream_t)stream;
+    if (N > 0) {
+        auto kern = sh ? (classic ? project_bwd_view_kernel<true, true> : project_bwd_view_kernel<true, false>)
+                       : (classic ? project_bwd_view_kernel<false, true> : project_bwd_view_kernel<false, false>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)w.rows), dim3(GS_VIEW_BLOCK), 0, s, N, GsCount{ V, nullptr }, D, means, quats, scales,
+                           opacities, viewmat, K, W, H, eps2d, gaussian_ids, conics, compensations, v_packed,
+                           rec_stride > 0 ? rec_stride : ((6 + D) + 15) / 16 * 16, v_depths, sh_coeffs, sh_K, sh_degree, v_means, v_quats,
+                           v_scales, v_opacities, v_colors, g_sh_coeffs, accumulate, w.partial);
+        GS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(project_view_sum_kernel, dim3(1), dim3(12 * GS_VIEW_SUM_LANES), 0, s, w.partial, (long long)w.rows, v_viewmat);
+    GS_CHECK_LAUNCH();
+    return GS_OK;
+}

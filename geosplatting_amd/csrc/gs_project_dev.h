@@ -193,10 +193,18 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)          // (coun
 // fused tail kernel (gs_front.hip).  (ia, ib, ic) = the conic, comp = the anti-alias compensation of the forward.
 struct ProjGrad { float mean[3], quat[4], scale[3], op; };
 
+// What the gradient of the VIEW MATRIX needs from the chain (gs_project_bwd_view): v_mc, finished (v_depth and the tan-fov clamp routes
+// in it), v_Cc as formed below and T1 = R cov.  The function differentiated is the forward AS IMPLEMENTED -- mc = R m + t,
+// Cc = R cov R^T and, with SH colours of degree >= 1, campos = -R^T t (sh_campos) -- over the twelve entries R, t it reads, not
+// inverse(viewmat): off the rigid manifold the two differ, through any rigid parametrisation they agree (and with upstream's v_viewmats).
+struct ProjViewTerms { float v_mc[3], v_Cc[9], T1[9]; };
+
+// VIEW == false, the default, is the function every kernel before gs_project_bwd_view inlines: `vt` is not touched.
+template <bool VIEW = false>
 __device__ __forceinline__ void project_bwd_one(const GsCam& cam, const float* mean, float4 q4, const float* scale, float opacity,
                                                 float Wf, float Hf, float eps2d, float ia, float ib, float ic, float comp,
                                                 float vm2x, float vm2y, float v_ca, float v_cb, float v_cc, float v_op, float v_depth,
-                                                ProjGrad& g)
+                                                ProjGrad& g, ProjViewTerms* vt = nullptr)
 {
     // a gradient, compared to 1e-4 and not bit for bit: contraction ON (the file default is off), reciprocals by v_rcp_f32
 #pragma clang fp contract(fast)
@@ -288,6 +296,12 @@ __device__ __forceinline__ void project_bwd_one(const GsCam& cam, const float* m
     v_mc[2] += -cam.fx * rz2 * v_J[0] - cam.fy * rz2 * v_J[4] + 2.0f * cam.fx * tx * rz3 * v_J[2]
              + 2.0f * cam.fy * ty * rz3 * v_J[5];
     v_mc[2] += v_depth;
+    if constexpr (VIEW) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) vt->v_mc[i] = v_mc[i];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { vt->v_Cc[i] = v_Cc[i]; vt->T1[i] = T1[i]; }
+    }
 
     const float* R = cam.R;
 #pragma unroll

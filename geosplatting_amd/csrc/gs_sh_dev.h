@@ -216,3 +216,44 @@ __device__ __forceinline__ void sh_color_bwd(const GsCam& cam, const float* mean
     default: sh_color_bwd_row<3>(cam, mean, row, sh_K, vec, visible, v_rgb, g_row, v_mean); break;
     }
 }
+
+// The direction term of sh_color_bwd_row BY ITSELF (gs_project_bwd_view: the gradient of the view matrix needs it apart from v_mean):
+// v_dir = d(sum_ch v_rgb[ch] * rgb[ch]) / d(mean - campos), chained through the normalisation; 0 for degree 0.  An evaluation of its
+// own -- nothing is shared with sh_color_bwd_row, whose instructions, and so the bits of v_mean and g_row, stay what they are.
+template <int DEG>
+__device__ __forceinline__ void sh_dir_term_row(const GsCam& cam, const float* mean, const float* __restrict__ row, bool vec,
+                                                const float* v_rgb, float* v_dir)
+{
+#pragma clang fp contract(fast)
+    v_dir[0] = v_dir[1] = v_dir[2] = 0.0f;
+    if constexpr (DEG >= 1) {
+        constexpr int NB = (DEG + 1) * (DEG + 1), NF = NB * 3;
+        float co[NF], c[3], vb[NB], vc[3];
+        sh_load_row<NF>(row, vec, co);
+        float x, y, z, inorm;
+        sh_dir(cam, mean, x, y, z, inorm);
+        sh_color_deg<DEG>(x, y, z, co, c);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) vc[ch] = (c[ch] + 0.5f >= 0.0f) ? v_rgb[ch] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) vb[k] = co[3 * k] * vc[0] + co[3 * k + 1] * vc[1] + co[3 * k + 2] * vc[2];
+        float vx = 0.f, vy = 0.f, vz = 0.f;
+        sh_basis_vjp<DEG>(x, y, z, vb, vx, vy, vz);
+        const float dotp = vx * x + vy * y + vz * z;
+        v_dir[0] = (vx - dotp * x) * inorm;
+        v_dir[1] = (vy - dotp * y) * inorm;
+        v_dir[2] = (vz - dotp * z) * inorm;
+    }
+}
+
+__device__ __forceinline__ void sh_dir_term(const GsCam& cam, const float* mean, const float* __restrict__ row, int sh_K, int degree,
+                                            const float* v_rgb, float* v_dir)
+{
+    const bool vec = sh_row_vec(row, sh_K);
+    switch (degree) {
+    case 0:  sh_dir_term_row<0>(cam, mean, row, vec, v_rgb, v_dir); break;
+    case 1:  sh_dir_term_row<1>(cam, mean, row, vec, v_rgb, v_dir); break;
+    case 2:  sh_dir_term_row<2>(cam, mean, row, vec, v_rgb, v_dir); break;
+    default: sh_dir_term_row<3>(cam, mean, row, vec, v_rgb, v_dir); break;
+    }
+}

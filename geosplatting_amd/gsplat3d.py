@@ -558,9 +558,16 @@ class GSplatTrainer:
     stop_split_at: int = 15000
     ssim_lambda: float = 0.2
     generator: Optional[torch.Generator] = None          # device generator of the split samples
+    # camera-pose refinement (poseopt.CameraPoseDeltas): off by default, and then no code path or bit changes.  pose_lr / pose_reg
+    # are the defaults of upstream gsplat's trainer AS REMEMBERED (pose_opt_lr = 1e-5, pose_opt_reg = 1e-6): unpinned.
+    pose_opt: bool = False
+    pose_lr: float = 1e-5
+    pose_reg: float = 1e-6
 
     def setup(self, model: GSplatModel, dataset_size: int) -> Dict[str, torch.optim.Adam]:
-        """:57-118: one Adam per field; the exp scheduler (half-life pos_lr_decay) on the means"""
+        """:57-118: one Adam per field; the exp scheduler (half-life pos_lr_decay) on the means.  With pose_opt: one correction per
+        dataset camera and one more Adam (weight_decay = pose_reg) keyed "poses" -- no Gaussian field, so densification and
+        mutate_adam, which go by field name, never touch it."""
         self._dataset_size = int(dataset_size)
         g = model.gaussians
         lrs = {"means": self.base_lr * 0.16, "scales": self.base_lr * 5, "quats": self.base_lr, "colors": self.base_lr * 2.5,
@@ -572,10 +579,18 @@ class GSplatTrainer:
         self.schedulers = {"means": torch.optim.lr_scheduler.LambdaLR(self.optimizers["means"], lr_lambda=lambda s: math.exp(-lam * s))}
         self.refined: List[Tuple[int, str]] = []
         self.last_indices: Optional[Tensor] = None
+        self.pose_deltas = None
+        if self.pose_opt:
+            from .poseopt import CameraPoseDeltas
+            self.pose_deltas = CameraPoseDeltas(self._dataset_size, device=g.device)
+            self.optimizers["poses"] = torch.optim.Adam(self.pose_deltas.parameters(), lr=self.pose_lr, weight_decay=self.pose_reg)
         return self.optimizers
 
-    def step(self, model: GSplatModel, camera: Camera, gt: Tensor) -> Tuple[Tensor, Dict[str, object]]:
-        """:120-151.  gt [H,W,4] (blended over this step's background colour, as RGBAImages.blend) or [H,W,3]."""
+    def step(self, model: GSplatModel, camera: Camera, gt: Tensor, camera_index: Optional[int] = None) -> Tuple[Tensor, Dict[str, object]]:
+        """:120-151.  gt [H,W,4] (blended over this step's background colour, as RGBAImages.blend) or [H,W,3].  With pose_opt and a
+        camera_index (the camera's place in the dataset) the render goes through that camera's corrected pose."""
+        if self.pose_opt and camera_index is not None:
+            camera = self.pose_deltas.camera(camera, camera_index)
         bg = model.get_background_color().to(model.gaussians.device)
         gt = gt.to(model.gaussians.device).clamp(0, 1)
         if gt.shape[-1] == 3:
@@ -622,13 +637,15 @@ class GSplatTrainer:
                                                 num_splits=self.num_splits, cull_alpha_thresh=self.cull_alpha_thresh,
                                                 cull_scale_thresh=scale_thresh, generator=self.generator, optimizers=self.optimizers)
 
-    def train_step(self, model: GSplatModel, camera: Camera, gt: Tensor, *, curr_step: int) -> Tuple[Tensor, Dict[str, object]]:
+    def train_step(self, model: GSplatModel, camera: Camera, gt: Tensor, *, curr_step: int,
+                   camera_index: Optional[int] = None) -> Tuple[Tensor, Dict[str, object]]:
         """One iteration of the reference's loop (rfstudio/engine/train.py:76-112); curr_step counts from 1."""
         for opt in self.optimizers.values():
             opt.zero_grad()
         model.train(True)
         self.before_update(model, curr_step=curr_step)
-        loss, metrics = self.step(model, camera, gt)
+        # (a subclass's step keeps the three-argument form: the index is passed only when one was given)
+        loss, metrics = self.step(model, camera, gt) if camera_index is None else self.step(model, camera, gt, camera_index)
         loss.backward()
         for opt in self.optimizers.values():
             opt.step()

@@ -2,7 +2,7 @@
 rfstudio/model/gsplat.py:334-355 (and :240-261; rfstudio/model/geosplat.py:276-295 with D=14).
 
 Same argument names / meaning / return triple ``(render[1,H,W,D], alpha[1,H,W,1], meta)``; differentiable
-w.r.t. means / quats / scales / opacities / colors.  Every stage runs in libgeosplat_hip.so (hand-written HIP
+w.r.t. means / quats / scales / opacities / colors and, when it requires grad, viewmats (Ks has no gradient).  Every stage runs in libgeosplat_hip.so (hand-written HIP
 for gfx950) through the C-ABI in include/geosplat_hip.h -- there is no PyTorch or CPU fallback.
 """
 from __future__ import annotations
@@ -242,9 +242,10 @@ def _forward_stages(means: Tensor, quats: Tensor, scales: Tensor, opacities: Ten
     return _raster_stage(pr, background, depth_channel)
 
 
-def _project_backward(saved, cfg, st, v_packed: Tensor):
+def _project_backward(saved, cfg, st, v_packed: Tensor, want_viewmat: bool = False):
     """A7 for one view from the compositor's packed gradients v_packed [V, stride]: gradients of (means, quats, scales,
-    opacities, colors); `colors` are the SH coefficients [N, K, 3] when sh_degree is set."""
+    opacities, colors); `colors` are the SH coefficients [N, K, 3] when sh_degree is set.  want_viewmat: through
+    gs_project_bwd_view, which writes the same five and the gradient of the view matrix [4, 4], returned as a sixth (else None)."""
     lib = L.lib()
     W, H, eps2d, V, depth_channel, sh_degree, classic = cfg
     means, quats, scales, opacities, colors, viewmat, K = saved
@@ -259,6 +260,18 @@ def _project_backward(saved, cfg, st, v_packed: Tensor):
     g_scales = torch.empty(N, 3, dtype=f32, device=dev); g_opac = torch.empty(N, dtype=f32, device=dev)
     g_colors = torch.empty_like(colors) if colors is not None else None
     v_depths = v_packed[:, 6 + Dc].contiguous() if depth_channel else None   # grad of the appended depth channel
+    if want_viewmat:
+        g_view = torch.empty(4, 4, dtype=f32, device=dev)
+        ws_bytes = lib.gs_project_bwd_view_ws_bytes(N)
+        ws = L.workspace(ws_bytes, dev)
+        L.check(lib.gs_project_bwd_view(N, V, Dc, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
+                                        L.ptr(K), W, H, eps2d, L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
+                                        L.ptr(st["compensations"]), L.ptr(v_packed), stride, L.ptr(v_depths),
+                                        L.ptr(colors) if sh else None, colors.shape[1] if sh else 0, sh_degree if sh else -1,
+                                        GS_PROJ_CLASSIC if classic else 0, L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales),
+                                        L.ptr(g_opac), None if sh else L.ptr(g_colors), L.ptr(g_colors) if sh else None, 0,
+                                        L.ptr(g_view), L.ptr(ws), ws_bytes, s), "gs_project_bwd_view")
+        return g_means, g_quats, g_scales, g_opac, g_colors, g_view
     if not sh and not classic:
         L.check(lib.gs_project_bwd(N, V, Dc, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
                                    L.ptr(K), W, H, eps2d, L.ptr(st["gaussian_ids_i32"]), L.ptr(st["conics"]),
@@ -272,7 +285,7 @@ def _project_backward(saved, cfg, st, v_packed: Tensor):
                                       GS_PROJ_CLASSIC if classic else 0, L.ptr(g_means), L.ptr(g_quats), L.ptr(g_scales),
                                       L.ptr(g_opac), None if sh else L.ptr(g_colors), L.ptr(g_colors) if sh else None, 0, s),
                 "gs_project_bwd_ex")
-    return g_means, g_quats, g_scales, g_opac, g_colors
+    return g_means, g_quats, g_scales, g_opac, g_colors, None
 
 
 def _raster_backward(W: int, H: int, tile_size: int, D: int, V: int, I: int, st, background, alphas, v_render, v_alphas):
@@ -316,8 +329,8 @@ class _Rasterize(torch.autograd.Function):
         D = render_channels(colors, sh_degree, depth_channel)
         v_packed = _raster_backward(W, H, tile_size, D, V, I, st, background, alphas, v_render, v_alphas)
         grads = _project_backward((means, quats, scales, opacities, colors, viewmat, K),
-                                  (W, H, eps2d, V, depth_channel, sh_degree, classic), st, v_packed)
-        return grads + (None,) * 13
+                                  (W, H, eps2d, V, depth_channel, sh_degree, classic), st, v_packed, ctx.needs_input_grad[5])
+        return grads + (None,) * 12
 
 
 def render_channels(colors: Optional[Tensor], sh_degree: Optional[int], depth_channel: bool) -> int:
@@ -365,8 +378,8 @@ class _ProjectBin(torch.autograd.Function):
         if v_means2d is not None and v_means2d.data_ptr() != v_packed.data_ptr():
             v_packed[:, :2] = v_means2d                       # the caller's own means2d terms, summed by autograd
         st = dict(gaussian_ids_i32=gids, conics=conics, compensations=comps)
-        grads = _project_backward((means, quats, scales, opacities, colors, viewmat, K), ctx.cfg, st, v_packed)
-        return grads + (None,) * 14
+        grads = _project_backward((means, quats, scales, opacities, colors, viewmat, K), ctx.cfg, st, v_packed, ctx.needs_input_grad[5])
+        return grads + (None,) * 13
 
 
 class _Composite(torch.autograd.Function):

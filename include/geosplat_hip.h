@@ -312,6 +312,27 @@ int gs_project_bwd_ex(int N, int V, int D, const float* means, const float* quat
                       int sh_degree, int flags, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
                       float* v_colors, float* g_sh_coeffs, int accumulate, void* stream);
 
+/* gs_project_bwd_ex that also returns the gradient of the view matrix (upstream's v_viewmats; camera-pose refinement): plain colours,
+ * sh_degree 0..3 and GS_PROJ_CLASSIC in one symbol.  v_means .. g_sh_coeffs are the bits gs_project_bwd_ex writes (or adds, with
+ * accumulate != 0).  v_viewmat [16], required: a row-major 4 x 4, ALWAYS a plain write whatever `accumulate` says (a per-view
+ * quantity), last row exactly 0; V == 0 (or N == 0) writes 16 zeros.
+ *   The function differentiated is the forward as implemented, over the twelve entries R[3][3], t[3] of viewmat it reads:
+ *   mc = R m + t, Cc = R cov R^T and, with SH colours of degree >= 1, campos = -R^T t -- NOT inverse(viewmat).  Off the rigid
+ *   manifold the two differ; through any rigid parametrisation of the pose they agree, and agree with upstream.  Per visible
+ *   Gaussian (v_mc, v_Cc: the chain's cotangents of mc and Cc; v_dir: the SH direction term that also enters v_means):
+ *       v_t = v_mc (+ R v_dir),   v_R = v_mc m^T + (v_Cc + v_Cc^T) R cov (+ t v_dir^T);   K has no gradient.
+ *   The sum over the Gaussians is bitwise reproducible: fp64 partial sums in one fixed order (one row of 12 doubles per 256
+ *   Gaussians in ws, then a second small launch), rounded once to fp32; no float atomics.  Every segment of ws is written before it
+ *   is read.  No host wait, no allocation. */
+size_t gs_project_bwd_view_ws_bytes(int N);
+int gs_project_bwd_view(int N, int V, int D, const float* means, const float* quats, const float* scales,
+                        const float* opacities, const float* viewmat, const float* K, int W, int H, float eps2d,
+                        const int32_t* gaussian_ids, const float* conics, const float* compensations,
+                        const float* v_packed, int rec_stride, const float* v_depths, const float* sh_coeffs, int sh_K,
+                        int sh_degree, int flags, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                        float* v_colors, float* g_sh_coeffs, int accumulate, float* v_viewmat /* [16] */, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* ------------------------------------------------------------------ S1..S3 ------------------------- */
 /* Split-sum pyramid description (host struct, device pointers inside). */
 typedef struct GsEnv {
